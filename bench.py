@@ -3,16 +3,19 @@
 
 A step = one pass of the hot path over one batch of synthetic 150-bp reads already
 resident in HBM: empty the set, encode + insert every read, produce keep flags.
-  N = 1 : BASELINE.json configs[1] — 100 M single-end 150 bp reads, ~20 % duplicates (the headline),
-          and beside it in the same JSON line: configs[2] (100 M pairs 2x150 bp, `pe`), the
-          PCIe-inclusive rate (`pcie_inclusive`: sequences start in pinned host memory) and the
+  N = 1 : BASELINE.json configs[1] — 100 M single-end 150 bp reads, ~20 % duplicates (the headline).
+          A plain run sets up, warms up, times --steps steps and prints the line, nothing else.  With --full
+          the line also holds the checks (keep flags == the generator's closed form, == the CPU oracle on a
+          prefix, which is timed as `cpu_baseline`) and beside the headline: configs[2] (100 M pairs 2x150 bp, `pe`),
+          the PCIe-inclusive rate (`pcie_inclusive`: sequences start in pinned host memory) and the
           end-to-end rate of the CLI, FASTQ file in -> FASTQ file out (`end_to_end`; `.gz`: BGZF in, .gz out;
           `.ordinary_gzip`: a gzip file without member sizes in; `end_to_end_unordered` likewise for --unordered).
   N > 1 : weak scaling, the same per-GPU batch on every rank; reads are sharded by hash
           prefix with an all-to-all over RCCL (the library's shard group: csrc/fqd_shard.hip, fastq-dupaway_amd/shard.py).
   --config se|pe|sharded1 : only that device-phase measurement (sharded1 = the N > 1 path
           rehearsed on one rank under RCCL).
-Launch: python bench.py [--gpus N --steps K --warmup W].  With N > 1 and no launcher around it the script
+--dump-outputs DIR : after the timed steps, the keep flags of the last step as .npy files (dump_outputs()).
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full].  With N > 1 and no launcher around it the script
 starts its own N ranks (child processes under torch.distributed.run, before any GPU call) and relays rank 0's
 line; started under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` it is one
 of those ranks.  Prints ONE JSON line (rank 0).
@@ -40,8 +43,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=["all", "se", "pe", "sharded1", "virtual"], default="all",
-                    help="all (default, N=1): headline configs[1] + pe + pcie_inclusive + end_to_end; sharded1: the N > 1 path on one rank under RCCL; "
+                    help="all (default, N=1): headline configs[1], with --full also pe + pcie_inclusive + end_to_end; sharded1: the N > 1 path on one rank under RCCL; "
                          "virtual: --virtual-ranks ranks of the N > 1 path sharing this one GPU (peer copies)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the keep flags and run the CPU baseline and the companion legs (config all); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path computed in its last step (keep flags, float32 / float64 .npy) into DIR")
     ap.add_argument("--virtual-ranks", type=int, default=4)
     ap.add_argument("--round-reads", type=int, default=0, help="reads a rank brings to one round of the sharded exchange (0: 50 Mi — rounds large enough for the owners' partitioned insert — or all of them if fewer)")
     ap.add_argument("--reads", type=int, default=100_000_000, help="reads (pairs) per GPU per step")
@@ -49,10 +56,10 @@ def parse():
     ap.add_argument("--paired", action="store_true", help="same as --config pe")
     ap.add_argument("--dup-permille", type=int, default=200)
     ap.add_argument("--seed", type=int, default=2026)
-    ap.add_argument("--cpu-sample", type=int, default=8_000_000, help="reads timed through the CPU oracle (0 = skip)")
-    ap.add_argument("--pe-cpu-sample", type=int, default=2_000_000, help="pairs of the pe run checked against the CPU oracle")
-    ap.add_argument("--e2e-reads", type=int, default=30_000_000, help="reads of the end-to-end CLI run (0 = skip)")
-    ap.add_argument("--e2e-pairs", type=int, default=4_000_000, help="pairs of the end-to-end --unordered CLI run (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=8_000_000, help="--full: reads timed through the CPU oracle (0 = skip)")
+    ap.add_argument("--pe-cpu-sample", type=int, default=2_000_000, help="--full: pairs of the pe run checked against the CPU oracle")
+    ap.add_argument("--e2e-reads", type=int, default=30_000_000, help="--full: reads of the end-to-end CLI run (0 = skip)")
+    ap.add_argument("--e2e-pairs", type=int, default=4_000_000, help="--full: pairs of the end-to-end --unordered CLI run (0 = skip)")
     ap.add_argument("--e2e-dir", default="", help="where the end-to-end FASTQ files go (default: a temp dir under /tmp)")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--send-hash", type=int, default=-1, help="sharded configs: 1 = every key's placement hash travels with it (FQD_SHARD_SEND_HASH), 0 = the owners hash arrived keys again; default: 1 from 4 ranks on")
@@ -171,8 +178,8 @@ def device_phase(a, torch, dist, dev, local, rank, world, paired, sharded_mode, 
 
     for _ in range(a.warmup):
         step()
-    parity = "skipped"
-    if not a.no_verify:
+    parity = "skipped" if a.full else "not checked (plain run; --full checks the keep flags)"
+    if a.full and not a.no_verify:
         # world == 1: closed-form flags of the generator.  world > 1: copies may point at other
         # ranks' reads, the closed form still holds globally (first occurrence = the non-copy).
         ok = bool(torch.equal(keep, expect)) if a.warmup > 0 else None
@@ -360,7 +367,7 @@ def end_to_end(a, torch, bases, expect, L):
            "what": f"fastq-dupaway -i in.fq -o out.fq --fast -v on {n} reads ({size_in / 1e9:.2f} GB FASTQ, 316 B/record), plain files on {d}, "
                    f"page cache warm (the input was just written), process start-up and output close included; best of 2 runs",
            "size_note": (f"{n} of the workload's {a.reads} reads: the full size needs about 70 GB of scratch files and four more minutes "
-                         f"(python bench.py --e2e-reads {a.reads} [--e2e-dir DIR]; profiles/r03_bench_e2e_100m_reads.json is such a run)") if n < a.reads else "the workload's full size",
+                         f"(python bench.py --full --e2e-reads {a.reads} [--e2e-dir DIR]; profiles/r03_bench_e2e_100m_reads.json is such a run)") if n < a.reads else "the workload's full size",
            "parity": "-v line and output size == closed form" if ok else f"MISMATCH rc={out.returncode} {out.stdout!r} {out.stderr[-300:]!r}"}
     # the CPU baseline SURVEY §8(d) specifies, beside it: the oracle's FILE driver (500 MiB block reader, record parser,
     # base-5/17 keys, std::unordered_set, find-then-insert, survivors written; reference hash_dup_remover.hpp:105-148) on
@@ -575,6 +582,25 @@ def end_to_end_unordered(a, torch, bases, L):
     return res
 
 
+DUMP_SAMPLE = 1 << 22          # flags written one by one; with their indices 48 MB at most
+
+
+def dump_outputs(d, keep, rank, world):
+    """The keep flags of the last timed step, what a caller of the hot path receives, for comparing two builds output
+    for output: every flag when there are at most DUMP_SAMPLE of them, else a fixed sample at seeded indices; and the
+    number of flags kept in every block of 65536 reads, which covers them all."""
+    import numpy as np
+    flags = keep.cpu().numpy()
+    n = len(flags)
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.default_rng(2026).integers(0, n, size=DUMP_SAMPLE))
+    tag = "" if world == 1 else f"rank{rank}_"
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / f"{tag}keep_flags_sample.npy", flags[idx].astype(np.float32))
+    np.save(d / f"{tag}keep_flags_sample_index.npy", idx.astype(np.float64))
+    np.save(d / f"{tag}kept_per_block.npy", np.add.reduceat(flags, np.arange(0, n, 65536), dtype=np.float64))
+
+
 def launch_command(gpus, argv, port):
     """The command `python bench.py --gpus N` (N > 1) turns itself into: one rank per GPU under
     torch.distributed.run, rendezvous on 127.0.0.1 (the container's hostname may not resolve)."""
@@ -669,7 +695,10 @@ def main():
     L = a.read_len
 
     headline_paired = config == "pe" or a.paired
-    res, eng, bases, expect, keep = device_phase(a, torch, dist, dev, local, rank, world, headline_paired, sharded_mode, a.cpu_sample)
+    res, eng, bases, expect, keep = device_phase(a, torch, dist, dev, local, rank, world, headline_paired, sharded_mode,
+                                                 a.cpu_sample if a.full else 0)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, keep, rank, world)
     out = None
     if rank == 0:
         out = {"metric": "Mreads/s dedup, 150 bp %s FASTQ (device phase: sequences resident in HBM)" % ("PE" if headline_paired else "SE"),
@@ -681,7 +710,7 @@ def main():
             out["cpu_baseline"] = res["cpu_baseline"]
         if "per_gpu" in res:
             out["per_gpu"] = res["per_gpu"]
-    if config == "all" and world == 1 and not sharded_mode:
+    if a.full and config == "all" and world == 1 and not sharded_mode:
         # the companions of the headline: a failure in one of them (a full /tmp, say) is reported in its
         # place and never costs the headline line
         def attempt(name, fn):

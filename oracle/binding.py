@@ -21,10 +21,18 @@ _u64p = C.POINTER(C.c_uint64)
 _i64p = C.POINTER(C.c_int64)
 
 
+def _reference_present() -> bool:
+    """The reference's sources are readable (a user who may not look into its parent sees none)."""
+    try:
+        return (REFERENCE / "src" / "seq_utils.cpp").exists()
+    except OSError:
+        return False
+
+
 def build(ref: bool = True) -> None:
     """Compile the restatement, and the reference objects when /root/reference exists."""
     subprocess.run(["make", "-s", "-C", str(HERE), "all"], check=True)
-    if ref and (REFERENCE / "src" / "seq_utils.cpp").exists():
+    if ref and _reference_present():
         subprocess.run(["make", "-s", "-C", str(HERE), "ref"], check=True)
 
 
@@ -199,7 +207,7 @@ def load_oracle() -> Oracle:
 def load_ref():
     so = HERE / "_ref" / "libfqd_ref.so"
     if not so.exists():
-        if (REFERENCE / "src" / "seq_utils.cpp").exists():
+        if _reference_present():
             build(ref=True)
         else:
             return None

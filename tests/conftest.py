@@ -1,7 +1,7 @@
 """pytest plumbing: markers, paths, and loaders for the checker libraries.
 
-`-m "not gpu"` covers the oracle (against golden vectors and, when built, the
-reference objects in oracle/_ref), host logic and the C-ABI's symbol table.
+`-m "not gpu"` covers the oracle (against golden vectors: the reference objects'
+answers, stored under tests/golden), host logic and the C-ABI's symbol table.
 `-m gpu` tests are the parity tests proper and call through the C-ABI.
 Nothing here reads /root/reference at run time.
 """
@@ -38,13 +38,3 @@ def oracle():
     """ctypes handle on oracle/liboracle.so (built on demand with g++)."""
     import oracle_binding
     return oracle_binding.load_oracle()
-
-
-@pytest.fixture(scope="session")
-def reflib():
-    """ctypes handle on oracle/_ref/libfqd_ref.so, or skip when it was never built."""
-    import oracle_binding
-    lib = oracle_binding.load_ref()
-    if lib is None:
-        pytest.skip("oracle/_ref/libfqd_ref.so not built (needs /root/reference)")
-    return lib

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/ref_vectors.json from the REFERENCE'S OWN object code.
+"""Generates tests/golden/ref_vectors.json and ref_fuzz.json from the REFERENCE'S OWN object code.
 
 Run in the build container only (needs /root/reference):
     python tests/golden/make_golden.py
 It builds oracle/_ref/libfqd_ref.so (the reference's seq_utils.cpp, fastqview.cpp,
 fastaview.cpp compiled where they lie) and records its outputs on the inputs
-below.  The JSON holds inputs and expected outputs only — data, no reference text.
+below (ref_vectors.json) and on the seeded inputs of tests/ref_fuzz_cases.py
+(ref_fuzz.json, outputs only).  The JSON holds data only, no reference text.
 """
 import json
 import random
@@ -14,7 +15,9 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[2]
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
 from oracle.binding import FASTA, FASTQ, build, load_ref  # noqa: E402
+import ref_fuzz_cases  # noqa: E402
 
 
 def seqs():
@@ -87,6 +90,14 @@ def main():
     out = Path(__file__).with_name("ref_vectors.json")
     out.write_text(json.dumps(vec, indent=0, separators=(",", ":")))
     print(f"wrote {out}: {len(vec['seq2hash'])} seq2hash, {len(vec['walk'])} walk, {len(vec['cmp_ids'])} cmp_ids")
+    fuzz = {"seq2hash": [ref.seq2hash(s) for s in ref_fuzz_cases.pack_cases()], "walk": [],
+            "cmp_ids": [ref.cmp_ids(a, b, FASTQ) for a, b in ref_fuzz_cases.tag_order_cases()]}
+    for fmt, blk in ref_fuzz_cases.parse_cases():
+        rows, consumed = ref.walk(blk, fmt)
+        fuzz["walk"].append({"records": None if rows is None else rows[:, :3].tolist(), "consumed": consumed})
+    out = Path(__file__).with_name("ref_fuzz.json")
+    out.write_text(json.dumps(fuzz, separators=(",", ":")))
+    print(f"wrote {out}: {len(fuzz['seq2hash'])} seq2hash, {len(fuzz['walk'])} walk, {len(fuzz['cmp_ids'])} cmp_ids")
 
 
 if __name__ == "__main__":

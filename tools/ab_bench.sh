@@ -7,7 +7,7 @@ LIB=fastq-dupaway_amd/lib/libfqdupaway.so
 cp $LIB /tmp/ab_keep.so
 for i in $(seq $N); do for v in A B; do
   if [ $v = A ]; then cp $A $LIB; else cp $B $LIB; fi
-  echo -n "$v: "; timeout -k 10 300 python bench.py --steps 6 --warmup 2 --cpu-sample 0 "$@" 2>/dev/null | python -c "
+  echo -n "$v: "; timeout -k 10 300 python bench.py --full --steps 6 --warmup 2 --cpu-sample 0 "$@" 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
