@@ -15,6 +15,7 @@ HEADER = REPO_ROOT / "include" / "fqdupaway.h"
 OK, ERR_ARG, ERR_HIP, ERR_BAD_BASE, ERR_CAPACITY, ERR_NO_DEVICE = range(6)
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_PROFILE, FLAG_NO_STAGE, FLAG_WEAK_HASH = 1, 2, 4
+SEQ_TIGHT, SEQ_LOOSE, SEQ_HAMMING = 0, 1, 2
 
 
 class FqdError(RuntimeError):
@@ -122,6 +123,8 @@ def load_library():
     L.fqd_key_words.restype = u32
     L.fqd_encode_uniform.argtypes = [vp, C.POINTER(ReadsDesc), u64, vp]
     L.fqd_sort_tags.argtypes = [vp, C.POINTER(TagsDesc), vp]
+    L.fqd_sort_seqs.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp]
+    L.fqd_seq_heads.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp, i32, u32, vp, C.POINTER(u64)]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

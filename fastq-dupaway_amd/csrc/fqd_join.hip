@@ -1018,6 +1018,31 @@ int run_join(fqd_engine* e, const fqd_tags* a, const fqd_tags* b, const fqd_join
 
 } // namespace
 
+// The radix passes above for the sequence sort (csrc/fqd_seq.hip): stable sort of (keys[cur], vals[cur]) by key bits
+// [0, nbits), 8 bits per pass; *cur flips with every pass.  counts holds fqd_internal_radix_counts(N) uint32, tot 256.
+FQD_HIDDEN size_t fqd_internal_radix_counts(uint64_t N) { return size_t(256) * ((N + kSortTile - 1) / kSortTile); }
+FQD_HIDDEN int fqd_internal_radix_sort(fqd_engine* e, hipStream_t stream, uint64_t* const keys[2], uint32_t* const vals[2],
+                                       uint32_t* counts, uint32_t* tot, uint64_t N, uint32_t nbits, int* cur_io)
+{
+    const uint32_t n_tiles = uint32_t((N + kSortTile - 1) / kSortTile);
+    const uint32_t grid = std::min<uint32_t>(n_tiles, 256u * 8u);
+    int cur = *cur_io;
+    for (uint32_t shift = 0; shift < nbits; shift += 8u) {
+        const uint32_t dbits = std::min(8u, nbits - shift), mask = (1u << dbits) - 1u;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(grid), dim3(kBlock), 0, stream,
+                           static_cast<const uint64_t*>(keys[cur]), N, shift, mask, counts, n_tiles);
+        hipLaunchKernelGGL(radix_rowscan_kernel, dim3(256), dim3(1024), 0, stream, counts, n_tiles, tot);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(grid), dim3(kBlock), 0, stream,
+                           static_cast<const uint64_t*>(keys[cur]), static_cast<const uint32_t*>(vals[cur]), N, shift, mask,
+                           static_cast<const uint32_t*>(counts), n_tiles, static_cast<const uint32_t*>(tot),
+                           keys[cur ^ 1], vals[cur ^ 1]);
+        cur ^= 1;
+    }
+    JOIN_TRY(e, hipGetLastError());
+    *cur_io = cur;
+    return FQD_OK;
+}
+
 extern "C" {
 
 int fqd_extract_tags(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, const uint32_t* id_len, uint64_t n,

@@ -237,6 +237,22 @@ class Engine:
         t = self._tags(bytes_, offsets, lengths, n)
         self._check(self._L.fqd_sort_tags(self._h, C.byref(t), self._p(perm)))
 
+    # -- sequence-based modes (--compare-seq) -----------------------------------------------
+    def sort_seqs(self, mate1, perm, mate2=None):
+        """mate1 / mate2 = (bytes, offsets, lengths, n) of the sequences without '\\n'; perm (n uint32) = sorted order."""
+        t1 = self._tags(*mate1)
+        t2 = self._tags(*mate2) if mate2 is not None else None
+        self._check(self._L.fqd_sort_seqs(self._h, C.byref(t1), C.byref(t2) if t2 is not None else None, self._p(perm)))
+
+    def seq_heads(self, mate1, perm, mode: int, distance: int, head, mate2=None) -> int:
+        """head[k] = 1 iff sorted record k is written (mode: SEQ_TIGHT / SEQ_LOOSE / SEQ_HAMMING); returns the number of heads."""
+        t1 = self._tags(*mate1)
+        t2 = self._tags(*mate2) if mate2 is not None else None
+        heads = C.c_uint64(0)
+        self._check(self._L.fqd_seq_heads(self._h, C.byref(t1), C.byref(t2) if t2 is not None else None, self._p(perm), mode, distance,
+                                          self._p(head), C.byref(heads)))
+        return int(heads.value)
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

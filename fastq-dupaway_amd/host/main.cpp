@@ -1,8 +1,9 @@
-// fastq-dupaway (MI355X-native build of the hash-based `--fast` mode).
+// fastq-dupaway (MI355X-native build: the hash-based `--fast` mode and the sequence-based `--compare-seq` modes).
 // Same command line, messages and exit codes as the reference's main.cpp
 // (src/main.cpp:40-262); the options are parsed the way Boost.program_options parses
 // them there (long/short names, --name=value, -xVALUE, unambiguous long prefixes).
-// Sequence-based modes are not part of this build and are refused with a clear message.
+// A bare invocation (neither --fast nor --compare-seq) is refused: the reference's default is the sequence-based mode
+// under a memory limit (-m), which this build does not honour; --compare-seq opts in.
 // Environment (extensions, none needed): FQD_DEVICE=<ordinal>, FQD_FULL_JOIN=1 (intended
 // full inner join for --unordered instead of the reference's end-of-file rule),
 // FQD_BLOCK_MB=<input block size>, FQD_DEVICES=<ordinal,ordinal,...> (one engine per listed GPU, reads
@@ -18,6 +19,7 @@
 
 #include "hash_dup_remover.hpp"
 #include "multi_gpu.hpp"
+#include "seq_dup_remover.hpp"
 
 namespace {
 
@@ -34,9 +36,11 @@ const OptSpec kSpecs[] = {
     {"output-2", 'p', true, "Second output file (optional, required for paired-end mode)"},
     {"mem-limit", 'm', true, "Memory limit in megabytes (default 2048 = 2Gb).\nSupported value range is [500 <-> 10240 (10 Gb)]\n"
                              "Actual memory usage may slightly exceed this value.\n"
-                             "NB: The 'fast' deduplication mode does not support strict memory limitation."},
+                             "NB: The 'fast' deduplication mode does not support strict memory limitation.\n"
+                             "NB: This build keeps the inputs in GPU memory in every mode: -m does not bound it."},
     {"format", 0, true, "input file format: fastq (default) or fasta."},
-    {"compare-seq", 0, true, "Sequence comparison mode for deduplication step (sequence-based modes; not part of the MI355X build)."},
+    {"compare-seq", 0, true, "Sequence comparison mode for deduplication step: tight, loose or tail-hamming.\n"
+                             "Runs the sequence-based mode on one GPU; required for it in this build."},
     {"distance", 0, true, "A threshold value for 'tail-hamming' distance calculation (sequence-based modes)."},
     {"write-clusters", 0, false, "Write ids of identified duplicate clusters to a file (sequence-based modes only)."},
     {"fast", 0, false, "Use hash-based approach instead of sequence-based.\nIn this mode the program will run significantly faster, "
@@ -153,6 +157,7 @@ struct Options {                                               // main.cpp:28-38
     int mode = BASE;
     ssize_t memLimit = 2L * 1024L * 1024L * 1024L;
     std::string input_1, input_2, output_1, output_2;
+    std::string compare_seq;                                   // "" = not given (the sequence-based run is opt-in)
     unsigned hammdist = 2;
     bool unordered = false, verbose = false, write_clusters = false;
 };
@@ -190,6 +195,7 @@ bool parse_args(int argc, char** argv, Options& opts)          // main.cpp:40-17
         if (count("compare-seq")) {                                                                  // :123-134
             const std::string& v = vm.values.at("compare-seq");
             if (v != "tight" && v != "loose" && v != "tail-hamming") throw std::runtime_error("Unsupported compare-seq type provided!");
+            opts.compare_seq = v;
         }
         if (count("mem-limit")) {                                                                    // :137-144
             if (mem_value >= 500L && mem_value <= 10240L) opts.memLimit = mem_value * 1024L * 1024L;
@@ -229,9 +235,11 @@ int main(int argc, char** argv)                                // main.cpp:181-2
     Options opts;
     if (!parse_args(argc, argv, opts)) return 1;
     try {
-        if (!(opts.mode & HASH))
-            throw std::runtime_error("this build implements the hash-based --fast mode only (MI355X engine); "
-                                     "run the sequence-based modes with the reference fastq-dupaway");
+        // The reference's bare mode is the sequence-based one under a memory limit (-m) this build does not honour:
+        // the sequence-based run is taken only when --compare-seq is given.
+        if (!(opts.mode & HASH) && opts.compare_seq.empty())
+            throw std::runtime_error("no deduplication mode chosen: this build runs the --fast mode only unless "
+                                     "--compare-seq tight|loose|tail-hamming is given");
         fqdhost::Tuning tune;
         if (const char* d = std::getenv("FQD_DEVICE")) tune.device = std::atoi(d);
         tune.devices = fqdhost::devices_from_env();
@@ -241,6 +249,14 @@ int main(int argc, char** argv)                                // main.cpp:181-2
         tune.leave_memory_to_exit = std::getenv("FQD_FREE_AT_END") == nullptr;   // the process ends after this run
         fqdhost::TemporaryDirectory tempdir;                   // main.cpp:192 (created lazily here)
         const fqdhost::Format fmt = (opts.mode & FASTA) ? fqdhost::Format::Fasta : fqdhost::Format::Fastq;
+        if (!(opts.mode & HASH)) {                             // main.cpp:194-216
+            const fqdhost::CompareSeq cmp = opts.compare_seq == "tight" ? fqdhost::CompareSeq::Tight
+                                          : opts.compare_seq == "loose" ? fqdhost::CompareSeq::Loose : fqdhost::CompareSeq::Hamming;
+            fqdhost::SeqDupRemover remover(fmt, opts.memLimit, cmp, opts.hammdist, opts.write_clusters, opts.verbose, tune);
+            if (opts.mode & PAIRED) remover.filterPE(opts.input_1, opts.input_2, opts.output_1, opts.output_2);
+            else                    remover.filterSE(opts.input_1, opts.output_1);
+            return 0;
+        }
         fqdhost::HashDupRemover remover(fmt, opts.memLimit, &tempdir, opts.verbose, tune);   // main.cpp:218-242
         if (opts.mode & PAIRED) remover.filterPE(opts.input_1, opts.input_2, opts.output_1, opts.output_2, opts.unordered);
         else                    remover.filterSE(opts.input_1, opts.output_1);

@@ -463,6 +463,29 @@ int  fqd_count_lines(fqd_engine* e, const uint8_t* text, uint64_t n, uint64_t* n
 int  fqd_scan_records(fqd_engine* e, const uint8_t* text, uint64_t n, uint32_t lines_per_record, uint64_t n_records,
                       uint64_t* start, uint64_t* seq_off, uint32_t* id_len, uint32_t* seq_len, uint32_t* size, int* well_formed);
 
+/* ---- the sequence-based modes (`--compare-seq`; seq_dup_remover.hpp:40-218) ---------------------------------------
+ * The reference sorts every record (pair) by sequence on disk (ExternalSorter<T> / PairedExternalSorter<T>,
+ * paired_external_sort.hpp:20-33,128-135) and walks the sorted file with one comparator (comparator.cpp:45-91).  Here
+ * both happen where the records lie in HBM (csrc/fqd_seq.hip, rules in csrc/fqd_seq_core.hpp).  A record's sequence is
+ * given as an fqd_tags entry WITHOUT its '\n'; for pairs mate2 has mate1's n (NULL: single-end).  Device pointers. */
+#define FQD_SEQ_TIGHT       0
+#define FQD_SEQ_LOOSE       1
+#define FQD_SEQ_HAMMING     2   /* `tail-hamming` */
+
+/* perm[k] (n uint32) = index of the record (pair) with the k-th smallest sequence in the order of FastqView::cmp
+ * (fastqview.cpp:56-67: bytewise over the shorter length with the '\n' counted, shorter first on a tie; pairs by mate 1,
+ * then mate 2 — RecordPair::operator<).  Equal sequences keep their input order (the reference's order among them is an
+ * artefact of std::sort and its chunking).  Any length; n < 2^31.  A sequence byte below '\n' (NUL, control bytes) is
+ * refused with FQD_ERR_ARG: it would make strncmp and byte order disagree.  Returns after the stream has drained. */
+int  fqd_sort_seqs(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, uint32_t* perm);
+
+/* head[k] (n bytes) = 1 iff the k-th record of perm is written by the reference's scan over the sorted records
+ * (seq_dup_remover.hpp:54-109,131-218) with comparator `mode` (FQD_SEQ_*; `distance` for FQD_SEQ_HAMMING, ignored
+ * otherwise); 0 = a duplicate of the last head before it.  *n_heads (host, may be NULL) = number of heads.  perm must
+ * be an order of fqd_sort_seqs (loose mode relies on it).  Returns after the stream has drained. */
+int  fqd_seq_heads(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, const uint32_t* perm, int mode, uint32_t distance,
+                   uint8_t* head, uint64_t* n_heads);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
