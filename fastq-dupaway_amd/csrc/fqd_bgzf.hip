@@ -13,22 +13,12 @@
 #include <algorithm>
 #include <cstring>
 
-#include "../../include/fqdupaway.h"
 #include "fqd_bgzf_core.hpp"
-
-#define FQD_HIDDEN __attribute__((visibility("hidden")))
-FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_device(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg);
-FQD_HIDDEN int fqd_internal_scratch(fqd_engine* e, int which, size_t bytes, void** out);
+#include "fqd_internal.hpp"
 
 namespace {
 
 using namespace fqd::bgzf;
-
-#define BGZF_TRY(e, expr)                                                                   \
-    do { hipError_t err_ = (expr); if (err_ != hipSuccess) { (void)hipGetLastError();       \
-        return fqd_internal_fail(e, FQD_ERR_HIP, hipGetErrorString(err_)); } } while (0)
 
 struct DeviceOr {
     __device__ void operator()(uint32_t* p, uint32_t v) const { if (v) atomicOr(p, v); }
@@ -287,7 +277,7 @@ int fqd_bgzf_deflate(fqd_engine* e, const uint8_t* src, uint64_t n, uint32_t lin
     if (n == 0) return FQD_OK;
     if (dst_capacity < fqd_bgzf_bound(n))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_bgzf_deflate: dst_capacity below fqd_bgzf_bound(n)");
-    BGZF_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const uint64_t members = (n + kMember - 1) / kMember;
 
@@ -308,27 +298,27 @@ int fqd_bgzf_deflate(fqd_engine* e, const uint8_t* src, uint64_t n, uint32_t lin
     uint8_t* d_slots = at;
 
     const uint32_t grid = uint32_t(std::min<uint64_t>(members, 2048));
-    BGZF_TRY(e, hipMemsetAsync(d_hist, 0, hist_bytes, stream));
-    BGZF_TRY(e, hipMemsetAsync(d_slots, 0, slots_bytes, stream));
+    FQD_TRY(e, hipMemsetAsync(d_hist, 0, hist_bytes, stream));
+    FQD_TRY(e, hipMemsetAsync(d_slots, 0, slots_bytes, stream));
     hipLaunchKernelGGL(bgzf_count_kernel, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record, d_hist);
-    BGZF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     uint64_t hist[kLitLen + kDist];
-    BGZF_TRY(e, hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, stream));
-    BGZF_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     static thread_local Codes codes;
     build_codes(hist, members, codes);
-    BGZF_TRY(e, hipMemcpyAsync(d_codes, &codes, sizeof codes, hipMemcpyHostToDevice, stream));
+    FQD_TRY(e, hipMemcpyAsync(d_codes, &codes, sizeof codes, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(bgzf_emit_kernel, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record,
                        static_cast<const Codes*>(d_codes), d_slots, d_sizes);
-    BGZF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(bgzf_offsets_kernel, dim3(1), dim3(1024), 0, stream, static_cast<const uint32_t*>(d_sizes), members, d_offs, d_offs + members);
-    BGZF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(bgzf_compact_kernel, dim3(grid), dim3(256), 0, stream, static_cast<const uint8_t*>(d_slots),
                        static_cast<const uint32_t*>(d_sizes), static_cast<const uint64_t*>(d_offs), members, dst);
-    BGZF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     uint64_t total = 0;
-    BGZF_TRY(e, hipMemcpyAsync(&total, d_offs + members, sizeof total, hipMemcpyDeviceToHost, stream));
-    BGZF_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&total, d_offs + members, sizeof total, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     *out_bytes = total;
     return FQD_OK;
 }

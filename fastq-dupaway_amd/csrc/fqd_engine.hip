@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/fqdupaway.h"
+#include "fqd_internal.hpp"
 #include "fqd_kernels.hpp"
 
 using namespace fqd;
@@ -604,7 +604,6 @@ bool seg_is_uniform(const fqd_reads& r) { return r.offsets == nullptr && r.lengt
 } // namespace
 
 // ---- what fqd_join.hip needs from an engine (same library, not exported) -----------------
-#define FQD_HIDDEN __attribute__((visibility("hidden")))
 FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e) { return e->stream; }
 FQD_HIDDEN int fqd_internal_device(fqd_engine* e) { return e->device; }
 FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg) { return e->fail(code, msg); }

@@ -15,6 +15,8 @@
 //   gz_windows_chain_kernel once), then the windows themselves unit after unit, the running window in LDS;
 //   gz_resolve_kernel       every place of every unit becomes a byte: one workgroup per unit, sixteen places a lane and step;
 //   gz_crc_kernel           CRC-32 of every 64 KiB of the text; the host folds them (one 32 x 32 bit matrix per fold).
+// The host side is GunzipRun, the state of one call and its steps: set_up / place, then batch after batch see_what_arrived, take_in,
+// next_batch, decode_batch, repair_in_one_launch, walk_chain, windows_and_bytes, at the end check_members; the entry point is the loop.
 // Anything irregular — a chain of unit ends and starts that does not close, damaged data, a unit that outgrows its room,
 // CRC or length that differ from the trailer — is only REPORTED (ok = 0): the caller reads the file the host way, whose
 // diagnostics are the reference's.
@@ -29,23 +31,18 @@
 #include <vector>
 #include <unistd.h>
 
-#include "../../include/fqdupaway.h"
 #include "fqd_gunzip_core.hpp"
 #include "fqd_inflate_wave.hpp"
-
-#define FQD_HIDDEN __attribute__((visibility("hidden")))
-FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_device(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg);
-FQD_HIDDEN int fqd_internal_scratch(fqd_engine* e, int which, size_t bytes, void** out);
+#include "fqd_internal.hpp"
 
 namespace {
 
 using namespace fqd::gunz;
+using fqd::winf::WaveCtx;
 
-#define GZ_TRY(e, expr)                                                                     \
-    do { hipError_t err_ = (expr); if (err_ != hipSuccess) { (void)hipGetLastError();       \
-        return fqd_internal_fail(e, FQD_ERR_HIP, hipGetErrorString(err_)); } } while (0)
+// FQD_GUNZIP_TRACE: the stages to stderr as they are reached (inside GunzipRun, below: its trace, stream and t_begin)
+#define GZ_TRACE(...) do { if (trace) { (void)hipStreamSynchronize(stream); std::fprintf(stderr, "[gunzip %7.2f ms] ", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count()); \
+    std::fprintf(stderr, __VA_ARGS__); std::fputc('\n', stderr); std::fflush(stderr); } } while (0)
 
 constexpr uint32_t kWave = 64;
 
@@ -134,18 +131,6 @@ void gz_find_starts_kernel(BitIn in, uint64_t unit_bits, uint64_t first_unit, ui
 // of the one-lane decoder this kernel replaced (csrc/fqd_gunzip_core.hpp, kept as the CPU reference form: 4.6 GB/s of text).
 struct UnitIn  { uint64_t start_bit, stop_bit, at, cap; };                   // where to start, the next unit's nominal start, the unit's place in a plane, room behind the window
 struct UnitOut { uint64_t end_bit, n; uint32_t status, how; };               // how: 1 a boundary, 2 the final block's end
-
-struct WaveCtx {                                                             // the wave as fqd_inflate_wave.hpp sees it (as in fqd_inflate.hip)
-    static constexpr uint32_t kLanes = kWave;
-    uint32_t lane;
-    template <class F> __device__ __forceinline__ void lanes(F f) { f(lane); __syncthreads(); }
-    template <class F> __device__ __forceinline__ void lanes_open(F f) { f(lane); }
-    __device__ __forceinline__ void sync() { __syncthreads(); }
-    template <class F> __device__ __forceinline__ uint64_t ballot(F f) { return __ballot(f(lane) ? 1 : 0); }
-    __device__ __forceinline__ uint32_t same(uint32_t v) const { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-    __device__ __forceinline__ void add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-    __device__ __forceinline__ void mark(int) {}
-};
 
 __device__ __forceinline__ uint32_t made_up(uint32_t plane, uint32_t w) { return plane ? ((w & 255u) ^ (1u + (w >> 8))) : (w & 255u); }
 
@@ -388,9 +373,417 @@ uint32_t advance_zero_bytes(uint32_t reg, uint64_t n)
     return reg;
 }
 
-struct View {                                                                // a piece of the engine's scratch (below)
-    void* p = nullptr;
-    template <class T> T* as() const { return static_cast<T*>(p); }
+// What follows a member's final block: its trailer (CRC-32, ISIZE) and the end of the file, or the header of another member (RFC 1952).
+struct Trailer { uint32_t crc = 0, isize = 0; int kind = 0; /* 0 neither, 1 the file ends, 2 another member */ uint64_t next_start = 0; };
+struct Member { uint64_t text_from, text_to, deflate_end; uint32_t crc, isize; };
+
+// One call of fqd_gunzip_arriving: its state, and the steps the entry point strings together.  Every step returns the call's
+// status (FQD_OK or what failed); what it FOUND is in the verdict members.
+struct GunzipRun {
+    // ---- the call: its arguments, and what set_up() works out from them and the environment
+    fqd_engine* const e; const hipStream_t stream; const int n_cu;
+    const uint8_t* const deflate; const uint64_t avail_bytes; const volatile uint64_t* const arrived;
+    uint8_t* const text; const uint64_t text_cap;
+    const bool trace; const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    BitIn in;
+    uint64_t unit_bytes = 0, ratio = 8;                                      // ratio: symbols of room per compressed byte (FASTQ packs 3-6 fold)
+    uint64_t n_nominal = 0, one_more = 0;                                    // units of unit_bytes in the stream; the room of a unit of one nominal unit
+    uint32_t decoders = 0;                                                   // waves a launch of the decoder runs at most
+    uint64_t plane_bytes = 0, nb_cap = 0;                                    // per plane; units a batch can hold
+    // ---- the pieces of the engine's scratch (place)
+    uint8_t *d_p = nullptr, *d_q = nullptr, *d_windows = nullptr; fqd::winf::Token* d_tokens = nullptr; uint16_t* d_maps = nullptr;
+    UnitIn *d_units = nullptr, *d_ru = nullptr; UnitOut *d_result = nullptr, *d_rr = nullptr;     // the batch; the units decoded again in one launch
+    uint64_t *d_text_at = nullptr, *d_start = nullptr; uint32_t *d_counter = nullptr, *d_shift = nullptr, *d_raw = nullptr;
+    // ---- the units: every nominal unit's block start, the units made of them, and how far that has got
+    std::vector<uint64_t> start; std::vector<UnitIn> units;
+    uint64_t searched = 0, built = 0;                                         // nominal units looked at for a start / turned into units
+    size_t at = 0;                                                            // units the chain has taken
+    // ---- the batch in hand: units [at, hi), nb of them (those put in between included), `used` bytes of a plane
+    size_t hi = 0; uint32_t nb = 0; uint64_t used = 0;
+    std::vector<UnitOut> result; std::vector<uint64_t> text_at;             // what the units decoded to; where their text goes
+    // ---- where the chain stands
+    uint64_t expect_start = 0, total = 0, member_from = 0;
+    bool member_end_before = false;                                           // the unit the chain took last ended a member
+    std::vector<Member> members;
+    std::vector<uint8_t> carry = std::vector<uint8_t>(kWindow, 0);            // the window before the next batch's first unit
+    // ---- arrival
+    uint64_t have = 0; bool all_there = false;                                // bytes of the stream a batch may count on
+    uint64_t wait_beyond = 0;                                                // nothing to do until more than this has arrived
+    // ---- verdict
+    bool good = true, final_seen = false, hopeless = false;                  // hopeless: left to the host reader (*ok stays 0), as !good is
+    uint64_t repairs = 0;
+    std::unordered_map<uint64_t, Trailer> trailers;                          // by byte offset: looked at twice (below), fetched once
+
+    static uint64_t room_of(const UnitIn& x) { return uint64_t(kWindow) + x.cap + 64u; }          // made-up window, text, slack (a multiple of 16)
+    // what lies behind a final block (trailer, perhaps a header of up to a kilobyte) can be looked at
+    bool trailer_there(uint64_t end_bit) const { return all_there || (end_bit + 7u) / 8u + 8u + 1024u <= have; }
+    uint64_t have_now() const { if (!arrived) return avail_bytes; const uint64_t a = *arrived; return a < avail_bytes ? a : (a == ~0ull ? ~0ull : avail_bytes); }
+
+    GunzipRun(fqd_engine* e_, int n_cu_, const uint8_t* deflate_, uint64_t avail_, const volatile uint64_t* arrived_, uint8_t* text_, uint64_t text_cap_, bool trace_)
+        : e(e_), stream(fqd_internal_stream(e_)), n_cu(n_cu_), deflate(deflate_), avail_bytes(avail_), arrived(arrived_), text(text_), text_cap(text_cap_), trace(trace_) {}
+
+    int set_up()
+    {
+        const uintptr_t addr = reinterpret_cast<uintptr_t>(deflate);
+        in.words = reinterpret_cast<const uint64_t*>(addr & ~uintptr_t(7));
+        in.lead = uint64_t(addr & 7u) * 8u;
+        in.nbits = avail_bytes * 8u;
+
+        // units: small enough that there are several per wave slot of the chip, large enough to hold a block start more often than
+        // not (zlib ends a block every 16 K codes: some 20-50 KB packed).  (Measured and replaced on the way here, DESIGN §3b: one
+        // serial decoder per wave writing 16-bit symbols, all lanes running it alike — 4.6 GB/s of text; the same, one decoder per
+        // LANE with its tables in HBM — 2.6 GB/s: lanes of a wave that copy matches of different lengths wait for the longest.)
+        // Large files: some 16 K units of at most 256 KiB — a unit that has to be decoded again is ONE wave's work (11 MB/s of packed bytes
+        // when it runs alone), the chip's 4096 decoders are filled in whole rounds, and the windows' chain costs 2 us a unit.
+        unit_bytes = std::min<uint64_t>(256u << 10, std::max<uint64_t>(64u << 10, (avail_bytes / 16384u + 4095u) & ~uint64_t(4095)));
+        if (const char* v = std::getenv("FQD_GUNZIP_UNIT_KB")) { const long kb = std::atol(v); if (kb > 0) unit_bytes = uint64_t(kb) << 10; }
+        if (const char* v = std::getenv("FQD_GUNZIP_RATIO")) { const long r = std::atol(v); if (r > 0) ratio = uint64_t(r); }
+        n_nominal = (avail_bytes + unit_bytes - 1) / unit_bytes;
+
+        // ---- 2-5 in batches of units whose two planes fit the scratch: by default up to two rounds of the chip's decoders (a wave a unit)
+        one_more = uint64_t(kWindow) + ((2u * unit_bytes * ratio + 1024u + 15u) & ~uint64_t(15)) + 64u;
+        decoders = uint32_t(std::min<uint64_t>(n_nominal, uint64_t(n_cu) * 16u));                         // a wave a unit; 10 KB of LDS, <= 128 VGPRs: sixteen waves a CU
+        plane_bytes = std::min<uint64_t>(uint64_t(8) << 30, (2u * decoders + 64u) * one_more);            // per plane: two rounds if 8 GiB hold them (two back to back take less than twice one)
+        if (const char* v = std::getenv("FQD_GUNZIP_SCRATCH_MB")) { const long mb = std::atol(v); if (mb > 0) plane_bytes = (uint64_t(mb) << 20) / 2; }
+        plane_bytes = std::min(plane_bytes, n_nominal * one_more + 64u * one_more);                       // (never more than all units need)
+        if (const int rc = place()) return rc;
+        start.assign(n_nominal, ~0ull);
+        GZ_TRACE("%llu bytes, %llu units of %llu bytes; scratch: 2 planes of %llu bytes, %u decoders' tokens", (unsigned long long)avail_bytes, (unsigned long long)n_nominal,
+                 (unsigned long long)unit_bytes, (unsigned long long)plane_bytes, decoders);
+        return FQD_OK;
+    }
+
+    // ONE piece of the engine's scratch holds everything the call needs on the device, and stays with the engine: a call that
+    // frees gigabytes hands them to the driver for clearing, and the process's next hipMalloc — the dedup engine's key store, the
+    // other file's planes — waits for that (configs[4] shape, two files at once: a second lost in whatever stage came next).
+    int place()
+    {
+        nb_cap = plane_bytes / one_more + 32u;
+        auto carve = [this](Carver c) {
+            d_p = c.take<uint8_t>(plane_bytes + 64); d_q = c.take<uint8_t>(plane_bytes + 64);
+            d_tokens = c.take<fqd::winf::Token>(size_t(decoders) * fqd::winf::kTokenRoom);
+            d_maps = c.take<uint16_t>(nb_cap * kWindow); d_windows = c.take<uint8_t>((nb_cap + 1u) * kWindow);
+            d_units = c.take<UnitIn>(nb_cap); d_result = c.take<UnitOut>(2u * nb_cap); d_text_at = c.take<uint64_t>(nb_cap);
+            d_ru = c.take<UnitIn>(nb_cap); d_rr = c.take<UnitOut>(2u * nb_cap);
+            d_counter = c.take<uint32_t>(16); d_start = c.take<uint64_t>(n_nominal); d_shift = c.take<uint32_t>(8 * 32); d_raw = c.take<uint32_t>(text_cap / kSlice + 2u);
+            return c.used;
+        };
+        void* base = nullptr;
+        const int rc = fqd_internal_scratch(e, 1, carve(Carver{nullptr}), &base);
+        if (rc != FQD_OK) return rc;
+        carve(Carver{static_cast<char*>(base)});
+        return FQD_OK;
+    }
+
+    // What has arrived by now (fqd_gunzip_arriving: the file is still being copied to HBM by another thread of the caller, which
+    // raises *arrived as its copies complete; everything below works on what is there and waits for the rest, so that block
+    // starts are found and units decoded under the read).  false: nothing to do in this turn of the loop.
+    bool see_what_arrived()
+    {
+        have = have_now();
+        if (have == ~0ull) { GZ_TRACE("the caller says the rest of the file will not come"); good = false; return false; }
+        all_there = have == avail_bytes;
+        if (!all_there && have <= wait_beyond) { ::usleep(100); return false; }
+        return true;
+    }
+
+    // ---- 1. starts, and the units they make — of what has ARRIVED
+    int take_in()
+    {
+        // a unit is looked at when it and what the looks read beyond a position (a block header: some hundred bytes) have arrived
+        const uint64_t can = have == avail_bytes ? n_nominal : (have > 4096u ? (have - 4096u) / unit_bytes : 0u);
+        if (can > searched) {
+            hipLaunchKernelGGL(gz_find_starts_kernel, dim3(uint32_t(std::min<uint64_t>(can - searched, uint64_t(n_cu) * 16u))), dim3(kWave), 0, stream,
+                               in, unit_bytes * 8u, searched, can, d_start);
+            FQD_TRY(e, hipGetLastError());
+            FQD_TRY(e, hipMemcpyAsync(start.data() + searched, d_start + searched, (can - searched) * 8, hipMemcpyDeviceToHost, stream));
+            FQD_TRY(e, hipStreamSynchronize(stream));
+            GZ_TRACE("%llu of %llu bytes there: block starts of units %llu to %llu looked for", (unsigned long long)have, (unsigned long long)avail_bytes,
+                     (unsigned long long)searched, (unsigned long long)can);
+            searched = can;
+        }
+        while (built < searched) {
+            if (start[built] == ~0ull) { ++built; continue; }
+            uint64_t next = built + 1;
+            while (next < searched && start[next] == ~0ull) ++next;              // a unit without a start belongs to the one before it
+            // a long stretch without a dynamic block's start (stored or fixed blocks only: nothing a sequencer or gzip writes for FASTQ)
+            // would be ONE wave's work at some 30 MB/s: beyond 32 MiB the host reader is the faster way, and the caller takes it
+            if ((next - built) * unit_bytes > (uint64_t(32) << 20)) {
+                GZ_TRACE("%llu bytes without a block start that can be guessed: left to the host reader", (unsigned long long)((next - built) * unit_bytes));
+                hopeless = true; return FQD_OK;
+            }
+            if (next == searched && searched < n_nominal) break;                 // where this unit stops is not known yet
+            UnitIn x;
+            x.start_bit = start[built];
+            x.stop_bit = next < n_nominal ? next * unit_bytes * 8u : ~0ull;
+            // room: `ratio` bytes of text per compressed byte of the unit's stretch — and of one unit more: a unit that is decoded again
+            // from the boundary the unit before it REALLY ended at (a member that ends early in that unit) starts that much earlier
+            x.cap = ((next - built + 1u) * unit_bytes * ratio + 1024u + 15u) & ~uint64_t(15);
+            x.at = 0;
+            units.push_back(x);
+            built = next;
+        }
+        return FQD_OK;
+    }
+
+    int trailer_at(uint64_t end_bit, Trailer& t)
+    {
+        const uint64_t trailer = (end_bit + 7u) / 8u;
+        const auto it = trailers.find(trailer);
+        if (it != trailers.end()) { t = it->second; return FQD_OK; }
+        t = Trailer();
+        if (trailer + 8u <= avail_bytes) {
+            uint8_t head[8 + 1024];
+            const size_t got = size_t(std::min<uint64_t>(sizeof head, avail_bytes - trailer));
+            FQD_TRY(e, hipMemcpyAsync(head, deflate + trailer, got, hipMemcpyDeviceToHost, stream));
+            FQD_TRY(e, hipStreamSynchronize(stream));
+            t.crc = head[0] | (uint32_t(head[1]) << 8) | (uint32_t(head[2]) << 16) | (uint32_t(head[3]) << 24);
+            t.isize = head[4] | (uint32_t(head[5]) << 8) | (uint32_t(head[6]) << 16) | (uint32_t(head[7]) << 24);
+            if (trailer + 8u == avail_bytes) t.kind = 1;
+            else {
+                const uint8_t* h = head + 8; const size_t hn = got - 8;
+                const size_t at_h = gzip_header_len(h, hn);                      // here also: no reserved flag bit, two bytes of the stream behind it
+                if (at_h && !(h[3] & 0xE0) && at_h + 2 <= hn) { t.kind = 2; t.next_start = (trailer + 8u + at_h) * 8u; }
+            }
+        }
+        trailers[trailer] = t;
+        return FQD_OK;
+    }
+
+    // `count` units from d_u[first] on decoded, both planes; their results to d_r[2 * first] on and from there to host_r[2 * first] on
+    int decode(const UnitIn* d_u, uint32_t first, uint32_t count, UnitOut* d_r, UnitOut* host_r)
+    {
+        FQD_TRY(e, hipMemsetAsync(d_counter, 0, 64, stream));
+        hipLaunchKernelGGL(gz_decode_planes_kernel, dim3(std::min<uint32_t>(count, decoders)), dim3(kWave), 0, stream,
+                           deflate, have, d_u + first, count, d_p, d_q, d_tokens, d_r + 2u * first, d_counter);
+        FQD_TRY(e, hipGetLastError());
+        FQD_TRY(e, hipMemcpyAsync(host_r + 2u * first, d_r + 2u * first, 2u * count * sizeof(UnitOut), hipMemcpyDeviceToHost, stream));
+        FQD_TRY(e, hipStreamSynchronize(stream));
+        return FQD_OK;
+    }
+
+    // The next batch: units [at, hi) laid out in the planes and copied to the device.  nb == 0: none in this turn of the loop
+    // (bytes to wait for, planes that had to grow), or none ever (hopeless).
+    int next_batch()
+    {
+        nb = 0;
+        // units that can be decoded with what is there: a unit reads on to the first block boundary behind its stop — a unit of slack
+        size_t ready = at;
+        while (ready < units.size() && (all_there || (units[ready].stop_bit != ~0ull && units[ready].stop_bit / 8u + unit_bytes <= have))) ++ready;
+        if (ready == at) {
+            if (!all_there) { wait_beyond = have; return FQD_OK; }
+            if (expect_start / 8u + 2u >= avail_bytes) { hopeless = true; return FQD_OK; }       // (no final block's end was seen: not ok)
+            // members go on behind the last unit that had a start: the rest of the file as one more unit, from where the chain stands
+            UnitIn x;
+            x.start_bit = expect_start; x.stop_bit = ~0ull; x.at = 0;
+            x.cap = ((avail_bytes - expect_start / 8u) * ratio + 1024u + 15u) & ~uint64_t(15);
+            if ((avail_bytes - expect_start / 8u) > (uint64_t(32) << 20)) { hopeless = true; return FQD_OK; }
+            units.push_back(x);
+            ready = units.size();
+        }
+        // a batch: what the planes hold — less some room for units put in between (below) — and, when there are that many, whole
+        // rounds of the decoders (a wave a unit): a round that fills a sixth of the chip takes as long as one that fills it
+        const uint64_t spare = std::min<uint64_t>(plane_bytes / 8u, 24u * one_more);
+        hi = at; used = 0;
+        while (hi < ready && used + room_of(units[hi]) <= plane_bytes - spare) { units[hi].at = used; used += room_of(units[hi]); ++hi; }
+        if (const size_t round = decoders; hi - at > round && (hi < ready || !all_there)) {
+            hi = at + (hi - at) / round * round;
+            used = units[hi - 1].at + room_of(units[hi - 1]);
+        }
+        if (hi == at) {
+            // one unit that needs more than a plane holds (FQD_GUNZIP_SCRATCH_MB set small, a long stretch): the planes grow
+            plane_bytes = room_of(units[at]) + room_of(units[at]) / 4u;
+            FQD_TRY(e, hipStreamSynchronize(stream));
+            return place();
+        }
+        nb = uint32_t(hi - at);                                                   // (up to 24 units may be put in between, below)
+        if (nb + 24u > nb_cap) { hi = at + size_t(nb_cap - 24u); nb = uint32_t(hi - at); used = units[hi - 1].at + room_of(units[hi - 1]); }   // (cannot be: a unit's room is at least one_more)
+        FQD_TRY(e, hipMemcpyAsync(d_units, units.data() + at, nb * sizeof(UnitIn), hipMemcpyHostToDevice, stream));
+        result.resize(2u * nb);
+        GZ_TRACE("batch of %u units queued for decoding (%llu bytes a plane)", nb, (unsigned long long)used);
+        return FQD_OK;
+    }
+
+    int decode_batch()
+    {
+        if (const int rc = decode(d_units, 0, nb, d_result, result.data())) return rc;
+        GZ_TRACE("decoded: first unit status %u, %llu bytes, end bit %llu", result[0].status, (unsigned long long)result[0].n, (unsigned long long)result[0].end_bit);
+        return FQD_OK;
+    }
+
+    // ---- 3. the chain
+    // Units that do not start where the unit before them ended — a guess that did not hold (a header-like stretch of bits inside a
+    // block: a few per gigabyte), or the unit behind a member's end, whose next member starts where the trailer and a header
+    // say — are decoded again from there.  One wave decodes some 30 MB/s of packed bytes, so such units are first collected over
+    // the whole batch, on the assumption that where a unit ENDS does not change when it is decoded again (both starts are block
+    // boundaries of one stream), and decoded again in ONE launch; the chain (walk_chain) then checks every link and mends, one unit
+    // at a time, what that assumption missed.  (One launch per unit: 13 ms each, 90 of the 188 ms of a 12-member file.)
+    int repair_in_one_launch()
+    {
+        // A unit behind a member's end is not decoded again as a whole: the stretch from the new member's first block to the unit's
+        // nominal start becomes a unit of its own, PUT IN before it (room for it at the planes' end), and the unit keeps what it
+        // decoded from its own guess — on average a quarter of the work, and it grows with the unit no more.
+        std::vector<uint32_t> again;                                             // positions in the batch
+        std::vector<UnitIn> put_in;                                              // .cap == 0: decoded again where it is
+        uint64_t expect = expect_start, spare_at = used;
+        bool behind_member_end = member_end_before;
+        for (uint32_t k = 0; k < nb; ++k) {
+            UnitIn& x = units[at + k];
+            if (x.start_bit != expect) {
+                const uint64_t nominal = at + k > 0 ? units[at + k - 1].stop_bit : ~0ull;      // where this unit's share of the stream begins
+                UnitIn y{0, 0, 0, 0};
+                if (behind_member_end && nominal != ~0ull && expect < nominal && x.start_bit >= nominal && put_in.size() < 24u &&
+                    spare_at + one_more <= plane_bytes && std::count_if(put_in.begin(), put_in.end(), [](const UnitIn& u) { return u.cap != 0; }) < 24) {
+                    y.start_bit = expect; y.stop_bit = nominal; y.at = spare_at; y.cap = one_more - kWindow - 64u;
+                    spare_at += one_more;
+                } else x.start_bit = expect;
+                again.push_back(k); put_in.push_back(y);
+            }
+            const UnitOut& r = result[2u * k]; const UnitOut& r2 = result[2u * k + 1u];
+            if (r.status != fqd::winf::kOk || r2.status != fqd::winf::kOk || r.end_bit != r2.end_bit || r.how != r2.how) break;   // garbage from a wrong guess: the chain takes over here
+            if (r.how == 2u) {
+                if (!trailer_there(r.end_bit)) break;
+                Trailer t;
+                if (const int rc = trailer_at(r.end_bit, t)) return rc;
+                if (t.kind != 2) break;
+                expect = t.next_start; behind_member_end = true;
+            } else { expect = r.end_bit; behind_member_end = false; }
+        }
+        if (again.empty()) return FQD_OK;
+        repairs += again.size();
+        if (repairs > 64u + units.size() / 16u) { GZ_TRACE("%llu units do not start where the one before them ended: giving up", (unsigned long long)repairs); good = false; return FQD_OK; }
+        std::vector<UnitIn> ru(again.size());
+        for (size_t i = 0; i < again.size(); ++i) ru[i] = put_in[i].cap ? put_in[i] : units[at + again[i]];
+        std::vector<UnitOut> rr(2u * again.size());
+        FQD_TRY(e, hipMemcpyAsync(d_ru, ru.data(), ru.size() * sizeof(UnitIn), hipMemcpyHostToDevice, stream));
+        if (const int rc = decode(d_ru, 0, uint32_t(ru.size()), d_rr, rr.data())) return rc;
+        uint32_t more = 0;
+        for (size_t i = again.size(); i-- > 0;) {                                 // from the back: positions before it stay what they are
+            const uint32_t k = again[i];
+            if (put_in[i].cap) {
+                units.insert(units.begin() + std::ptrdiff_t(at + k), put_in[i]);
+                result.insert(result.begin() + std::ptrdiff_t(2u * k), {rr[2u * i], rr[2u * i + 1u]});
+                ++more;
+            } else { result[2u * k] = rr[2u * i]; result[2u * k + 1u] = rr[2u * i + 1u]; }
+        }
+        nb += more; hi += more;
+        FQD_TRY(e, hipMemcpyAsync(d_units, units.data() + at, nb * sizeof(UnitIn), hipMemcpyHostToDevice, stream));
+        FQD_TRY(e, hipMemcpyAsync(d_result, result.data(), 2u * nb * sizeof(UnitOut), hipMemcpyHostToDevice, stream));
+        GZ_TRACE("%zu units decoded again in one launch, each from where the unit before it ended (%u of them the short stretch behind a member's end, put in as a unit)",
+                 again.size(), more);
+        return FQD_OK;
+    }
+
+    // Every link of the batch's chain checked, unit after unit; the first `live` units are text now (text_at: where), members that
+    // ended among them are noted with their trailers.
+    int walk_chain(uint32_t& live)
+    {
+        text_at.resize(nb);
+        live = 0;
+        bool put_off = false;                                                     // a unit that needs bytes that have not arrived: it and what follows wait
+        for (uint32_t k = 0; k < nb && good && !final_seen; ++k) {
+            UnitIn& x = units[at + k];
+            if (x.start_bit != expect_start) {
+                // what the pass above could not know: the unit before this one ended elsewhere when it was decoded again
+                if (++repairs > 64u + units.size() / 16u) { good = false; break; }           // (damage, not bad luck)
+                x.start_bit = expect_start;
+                FQD_TRY(e, hipMemcpyAsync(d_units + k, &x, sizeof(UnitIn), hipMemcpyHostToDevice, stream));
+                if (const int rc = decode(d_units, k, 1u, d_result, result.data())) return rc;
+                GZ_TRACE("unit %zu decoded again from bit %llu: status %u, %llu bytes", at + k, (unsigned long long)expect_start, result[2u * k].status, (unsigned long long)result[2u * k].n);
+            }
+            const UnitOut& r = result[2u * k]; const UnitOut& r2 = result[2u * k + 1u];
+            if (r.status != fqd::winf::kOk || r2.status != fqd::winf::kOk || r.end_bit != r2.end_bit || r.n != r2.n || r.how != r2.how) {
+                if (!all_there) { put_off = true; break; }                        // (it may have run into what has not arrived: once more when there is more)
+                GZ_TRACE("unit %zu (from bit %llu, room %llu): status %u / %u, %llu / %llu bytes: giving up", at + k, (unsigned long long)x.start_bit, (unsigned long long)x.cap,
+                         r.status, r2.status, (unsigned long long)r.n, (unsigned long long)r2.n);
+                good = false; break;
+            }
+            if (r.how == 2u && !trailer_there(r.end_bit)) { put_off = true; break; }
+            if (total + r.n > text_cap) { GZ_TRACE("the text outgrows the room given (%llu bytes)", (unsigned long long)text_cap); good = false; break; }
+            text_at[k] = total; total += r.n;
+            expect_start = r.end_bit;
+            live = k + 1;
+            member_end_before = r.how == 2u;
+            if (r.how == 2u) {
+                // the member's final block ended here: its trailer follows at the next byte, and — `cat a.gz b.gz`, or a writer that
+                // starts a member every so often — perhaps another member, whose first block the next unit is then decoded from
+                Trailer t;
+                if (const int rc = trailer_at(r.end_bit, t)) return rc;
+                if (t.kind == 0) { GZ_TRACE("no trailer, or no member header, behind the final block that ends at bit %llu", (unsigned long long)r.end_bit); good = false; break; }
+                Member m;
+                m.text_from = member_from; m.text_to = total; m.deflate_end = (r.end_bit + 7u) / 8u;
+                m.crc = t.crc; m.isize = t.isize;
+                members.push_back(m);
+                member_from = total;
+                if (t.kind == 1) { final_seen = true; break; }
+                expect_start = t.next_start;
+            }
+        }
+        if (good && put_off) { GZ_TRACE("unit %zu waits for bytes that have not arrived (%llu there)", at + live, (unsigned long long)have); wait_beyond = have; }
+        return FQD_OK;
+    }
+
+    // ---- 4, 5: the windows of the batch's first `live` units and their bytes; the chain moves on behind them
+    int windows_and_bytes(uint32_t live)
+    {
+        FQD_TRY(e, hipMemcpyAsync(d_text_at, text_at.data(), live * 8, hipMemcpyHostToDevice, stream));
+        FQD_TRY(e, hipMemcpyAsync(d_windows, carry.data(), kWindow, hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(gz_window_maps_kernel, dim3(std::min<uint32_t>(live, uint32_t(n_cu) * 8u)), dim3(256), 0, stream,
+                           d_units, d_result, live, d_p, d_q, d_maps);
+        FQD_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(gz_windows_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(2u * kWindow)));
+        hipLaunchKernelGGL(gz_windows_chain_kernel, dim3(1), dim3(1024), 2u * kWindow, stream, d_maps, live, d_windows);
+        FQD_TRY(e, hipGetLastError());
+        GZ_TRACE("windows of %u units made", live);
+        hipLaunchKernelGGL(gz_resolve_kernel, dim3(std::min<uint32_t>(live, uint32_t(n_cu) * 8u)), dim3(256), 0, stream,
+                           d_units, d_result, d_text_at, live, d_p, d_q, d_windows, text);
+        FQD_TRY(e, hipGetLastError());
+        FQD_TRY(e, hipMemcpyAsync(carry.data(), d_windows + uint64_t(live) * kWindow, kWindow, hipMemcpyDeviceToHost, stream));
+        FQD_TRY(e, hipStreamSynchronize(stream));
+        GZ_TRACE("windows and bytes of %u units done, %llu bytes of text so far", live, (unsigned long long)total);
+        at = at + live < hi && final_seen ? hi : at + live;                      // (units of the batch behind a repair that were not reached are decoded with the next batch)
+        return FQD_OK;
+    }
+
+    // ---- CRC-32 and length of every member's text against its trailer
+    int check_members(uint64_t* text_bytes, uint64_t* deflate_bytes, uint32_t* crc32, int32_t* ok)
+    {
+        if (members.empty()) return FQD_OK;
+        uint32_t crc = 0;
+        uint32_t shift[8][32];
+        Mat m = mat_one_zero_byte();
+        for (int k = 0; k < 8; ++k) m = mat_square(m);                            // 256 zero bytes
+        for (int k = 0; k < 8; ++k) { std::memcpy(shift[k], m.col, sizeof m.col); m = mat_square(m); }
+        const Mat slice_mat = m;                                                  // 65536 zero bytes
+        FQD_TRY(e, hipMemcpyAsync(d_shift, shift, sizeof shift, hipMemcpyHostToDevice, stream));
+        std::vector<uint32_t> raw;
+        for (const Member& mb : members) {
+            const uint64_t len = mb.text_to - mb.text_from;
+            crc = 0;
+            if (len) {
+                const uint64_t n_slices = (len + kSlice - 1) / kSlice;
+                hipLaunchKernelGGL(gz_crc_kernel, dim3(uint32_t(std::min<uint64_t>(n_slices, uint64_t(n_cu) * 8u))), dim3(kCrcThreads), 0, stream,
+                                   static_cast<const uint8_t*>(text) + mb.text_from, len, n_slices, d_shift, d_raw);
+                FQD_TRY(e, hipGetLastError());
+                raw.resize(n_slices);
+                FQD_TRY(e, hipMemcpyAsync(raw.data(), d_raw, n_slices * 4, hipMemcpyDeviceToHost, stream));
+                FQD_TRY(e, hipStreamSynchronize(stream));
+                // raw register of the member's text started from 0: full slices fold with the 64 KiB matrix, the short last one with its own length
+                uint32_t reg = 0;
+                for (uint64_t sl = 0; sl < n_slices; ++sl) {
+                    const uint64_t l = sl + 1 < n_slices ? kSlice : len - sl * kSlice;
+                    reg = (l == kSlice ? mat_apply(slice_mat, reg) : advance_zero_bytes(reg, l)) ^ raw[sl];
+                }
+                crc = reg ^ advance_zero_bytes(0xFFFFFFFFu, len) ^ 0xFFFFFFFFu;   // the same register started from all ones, then inverted: zlib's CRC-32
+            }
+            if (crc != mb.crc || uint32_t(len) != mb.isize) { GZ_TRACE("a member's CRC-32 or length is not its trailer's"); return FQD_OK; }   // *ok stays 0
+        }
+        GZ_TRACE("%zu member(s): CRC-32 and length as the trailers say", members.size());
+        *text_bytes = total;
+        *deflate_bytes = members.back().deflate_end;
+        *crc32 = crc;
+        *ok = 1;
+        return FQD_OK;
+    }
 };
 
 } // namespace
@@ -410,383 +803,26 @@ int fqd_gunzip_arriving(fqd_engine* e, const uint8_t* deflate, uint64_t avail_by
     if (!deflate || !text || !text_bytes || !deflate_bytes || !crc32 || !ok) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_gunzip: bad arguments");
     *ok = 0; *text_bytes = 0; *deflate_bytes = 0; *crc32 = 0;
     if (avail_bytes < 2) return FQD_OK;
-    GZ_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    hipStream_t stream = fqd_internal_stream(e);
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     int n_cu = 256;
     { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, fqd_internal_device(e)) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount; }
-
     static const bool trace = std::getenv("FQD_GUNZIP_TRACE") != nullptr;      // stages to stderr as they are reached
-    const auto t_begin = std::chrono::steady_clock::now();
-#define GZ_TRACE(...) do { if (trace) { (void)hipStreamSynchronize(stream); std::fprintf(stderr, "[gunzip %7.2f ms] ", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count()); \
-    std::fprintf(stderr, __VA_ARGS__); std::fputc('\n', stderr); std::fflush(stderr); } } while (0)
-    BitIn in;
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(deflate);
-    in.words = reinterpret_cast<const uint64_t*>(addr & ~uintptr_t(7));
-    in.lead = uint64_t(addr & 7u) * 8u;
-    in.nbits = avail_bytes * 8u;
 
-    // units: small enough that there are several per wave slot of the chip, large enough to hold a block start more often than
-    // not (zlib ends a block every 16 K codes: some 20-50 KB packed).  (Measured and replaced on the way here, DESIGN §3b: one
-    // serial decoder per wave writing 16-bit symbols, all lanes running it alike — 4.6 GB/s of text; the same, one decoder per
-    // LANE with its tables in HBM — 2.6 GB/s: lanes of a wave that copy matches of different lengths wait for the longest.)
-    // Large files: some 16 K units of at most 256 KiB — a unit that has to be decoded again is ONE wave's work (11 MB/s of packed bytes
-    // when it runs alone), the chip's 4096 decoders are filled in whole rounds, and the windows' chain costs 2 us a unit.
-    uint64_t unit_bytes = std::min<uint64_t>(256u << 10, std::max<uint64_t>(64u << 10, (avail_bytes / 16384u + 4095u) & ~uint64_t(4095)));
-    if (const char* v = std::getenv("FQD_GUNZIP_UNIT_KB")) { const long kb = std::atol(v); if (kb > 0) unit_bytes = uint64_t(kb) << 10; }
-    uint64_t ratio = 8;                                                      // symbols of room per compressed byte (FASTQ packs 3-6 fold)
-    if (const char* v = std::getenv("FQD_GUNZIP_RATIO")) { const long r = std::atol(v); if (r > 0) ratio = uint64_t(r); }
-    const uint64_t n_nominal = (avail_bytes + unit_bytes - 1) / unit_bytes;
-
-    // ---- 2-5 in batches of units whose two planes fit the scratch: by default up to two rounds of the chip's decoders (a wave a unit)
-    const uint64_t one_more = uint64_t(kWindow) + ((2u * unit_bytes * ratio + 1024u + 15u) & ~uint64_t(15)) + 64u;     // the room of a unit of one nominal unit
-    const uint32_t decoders = uint32_t(std::min<uint64_t>(n_nominal, uint64_t(n_cu) * 16u));           // a wave a unit; 10 KB of LDS, <= 128 VGPRs: sixteen waves a CU
-    uint64_t plane_bytes = std::min<uint64_t>(uint64_t(8) << 30, (2u * decoders + 64u) * one_more);   // per plane: two rounds if 8 GiB hold them (two back to back take less than twice one)
-    if (const char* v = std::getenv("FQD_GUNZIP_SCRATCH_MB")) { const long mb = std::atol(v); if (mb > 0) plane_bytes = (uint64_t(mb) << 20) / 2; }
-    auto room_of = [](const UnitIn& x) { return uint64_t(kWindow) + x.cap + 64u; };          // made-up window, text, slack (a multiple of 16)
-    plane_bytes = std::min(plane_bytes, n_nominal * one_more + 64u * one_more);                       // (never more than all units need)
-    // ONE piece of the engine's scratch holds everything the call needs on the device, and stays with the engine: a call that
-    // frees gigabytes hands them to the driver for clearing, and the process's next hipMalloc — the dedup engine's key store, the
-    // other file's planes — waits for that (configs[4] shape, two files at once: a second lost in whatever stage came next).
-    View d_start, d_p, d_q, d_units, d_result, d_text_at, d_windows, d_counter, d_tokens, d_maps, d_ru, d_rr, d_shift, d_raw;
-    uint64_t nb_cap = 0;                                                      // units a batch can hold
-    auto place = [&]() -> int {
-        nb_cap = plane_bytes / one_more + 32u;
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at_o = o; o = (o + bytes + 255u) & ~size_t(255); return at_o; };
-        const size_t o_p = take(plane_bytes + 64), o_q = take(plane_bytes + 64);
-        const size_t o_tok = take(size_t(decoders) * fqd::winf::kTokenRoom * sizeof(fqd::winf::Token));
-        const size_t o_maps = take(nb_cap * kWindow * 2u), o_win = take((nb_cap + 1u) * kWindow);
-        const size_t o_units = take(nb_cap * sizeof(UnitIn)), o_res = take(2u * nb_cap * sizeof(UnitOut)), o_at = take(nb_cap * 8u);
-        const size_t o_ru = take(nb_cap * sizeof(UnitIn)), o_rr = take(2u * nb_cap * sizeof(UnitOut));
-        const size_t o_cnt = take(64), o_start = take(n_nominal * 8u), o_shift = take(8 * 32 * 4), o_raw = take((text_cap / kSlice + 2u) * 4u);
-        void* base = nullptr;
-        const int rc_s = fqd_internal_scratch(e, 1, o, &base);
-        if (rc_s != FQD_OK) return rc_s;
-        uint8_t* b8 = static_cast<uint8_t*>(base);
-        d_p.p = b8 + o_p; d_q.p = b8 + o_q; d_tokens.p = b8 + o_tok; d_maps.p = b8 + o_maps; d_windows.p = b8 + o_win;
-        d_units.p = b8 + o_units; d_result.p = b8 + o_res; d_text_at.p = b8 + o_at; d_ru.p = b8 + o_ru; d_rr.p = b8 + o_rr;
-        d_counter.p = b8 + o_cnt; d_start.p = b8 + o_start; d_shift.p = b8 + o_shift; d_raw.p = b8 + o_raw;
-        return FQD_OK;
-    };
-    { const int rc_p = place(); if (rc_p != FQD_OK) return rc_p; }
-    // ---- 1. starts, and the units they make — of what has ARRIVED (fqd_gunzip_arriving: the file is still being copied to HBM
-    // by another thread of the caller, which raises *arrived as its copies complete; everything below works on what is there
-    // and waits for the rest, so that block starts are found and units decoded under the read)
-    auto have_now = [&]() -> uint64_t { if (!arrived) return avail_bytes; const uint64_t a = *arrived; return a < avail_bytes ? a : (a == ~0ull ? ~0ull : avail_bytes); };
-    std::vector<uint64_t> start(n_nominal, ~0ull);
-    std::vector<UnitIn> units;
-    uint64_t searched = 0, built = 0;                                         // nominal units looked at for a start / turned into units
-    bool hopeless = false;
-    auto take_in = [&](uint64_t have) -> int {
-        // a unit is looked at when it and what the looks read beyond a position (a block header: some hundred bytes) have arrived
-        const uint64_t can = have == avail_bytes ? n_nominal : (have > 4096u ? (have - 4096u) / unit_bytes : 0u);
-        if (can > searched) {
-            hipLaunchKernelGGL(gz_find_starts_kernel, dim3(uint32_t(std::min<uint64_t>(can - searched, uint64_t(n_cu) * 16u))), dim3(kWave), 0, stream,
-                               in, unit_bytes * 8u, searched, can, d_start.as<uint64_t>());
-            GZ_TRY(e, hipGetLastError());
-            GZ_TRY(e, hipMemcpyAsync(start.data() + searched, d_start.as<uint64_t>() + searched, (can - searched) * 8, hipMemcpyDeviceToHost, stream));
-            GZ_TRY(e, hipStreamSynchronize(stream));
-            GZ_TRACE("%llu of %llu bytes there: block starts of units %llu to %llu looked for", (unsigned long long)have, (unsigned long long)avail_bytes,
-                     (unsigned long long)searched, (unsigned long long)can);
-            searched = can;
-        }
-        while (built < searched) {
-            if (start[built] == ~0ull) { ++built; continue; }
-            uint64_t next = built + 1;
-            while (next < searched && start[next] == ~0ull) ++next;          // a unit without a start belongs to the one before it
-            // a long stretch without a dynamic block's start (stored or fixed blocks only: nothing a sequencer or gzip writes for FASTQ)
-            // would be ONE wave's work at some 30 MB/s: beyond 32 MiB the host reader is the faster way, and the caller takes it
-            if ((next - built) * unit_bytes > (uint64_t(32) << 20)) {
-                GZ_TRACE("%llu bytes without a block start that can be guessed: left to the host reader", (unsigned long long)((next - built) * unit_bytes));
-                hopeless = true; return FQD_OK;
-            }
-            if (next == searched && searched < n_nominal) break;             // where this unit stops is not known yet
-            UnitIn x;
-            x.start_bit = start[built];
-            x.stop_bit = next < n_nominal ? next * unit_bytes * 8u : ~0ull;
-            // room: `ratio` bytes of text per compressed byte of the unit's stretch — and of one unit more: a unit that is decoded again
-            // from the boundary the unit before it REALLY ended at (a member that ends early in that unit) starts that much earlier
-            x.cap = ((next - built + 1u) * unit_bytes * ratio + 1024u + 15u) & ~uint64_t(15);
-            x.at = 0;
-            units.push_back(x);
-            built = next;
-        }
-        return FQD_OK;
-    };
-
-    GZ_TRACE("%llu bytes, %llu units of %llu bytes; scratch: 2 planes of %llu bytes, %u decoders' tokens", (unsigned long long)avail_bytes, (unsigned long long)n_nominal,
-             (unsigned long long)unit_bytes, (unsigned long long)plane_bytes, decoders);
-    struct Member { uint64_t text_from, text_to, deflate_end; uint32_t crc, isize; };
-    std::vector<Member> members;
-    uint64_t member_from = 0;
-    std::vector<uint8_t> carry(kWindow, 0);                                   // the window before the next batch's first unit
-    uint64_t total = 0, expect_start = 0, repairs = 0;
-    bool final_seen = false, good = true;
-    std::vector<UnitOut> result;
-    std::vector<uint64_t> text_at;
-    size_t at = 0;
-    uint64_t have = 0;                                                        // bytes of the stream a batch may count on
-    bool member_end_before = false;                                           // the unit the chain took last ended a member
-    bool all_there = false;
-    // What follows a member's final block: its trailer (CRC-32, ISIZE) and the end of the file, or the header of another member (RFC 1952).
-    struct Trailer { uint32_t crc = 0, isize = 0; int kind = 0; /* 0 neither, 1 the file ends, 2 another member */ uint64_t next_start = 0; };
-    std::unordered_map<uint64_t, Trailer> trailers;                          // by byte offset: looked at twice (below), fetched once
-    auto trailer_at = [&](uint64_t end_bit, Trailer& t) -> int {
-        const uint64_t trailer = (end_bit + 7u) / 8u;
-        const auto it = trailers.find(trailer);
-        if (it != trailers.end()) { t = it->second; return FQD_OK; }
-        t = Trailer();
-        if (trailer + 8u <= avail_bytes) {
-            uint8_t head[8 + 1024];
-            const size_t got = size_t(std::min<uint64_t>(sizeof head, avail_bytes - trailer));
-            GZ_TRY(e, hipMemcpyAsync(head, deflate + trailer, got, hipMemcpyDeviceToHost, stream));
-            GZ_TRY(e, hipStreamSynchronize(stream));
-            t.crc = head[0] | (uint32_t(head[1]) << 8) | (uint32_t(head[2]) << 16) | (uint32_t(head[3]) << 24);
-            t.isize = head[4] | (uint32_t(head[5]) << 8) | (uint32_t(head[6]) << 16) | (uint32_t(head[7]) << 24);
-            if (trailer + 8u == avail_bytes) t.kind = 1;
-            else {
-                const uint8_t* h = head + 8; const size_t hn = got - 8;
-                size_t at_h = 10;
-                bool fine = hn >= 18 && h[0] == 31 && h[1] == 139 && h[2] == 8 && !(h[3] & 0xE0);
-                if (fine && (h[3] & 4)) { if (at_h + 2 > hn) fine = false; else at_h += 2 + (h[at_h] | (size_t(h[at_h + 1]) << 8)); }
-                if (fine && (h[3] & 8)) { while (at_h < hn && h[at_h]) ++at_h; ++at_h; }
-                if (fine && (h[3] & 16)) { while (at_h < hn && h[at_h]) ++at_h; ++at_h; }
-                if (fine && (h[3] & 2)) at_h += 2;
-                if (fine && at_h + 2 <= hn) { t.kind = 2; t.next_start = (trailer + 8u + at_h) * 8u; }
-            }
-        }
-        trailers[trailer] = t;
-        return FQD_OK;
-    };
-    auto decode = [&](uint32_t first, uint32_t count) -> int {              // units [first, first + count) of the batch, both planes
-        GZ_TRY(e, hipMemsetAsync(d_counter.p, 0, 64, stream));
-        hipLaunchKernelGGL(gz_decode_planes_kernel, dim3(std::min<uint32_t>(count, decoders)), dim3(kWave), 0, stream,
-                           deflate, have, d_units.as<const UnitIn>() + first, count, d_p.as<uint8_t>(), d_q.as<uint8_t>(),
-                           d_tokens.as<fqd::winf::Token>(), d_result.as<UnitOut>() + 2u * first, d_counter.as<uint32_t>());
-        GZ_TRY(e, hipGetLastError());
-        GZ_TRY(e, hipMemcpyAsync(result.data() + 2u * first, d_result.as<UnitOut>() + 2u * first, 2u * count * sizeof(UnitOut), hipMemcpyDeviceToHost, stream));
-        GZ_TRY(e, hipStreamSynchronize(stream));
-        return FQD_OK;
-    };
-    // what lies behind a final block (trailer, perhaps a header of up to a kilobyte) can be looked at
-    auto trailer_there = [&](uint64_t end_bit) { return all_there || (end_bit + 7u) / 8u + 8u + 1024u <= have; };
-    uint64_t wait_beyond = 0;                                                // nothing to do until more than this has arrived
-    while (good && !final_seen) {
-        have = have_now();
-        if (have == ~0ull) { GZ_TRACE("the caller says the rest of the file will not come"); good = false; break; }
-        all_there = have == avail_bytes;
-        if (!all_there && have <= wait_beyond) { ::usleep(100); continue; }
-        int rc = take_in(have);
-        if (rc) return rc;
-        if (hopeless) return FQD_OK;
-        // units that can be decoded with what is there: a unit reads on to the first block boundary behind its stop — a unit of slack
-        size_t ready = at;
-        while (ready < units.size() && (all_there || (units[ready].stop_bit != ~0ull && units[ready].stop_bit / 8u + unit_bytes <= have))) ++ready;
-        if (ready == at) {
-            if (!all_there) { wait_beyond = have; continue; }
-            if (expect_start / 8u + 2u >= avail_bytes) break;                // (no final block's end was seen: not ok)
-            // members go on behind the last unit that had a start: the rest of the file as one more unit, from where the chain stands
-            UnitIn x;
-            x.start_bit = expect_start; x.stop_bit = ~0ull; x.at = 0;
-            x.cap = ((avail_bytes - expect_start / 8u) * ratio + 1024u + 15u) & ~uint64_t(15);
-            if ((avail_bytes - expect_start / 8u) > (uint64_t(32) << 20)) return FQD_OK;
-            units.push_back(x);
-            ready = units.size();
-        }
-        // a batch: what the planes hold — less some room for units put in between (below) — and, when there are that many, whole
-        // rounds of the decoders (a wave a unit): a round that fills a sixth of the chip takes as long as one that fills it
-        const uint64_t spare = std::min<uint64_t>(plane_bytes / 8u, 24u * one_more);
-        size_t hi = at; uint64_t used = 0;
-        while (hi < ready && used + room_of(units[hi]) <= plane_bytes - spare) { units[hi].at = used; used += room_of(units[hi]); ++hi; }
-        if (const size_t round = decoders; hi - at > round && (hi < ready || !all_there)) {
-            hi = at + (hi - at) / round * round;
-            used = units[hi - 1].at + room_of(units[hi - 1]);
-        }
-        if (hi == at) {
-            // one unit that needs more than a plane holds (FQD_GUNZIP_SCRATCH_MB set small, a long stretch): the planes grow
-            plane_bytes = room_of(units[at]) + room_of(units[at]) / 4u;
-            GZ_TRY(e, hipStreamSynchronize(stream));
-            if ((rc = place())) return rc;
-            continue;
-        }
-        uint32_t nb = uint32_t(hi - at);                                      // (up to 24 units may be put in between, below)
-        if (nb + 24u > nb_cap) { hi = at + size_t(nb_cap - 24u); nb = uint32_t(hi - at); used = units[hi - 1].at + room_of(units[hi - 1]); }   // (cannot be: a unit's room is at least one_more)
-        GZ_TRY(e, hipMemcpyAsync(d_units.p, units.data() + at, nb * sizeof(UnitIn), hipMemcpyHostToDevice, stream));
-        result.resize(2u * nb);
-        GZ_TRACE("batch of %u units queued for decoding (%llu bytes a plane)", nb, (unsigned long long)used);
-        rc = decode(0, nb);
-        if (rc) return rc;
-        GZ_TRACE("decoded: first unit status %u, %llu bytes, end bit %llu", result[0].status, (unsigned long long)result[0].n, (unsigned long long)result[0].end_bit);
-        // ---- 3. the chain
-        // Units that do not start where the unit before them ended — a guess that did not hold (a header-like stretch of bits inside a
-        // block: a few per gigabyte), or the unit behind a member's end, whose next member starts where the trailer and a header
-        // say — are decoded again from there.  One wave decodes some 30 MB/s of packed bytes, so such units are first collected over
-        // the whole batch, on the assumption that where a unit ENDS does not change when it is decoded again (both starts are block
-        // boundaries of one stream), and decoded again in ONE launch; the chain below then checks every link and mends, one unit
-        // at a time, what that assumption missed.  (One launch per unit: 13 ms each, 90 of the 188 ms of a 12-member file.)
-        {
-            // A unit behind a member's end is not decoded again as a whole: the stretch from the new member's first block to the unit's
-            // nominal start becomes a unit of its own, PUT IN before it (room for it at the planes' end), and the unit keeps what it
-            // decoded from its own guess — on average a quarter of the work, and it grows with the unit no more.
-            std::vector<uint32_t> again;                                     // positions in the batch
-            std::vector<UnitIn> put_in;                                      // .cap == 0: decoded again where it is
-            uint64_t expect = expect_start, spare_at = used;
-            bool behind_member_end = member_end_before;
-            for (uint32_t k = 0; k < nb; ++k) {
-                UnitIn& x = units[at + k];
-                if (x.start_bit != expect) {
-                    const uint64_t nominal = at + k > 0 ? units[at + k - 1].stop_bit : ~0ull;      // where this unit's share of the stream begins
-                    UnitIn y{0, 0, 0, 0};
-                    if (behind_member_end && nominal != ~0ull && expect < nominal && x.start_bit >= nominal && put_in.size() < 24u &&
-                        spare_at + one_more <= plane_bytes && std::count_if(put_in.begin(), put_in.end(), [](const UnitIn& u) { return u.cap != 0; }) < 24) {
-                        y.start_bit = expect; y.stop_bit = nominal; y.at = spare_at; y.cap = one_more - kWindow - 64u;
-                        spare_at += one_more;
-                    } else x.start_bit = expect;
-                    again.push_back(k); put_in.push_back(y);
-                }
-                const UnitOut& r = result[2u * k]; const UnitOut& r2 = result[2u * k + 1u];
-                if (r.status != fqd::winf::kOk || r2.status != fqd::winf::kOk || r.end_bit != r2.end_bit || r.how != r2.how) break;   // garbage from a wrong guess: the chain takes over here
-                if (r.how == 2u) {
-                    if (!trailer_there(r.end_bit)) break;
-                    Trailer t;
-                    if ((rc = trailer_at(r.end_bit, t))) return rc;
-                    if (t.kind != 2) break;
-                    expect = t.next_start; behind_member_end = true;
-                } else { expect = r.end_bit; behind_member_end = false; }
-            }
-            if (!again.empty()) {
-                repairs += again.size();
-                if (repairs > 64u + units.size() / 16u) { GZ_TRACE("%llu units do not start where the one before them ended: giving up", (unsigned long long)repairs); good = false; break; }
-                std::vector<UnitIn> ru(again.size());
-                for (size_t i = 0; i < again.size(); ++i) ru[i] = put_in[i].cap ? put_in[i] : units[at + again[i]];
-                std::vector<UnitOut> rr(2u * again.size());
-                GZ_TRY(e, hipMemcpyAsync(d_ru.p, ru.data(), ru.size() * sizeof(UnitIn), hipMemcpyHostToDevice, stream));
-                GZ_TRY(e, hipMemsetAsync(d_counter.p, 0, 64, stream));
-                hipLaunchKernelGGL(gz_decode_planes_kernel, dim3(std::min<uint32_t>(uint32_t(ru.size()), decoders)), dim3(kWave), 0, stream,
-                                   deflate, have, d_ru.as<const UnitIn>(), uint32_t(ru.size()), d_p.as<uint8_t>(), d_q.as<uint8_t>(),
-                                   d_tokens.as<fqd::winf::Token>(), d_rr.as<UnitOut>(), d_counter.as<uint32_t>());
-                GZ_TRY(e, hipGetLastError());
-                GZ_TRY(e, hipMemcpyAsync(rr.data(), d_rr.p, rr.size() * sizeof(UnitOut), hipMemcpyDeviceToHost, stream));
-                GZ_TRY(e, hipStreamSynchronize(stream));
-                uint32_t more = 0;
-                for (size_t i = again.size(); i-- > 0;) {                     // from the back: positions before it stay what they are
-                    const uint32_t k = again[i];
-                    if (put_in[i].cap) {
-                        units.insert(units.begin() + std::ptrdiff_t(at + k), put_in[i]);
-                        result.insert(result.begin() + std::ptrdiff_t(2u * k), {rr[2u * i], rr[2u * i + 1u]});
-                        ++more;
-                    } else { result[2u * k] = rr[2u * i]; result[2u * k + 1u] = rr[2u * i + 1u]; }
-                }
-                nb += more; hi += more;
-                GZ_TRY(e, hipMemcpyAsync(d_units.p, units.data() + at, nb * sizeof(UnitIn), hipMemcpyHostToDevice, stream));
-                GZ_TRY(e, hipMemcpyAsync(d_result.p, result.data(), 2u * nb * sizeof(UnitOut), hipMemcpyHostToDevice, stream));
-                GZ_TRACE("%zu units decoded again in one launch, each from where the unit before it ended (%u of them the short stretch behind a member's end, put in as a unit)",
-                         again.size(), more);
-            }
-        }
-        text_at.resize(nb);
+    GunzipRun run(e, n_cu, deflate, avail_bytes, arrived, text, text_cap, trace);
+    int rc = run.set_up();
+    while (!rc && run.good && !run.final_seen) {
+        if (!run.see_what_arrived()) continue;
+        if ((rc = run.take_in()) || run.hopeless) return rc;
+        if ((rc = run.next_batch()) || run.hopeless) return rc;
+        if (run.nb == 0) continue;
+        if ((rc = run.decode_batch())) return rc;
         uint32_t live = 0;
-        bool put_off = false;                                                 // a unit that needs bytes that have not arrived: it and what follows wait
-        for (uint32_t k = 0; k < nb && good && !final_seen; ++k) {
-            UnitIn& x = units[at + k];
-            if (x.start_bit != expect_start) {
-                // what the pass above could not know: the unit before this one ended elsewhere when it was decoded again
-                if (++repairs > 64u + units.size() / 16u) { good = false; break; }       // (damage, not bad luck)
-                x.start_bit = expect_start;
-                GZ_TRY(e, hipMemcpyAsync(d_units.as<UnitIn>() + k, &x, sizeof(UnitIn), hipMemcpyHostToDevice, stream));
-                if ((rc = decode(k, 1u))) return rc;
-                GZ_TRACE("unit %zu decoded again from bit %llu: status %u, %llu bytes", at + k, (unsigned long long)expect_start, result[2u * k].status, (unsigned long long)result[2u * k].n);
-            }
-            const UnitOut& r = result[2u * k]; const UnitOut& r2 = result[2u * k + 1u];
-            if (r.status != fqd::winf::kOk || r2.status != fqd::winf::kOk || r.end_bit != r2.end_bit || r.n != r2.n || r.how != r2.how) {
-                if (!all_there) { put_off = true; break; }                    // (it may have run into what has not arrived: once more when there is more)
-                GZ_TRACE("unit %zu (from bit %llu, room %llu): status %u / %u, %llu / %llu bytes: giving up", at + k, (unsigned long long)x.start_bit, (unsigned long long)x.cap,
-                         r.status, r2.status, (unsigned long long)r.n, (unsigned long long)r2.n);
-                good = false; break;
-            }
-            if (r.how == 2u && !trailer_there(r.end_bit)) { put_off = true; break; }
-            if (total + r.n > text_cap) { GZ_TRACE("the text outgrows the room given (%llu bytes)", (unsigned long long)text_cap); good = false; break; }
-            text_at[k] = total; total += r.n;
-            expect_start = r.end_bit;
-            live = k + 1;
-            member_end_before = r.how == 2u;
-            if (r.how == 2u) {
-                // the member's final block ended here: its trailer follows at the next byte, and — `cat a.gz b.gz`, or a writer that
-                // starts a member every so often — perhaps another member, whose first block the next unit is then decoded from
-                Trailer t;
-                if ((rc = trailer_at(r.end_bit, t))) return rc;
-                if (t.kind == 0) { GZ_TRACE("no trailer, or no member header, behind the final block that ends at bit %llu", (unsigned long long)r.end_bit); good = false; break; }
-                Member m;
-                m.text_from = member_from; m.text_to = total; m.deflate_end = (r.end_bit + 7u) / 8u;
-                m.crc = t.crc; m.isize = t.isize;
-                members.push_back(m);
-                member_from = total;
-                if (t.kind == 1) { final_seen = true; break; }
-                expect_start = t.next_start;
-            }
-        }
-        if (!good) break;
-        if (put_off) { GZ_TRACE("unit %zu waits for bytes that have not arrived (%llu there)", at + live, (unsigned long long)have); wait_beyond = have; }
-        if (live == 0) continue;
-        // ---- 4, 5
-        GZ_TRY(e, hipMemcpyAsync(d_text_at.p, text_at.data(), live * 8, hipMemcpyHostToDevice, stream));
-        GZ_TRY(e, hipMemcpyAsync(d_windows.p, carry.data(), kWindow, hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(gz_window_maps_kernel, dim3(std::min<uint32_t>(live, uint32_t(n_cu) * 8u)), dim3(256), 0, stream, d_units.as<const UnitIn>(),
-                           d_result.as<const UnitOut>(), live, d_p.as<const uint8_t>(), d_q.as<const uint8_t>(), d_maps.as<uint16_t>());
-        GZ_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(gz_windows_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(2u * kWindow)));
-        hipLaunchKernelGGL(gz_windows_chain_kernel, dim3(1), dim3(1024), 2u * kWindow, stream, d_maps.as<const uint16_t>(), live, d_windows.as<uint8_t>());
-        GZ_TRY(e, hipGetLastError());
-        GZ_TRACE("windows of %u units made", live);
-        hipLaunchKernelGGL(gz_resolve_kernel, dim3(std::min<uint32_t>(live, uint32_t(n_cu) * 8u)), dim3(256), 0, stream,
-                           d_units.as<const UnitIn>(), d_result.as<const UnitOut>(), d_text_at.as<const uint64_t>(), live,
-                           d_p.as<const uint8_t>(), d_q.as<const uint8_t>(), d_windows.as<const uint8_t>(), text);
-        GZ_TRY(e, hipGetLastError());
-        GZ_TRY(e, hipMemcpyAsync(carry.data(), d_windows.as<uint8_t>() + uint64_t(live) * kWindow, kWindow, hipMemcpyDeviceToHost, stream));
-        GZ_TRY(e, hipStreamSynchronize(stream));
-        GZ_TRACE("windows and bytes of %u units done, %llu bytes of text so far", live, (unsigned long long)total);
-        at = at + live < hi && final_seen ? hi : at + live;                  // (units of the batch behind a repair that were not reached are decoded with the next batch)
+        if ((rc = run.repair_in_one_launch()) || !run.good) return rc;
+        if ((rc = run.walk_chain(live)) || !run.good) return rc;
+        if (live) rc = run.windows_and_bytes(live);
     }
-    if (!good || !final_seen) return FQD_OK;                                  // *ok stays 0: the caller reads the file the host way
-
-    // ---- CRC-32 and length of every member's text against its trailer
-    if (members.empty()) return FQD_OK;
-    uint32_t crc = 0;
-    {
-        uint32_t shift[8][32];
-        Mat m = mat_one_zero_byte();
-        for (int k = 0; k < 8; ++k) m = mat_square(m);                        // 256 zero bytes
-        for (int k = 0; k < 8; ++k) { std::memcpy(shift[k], m.col, sizeof m.col); m = mat_square(m); }
-        const Mat slice_mat = m;                                              // 65536 zero bytes
-        GZ_TRY(e, hipMemcpyAsync(d_shift.p, shift, sizeof shift, hipMemcpyHostToDevice, stream));
-        std::vector<uint32_t> raw;
-        for (const Member& mb : members) {
-            const uint64_t len = mb.text_to - mb.text_from;
-            crc = 0;
-            if (len) {
-                const uint64_t n_slices = (len + kSlice - 1) / kSlice;
-                hipLaunchKernelGGL(gz_crc_kernel, dim3(uint32_t(std::min<uint64_t>(n_slices, uint64_t(n_cu) * 8u))), dim3(kCrcThreads), 0, stream,
-                                   static_cast<const uint8_t*>(text) + mb.text_from, len, n_slices, d_shift.as<const uint32_t>(), d_raw.as<uint32_t>());
-                GZ_TRY(e, hipGetLastError());
-                raw.resize(n_slices);
-                GZ_TRY(e, hipMemcpyAsync(raw.data(), d_raw.p, n_slices * 4, hipMemcpyDeviceToHost, stream));
-                GZ_TRY(e, hipStreamSynchronize(stream));
-                // raw register of the member's text started from 0: full slices fold with the 64 KiB matrix, the short last one with its own length
-                uint32_t reg = 0;
-                for (uint64_t sl = 0; sl < n_slices; ++sl) {
-                    const uint64_t l = sl + 1 < n_slices ? kSlice : len - sl * kSlice;
-                    reg = (l == kSlice ? mat_apply(slice_mat, reg) : advance_zero_bytes(reg, l)) ^ raw[sl];
-                }
-                crc = reg ^ advance_zero_bytes(0xFFFFFFFFu, len) ^ 0xFFFFFFFFu;   // the same register started from all ones, then inverted: zlib's CRC-32
-            }
-            if (crc != mb.crc || uint32_t(len) != mb.isize) { GZ_TRACE("a member's CRC-32 or length is not its trailer's"); return FQD_OK; }   // *ok stays 0
-        }
-    }
-    GZ_TRACE("%zu member(s): CRC-32 and length as the trailers say", members.size());
-    *text_bytes = total;
-    *deflate_bytes = members.back().deflate_end;
-    *crc32 = crc;
-    *ok = 1;
-    return FQD_OK;
+    if (rc || !run.good || !run.final_seen) return rc;                        // (FQD_OK and *ok stays 0: the caller reads the file the host way)
+    return run.check_members(text_bytes, deflate_bytes, crc32, ok);
 }
 
 } // extern "C"

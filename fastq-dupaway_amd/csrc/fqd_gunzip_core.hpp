@@ -422,5 +422,19 @@ FQD_HD uint8_t window_byte(const uint8_t* prev, const uint16_t* sym, uint64_t n,
     return prev[k + n];
 }
 
+// A member's header (RFC 1952) in the n bytes at p: the offset behind its optional fields (FEXTRA, FNAME, FCOMMENT, FHCRC), where
+// the deflate stream starts; 0: not a gzip/deflate header, or one that does not end within the n bytes.  (Host side only.)
+static inline size_t gzip_header_len(const uint8_t* p, size_t n)
+{
+    if (n < 18 || p[0] != 31 || p[1] != 139 || p[2] != 8) return 0;
+    const uint8_t flg = p[3];
+    size_t at = 10;
+    if (flg & 4) at += 2 + (p[at] | (size_t(p[at + 1]) << 8));
+    if (flg & 8) { while (at < n && p[at]) ++at; ++at; }
+    if (flg & 16) { while (at < n && p[at]) ++at; ++at; }
+    if (flg & 2) at += 2;
+    return at <= n ? at : 0;
+}
+
 } // namespace gunz
 } // namespace fqd

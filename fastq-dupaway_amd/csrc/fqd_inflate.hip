@@ -16,42 +16,15 @@
 #include <cstdio>
 #include <cstring>
 
-#include "../../include/fqdupaway.h"
 #include "fqd_bgzf_core.hpp"
 #include "fqd_inflate_wave.hpp"
-
-#define FQD_HIDDEN __attribute__((visibility("hidden")))
-FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_device(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg);
-FQD_HIDDEN int fqd_internal_scratch(fqd_engine* e, int which, size_t bytes, void** out);
+#include "fqd_internal.hpp"
 
 namespace {
 
-#define INF_TRY(e, expr)                                                                    \
-    do { hipError_t err_ = (expr); if (err_ != hipSuccess) { (void)hipGetLastError();       \
-        return fqd_internal_fail(e, FQD_ERR_HIP, hipGetErrorString(err_)); } } while (0)
-
 constexpr uint32_t kWave = 64;
 
-// The wave as fqd_inflate_wave.hpp sees it: a workgroup IS one wave, so the workgroup barrier costs nothing and makes
-// the LDS and global writes of a phase visible to the next.
-struct WaveCtx {
-    static constexpr uint32_t kLanes = kWave;
-    uint32_t lane;
-    template <class F> __device__ __forceinline__ void lanes(F f) { f(lane); __syncthreads(); }
-    template <class F> __device__ __forceinline__ void lanes_open(F f) { f(lane); }
-    __device__ __forceinline__ void sync() { __syncthreads(); }
-    template <class F> __device__ __forceinline__ uint64_t ballot(F f) { return __ballot(f(lane) ? 1 : 0); }
-    __device__ __forceinline__ uint32_t same(uint32_t v) const { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
-    __device__ __forceinline__ void add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
-#ifdef FQD_STAMPS
-    unsigned long long last = 0, spent[8] = {};
-    __device__ __forceinline__ void mark(int k) { const unsigned long long now = __builtin_readcyclecounter(); spent[k] += now - last; last = now; }
-#else
-    __device__ __forceinline__ void mark(int) {}
-#endif
-};
+using fqd::winf::WaveCtx;
 #ifdef FQD_STAMPS
 __device__ unsigned long long g_inflate_cycles[8];
 #endif
@@ -322,7 +295,7 @@ int fqd_bgzf_inflate_async(fqd_engine* e, const uint8_t* comp, const uint64_t* c
     if (!bad_counters || (n_members && (!comp || !comp_off || !comp_len || !out_off || !out_len || !crc || !text)))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_bgzf_inflate_async: bad arguments");
     if (n_members == 0) return FQD_OK;
-    INF_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const uint32_t grid = uint32_t(std::min<uint64_t>(n_members, 256u * kInflateWavesPerCu));
     const size_t lens_bytes = round_up(sizeof(fqd::winf::Token) * fqd::winf::kTokenRoom * grid, 256);
@@ -333,10 +306,10 @@ int fqd_bgzf_inflate_async(fqd_engine* e, const uint8_t* comp, const uint64_t* c
     unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(bad_counters);
     hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid), dim3(kWave), 0, stream, comp, comp_off, comp_len, out_off, out_len, n_members,
                        text, d_tokens, d_bad);
-    INF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(bgzf_check_crc_kernel, dim3(uint32_t(std::min<uint64_t>(n_members, 2048))), dim3(fqd::bgzf::kThreads), 0, stream,
                        static_cast<const uint8_t*>(text), out_off, out_len, crc, n_members, d_bad + 1);
-    INF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     return FQD_OK;
 }
 
@@ -349,7 +322,7 @@ int fqd_bgzf_inflate(fqd_engine* e, const uint8_t* comp, const uint64_t* comp_of
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_bgzf_inflate: bad arguments");
     *n_bad = 0;
     if (n_members == 0) return FQD_OK;
-    INF_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const uint32_t grid = uint32_t(std::min<uint64_t>(n_members, 256u * kInflateWavesPerCu));
     const size_t lens_bytes = round_up(sizeof(fqd::winf::Token) * fqd::winf::kTokenRoom * grid, 256);
@@ -358,21 +331,21 @@ int fqd_bgzf_inflate(fqd_engine* e, const uint8_t* comp, const uint64_t* comp_of
     if (rc != FQD_OK) return rc;
     unsigned long long* d_bad = static_cast<unsigned long long*>(base);
     fqd::winf::Token* d_tokens = reinterpret_cast<fqd::winf::Token*>(static_cast<uint8_t*>(base) + 256);
-    INF_TRY(e, hipMemsetAsync(d_bad, 0, 256, stream));
+    FQD_TRY(e, hipMemsetAsync(d_bad, 0, 256, stream));
     hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid), dim3(kWave), 0, stream, comp, comp_off, comp_len, out_off, out_len, n_members,
                        text, d_tokens, d_bad);
-    INF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(bgzf_check_crc_kernel, dim3(uint32_t(std::min<uint64_t>(n_members, 2048))), dim3(fqd::bgzf::kThreads), 0, stream,
                        static_cast<const uint8_t*>(text), out_off, out_len, crc, n_members, d_bad + 1);
-    INF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     unsigned long long bad[2] = {0, 0};
-    INF_TRY(e, hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, stream));
-    INF_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
 #ifdef FQD_STAMPS
     {
         unsigned long long c[8] = {}, zero[8] = {};
-        INF_TRY(e, hipMemcpyFromSymbol(c, HIP_SYMBOL(g_inflate_cycles), sizeof c));
-        INF_TRY(e, hipMemcpyToSymbol(HIP_SYMBOL(g_inflate_cycles), zero, sizeof zero));
+        FQD_TRY(e, hipMemcpyFromSymbol(c, HIP_SYMBOL(g_inflate_cycles), sizeof c));
+        FQD_TRY(e, hipMemcpyToSymbol(HIP_SYMBOL(g_inflate_cycles), zero, sizeof zero));
         unsigned long long all = 0; for (int k = 0; k < 8; ++k) all += c[k];
         const char* name[8] = {"headers", "tables", "count rounds", "prefix", "write pass", "match order", "stored", "match copies"};
         std::fprintf(stderr, "[inflate cycles, summed over waves] total %.3e:", double(all));
@@ -390,7 +363,7 @@ int fqd_count_lines(fqd_engine* e, const uint8_t* text, uint64_t n, uint64_t* n_
     if (!n_lines || (n && !text)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_count_lines: bad arguments");
     *n_lines = 0;
     if (n == 0) return FQD_OK;
-    INF_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const uint64_t tiles = (n + kScanTile - 1) / kScanTile;
     void* base = nullptr;
@@ -400,11 +373,11 @@ int fqd_count_lines(fqd_engine* e, const uint8_t* text, uint64_t n, uint64_t* n_
     uint32_t* counts = static_cast<uint32_t*>(base);
     uint64_t* offs = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(base) + counts_bytes);
     hipLaunchKernelGGL(count_newlines_kernel, dim3(uint32_t(std::min<uint64_t>(tiles, 8192))), dim3(kScanThreads), 0, stream, text, n, tiles, counts);
-    INF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     launch_tile_offsets(stream, counts, tiles, offs, reinterpret_cast<unsigned long long*>(offs + tiles + 1));
-    INF_TRY(e, hipGetLastError());
-    INF_TRY(e, hipMemcpyAsync(n_lines, offs + tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    INF_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipMemcpyAsync(n_lines, offs + tiles, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     return FQD_OK;
 }
 
@@ -417,7 +390,7 @@ int fqd_scan_records(fqd_engine* e, const uint8_t* text, uint64_t n, uint32_t li
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_scan_records: bad arguments");
     *well_formed = 0;
     if (n == 0) { *well_formed = n_records == 0; return FQD_OK; }
-    INF_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const uint64_t tiles = (n + kScanTile - 1) / kScanTile;
     // the line count of the text decides how much scratch the newline positions need: counted first
@@ -425,8 +398,8 @@ int fqd_scan_records(fqd_engine* e, const uint8_t* text, uint64_t n, uint32_t li
     int rc = fqd_count_lines(e, text, n, &n_lines);
     if (rc != FQD_OK) return rc;
     uint8_t last_byte = 0;
-    INF_TRY(e, hipMemcpyAsync(&last_byte, text + n - 1, 1, hipMemcpyDeviceToHost, stream));
-    INF_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&last_byte, text + n - 1, 1, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     if (last_byte != uint8_t('\n') || n_lines != n_records * lines_per_record) return FQD_OK;       // not well formed: nothing written
     if (n_records == 0) { *well_formed = 1; return FQD_OK; }
     const size_t counts_bytes = round_up(tiles * sizeof(uint32_t), 256), offs_bytes = round_up((tiles + 1 + kOffsetParts) * sizeof(uint64_t), 256);
@@ -440,18 +413,18 @@ int fqd_scan_records(fqd_engine* e, const uint8_t* text, uint64_t n, uint32_t li
     // (the scratch may have moved when it grew: the counts are made again, it takes microseconds)
     hipLaunchKernelGGL(count_newlines_kernel, dim3(uint32_t(std::min<uint64_t>(tiles, 8192))), dim3(kScanThreads), 0, stream, text, n, tiles, counts);
     launch_tile_offsets(stream, counts, tiles, offs, reinterpret_cast<unsigned long long*>(offs + tiles + 1));
-    INF_TRY(e, hipGetLastError());
-    INF_TRY(e, hipMemsetAsync(d_flags, 0, 256, stream));
+    FQD_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipMemsetAsync(d_flags, 0, 256, stream));
     hipLaunchKernelGGL(newline_positions_kernel, dim3(uint32_t(std::min<uint64_t>(tiles, 8192))), dim3(kScanThreads), 0, stream, text, n, tiles,
                        static_cast<const uint64_t*>(offs), nl_pos);
-    INF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(records_kernel, dim3(uint32_t(std::min<uint64_t>((n_records + 255) / 256, 8192))), dim3(256), 0, stream, text,
                        static_cast<const uint64_t*>(nl_pos), n_records, lines_per_record, uint8_t(lines_per_record == 4 ? '@' : '>'),
                        start, seq_off, id_len, seq_len, size, d_flags);
-    INF_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     uint32_t flags = 0;
-    INF_TRY(e, hipMemcpyAsync(&flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, stream));
-    INF_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     *well_formed = flags == 0;
     return FQD_OK;
 }

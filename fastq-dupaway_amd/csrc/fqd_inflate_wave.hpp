@@ -755,5 +755,26 @@ FQD_HD uint32_t inflate_stretch(Ctx& ctx, S& sh, const uint8_t* comp, uint32_t c
     return inflate_impl<true>(ctx, sh, comp, comp_len, first_bit, stop_bit, out, out_start, out_len, tok, info, out2);
 }
 
+#if defined(__HIPCC__)
+// The wave as the code above sees it on the GPU (fqd_inflate.hip, fqd_gunzip.hip): a workgroup IS one 64-lane wave, so the
+// workgroup barrier costs nothing and makes the LDS and global writes of a phase visible to the next.
+struct WaveCtx {
+    static constexpr uint32_t kLanes = 64;
+    uint32_t lane;
+    template <class F> __device__ __forceinline__ void lanes(F f) { f(lane); __syncthreads(); }
+    template <class F> __device__ __forceinline__ void lanes_open(F f) { f(lane); }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+    template <class F> __device__ __forceinline__ uint64_t ballot(F f) { return __ballot(f(lane) ? 1 : 0); }
+    __device__ __forceinline__ uint32_t same(uint32_t v) const { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
+    __device__ __forceinline__ void add(uint32_t* p, uint32_t v) { atomicAdd(p, v); }
+#ifdef FQD_STAMPS
+    unsigned long long last = 0, spent[8] = {};
+    __device__ __forceinline__ void mark(int k) { const unsigned long long now = __builtin_readcyclecounter(); spent[k] += now - last; last = now; }
+#else
+    __device__ __forceinline__ void mark(int) {}
+#endif
+};
+#endif
+
 } // namespace winf
 } // namespace fqd

@@ -31,28 +31,13 @@
 #include <algorithm>
 #include <cstring>
 
-#include "../../include/fqdupaway.h"
-
-#define FQD_HIDDEN __attribute__((visibility("hidden")))
-FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_device(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg);
-FQD_HIDDEN int fqd_internal_scratch(fqd_engine* e, int which, size_t bytes, void** out);
+#include "fqd_internal.hpp"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kFileB = 0x80000000u;             // payload of a record of file 2: kFileB | index
-
-#define JOIN_TRY(e, expr)                                                                   \
-    do { hipError_t err_ = (expr); if (err_ != hipSuccess) { (void)hipGetLastError();       \
-        return fqd_internal_fail(e, FQD_ERR_HIP, hipGetErrorString(err_)); } } while (0)
-
-inline uint32_t grid_for(uint64_t n, uint32_t per_block = kBlock, uint32_t cap = 4096)
-{
-    return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap)));
-}
 
 // ---------------------------------------------------------------------------------------------
 // 1. tag extraction (fastqview.cpp:190-204; fastaview.cpp:153-167 is the same rule): the tag
@@ -864,16 +849,6 @@ void plan_offsets_kernel(const uint32_t* __restrict__ len, uint64_t n, const uns
 }
 
 // ---------------------------------------------------------------------------------------------
-struct Carver {                                       // 256-byte aligned pieces of one scratch block
-    char* p; size_t used = 0;
-    template <class T> T* take(size_t count)
-    {
-        T* r = p ? reinterpret_cast<T*>(p + used) : nullptr;
-        used += (count * sizeof(T) + 255) & ~size_t(255);
-        return r;
-    }
-};
-
 struct SortBuffers {
     uint64_t *keys[2]; uint32_t *vals[2]; uint32_t *counts, *tot;
     uint32_t *bitmap; uint8_t* rank; uint32_t *width, *lsb, *vary, *info;
@@ -893,12 +868,12 @@ int sort_union(fqd_engine* e, hipStream_t stream, const Union& u, const SortBuff
     hipLaunchKernelGGL(iota_payload_kernel, dim3(grid_for(N)), dim3(kBlock), 0, stream, sb.vals[0], u.n_a, u.n_b);
     uint32_t info[2] = {0, 0};
     if (max_len) {
-        JOIN_TRY(e, hipMemsetAsync(sb.bitmap, 0, size_t(max_len) * 8 * sizeof(uint32_t), stream));
+        FQD_TRY(e, hipMemsetAsync(sb.bitmap, 0, size_t(max_len) * 8 * sizeof(uint32_t), stream));
         hipLaunchKernelGGL(census_kernel, dim3(grid_for(N, kBlock, 1024)), dim3(kBlock), 0, stream, u, max_len, sb.bitmap);
         hipLaunchKernelGGL(build_codes_kernel, dim3(1), dim3(1024), 0, stream,
                            static_cast<const uint32_t*>(sb.bitmap), min_len, max_len, ct);
-        JOIN_TRY(e, hipMemcpyAsync(info, sb.info, sizeof info, hipMemcpyDeviceToHost, stream));
-        JOIN_TRY(e, hipStreamSynchronize(stream));       // the key width decides how many passes are launched
+        FQD_TRY(e, hipMemcpyAsync(info, sb.info, sizeof info, hipMemcpyDeviceToHost, stream));
+        FQD_TRY(e, hipStreamSynchronize(stream));       // the key width decides how many passes are launched
     }
     const uint32_t B = info[0];
     // Every 64 key bits cost an encode and up to eight radix passes over all records: tags that need tens of
@@ -926,7 +901,7 @@ int sort_union(fqd_engine* e, hipStream_t stream, const Union& u, const SortBuff
             cur ^= 1;
         }
     }
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     *cur_out = cur; *key_words_out = W;
     return FQD_OK;
 }
@@ -957,17 +932,17 @@ int carve(fqd_engine* e, uint64_t N, uint64_t n_a, uint32_t max_len_cap, bool si
 int length_range(fqd_engine* e, hipStream_t stream, const Union& u, unsigned int* d_min_max, uint32_t* min_len, uint32_t* max_len)
 {
     unsigned int init[2] = {0xFFFFFFFFu, 0u}, got[2] = {0, 0};
-    JOIN_TRY(e, hipMemcpyAsync(d_min_max, init, sizeof init, hipMemcpyHostToDevice, stream));
+    FQD_TRY(e, hipMemcpyAsync(d_min_max, init, sizeof init, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(len_range_kernel, dim3(grid_for(u.n_a + u.n_b, kBlock, 1024)), dim3(kBlock), 0, stream, u, d_min_max);
-    JOIN_TRY(e, hipMemcpyAsync(got, d_min_max, sizeof got, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(got, d_min_max, sizeof got, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     *min_len = got[0]; *max_len = got[1];
     return FQD_OK;
 }
 
 int run_join(fqd_engine* e, const fqd_tags* a, const fqd_tags* b, const fqd_join* out, uint32_t* perm_only)
 {
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const Union u{a->bytes, a->offsets, a->lengths, a->n, b ? b->bytes : nullptr, b ? b->offsets : nullptr, b ? b->lengths : nullptr, b ? b->n : 0};
     const uint64_t N = u.n_a + u.n_b;
@@ -987,20 +962,20 @@ int run_join(fqd_engine* e, const fqd_tags* a, const fqd_tags* b, const fqd_join
     if ((rc = sort_union(e, stream, u, sb, max_len, min_len, max_len, &cur, &W))) return rc;
     const uint64_t* keys = sb.keys[cur]; const uint32_t* vals = sb.vals[cur];
     if (perm_only) {                                   // fqd_sort_tags: the sorted payloads are the permutation
-        JOIN_TRY(e, hipMemcpyAsync(perm_only, vals, N * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-        JOIN_TRY(e, hipStreamSynchronize(stream));      // the scratch may be reused by the next call
+        FQD_TRY(e, hipMemcpyAsync(perm_only, vals, N * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        FQD_TRY(e, hipStreamSynchronize(stream));      // the scratch may be reused by the next call
         return FQD_OK;
     }
-    if (W == 0) JOIN_TRY(e, hipMemsetAsync(sb.keys[cur], 0, N * sizeof(uint64_t), stream));   // all tags equal: one run
+    if (W == 0) FQD_TRY(e, hipMemsetAsync(sb.keys[cur], 0, N * sizeof(uint64_t), stream));   // all tags equal: one run
     hipLaunchKernelGGL(heads_kernel, dim3(grid_for(N, kBlock, 2048)), dim3(kBlock), 0, stream, u, keys, vals, N, W, sb.head);
     const uint32_t j_tiles = uint32_t((N + kJoinTile - 1) / kJoinTile);
     hipLaunchKernelGGL(join_summary_kernel, dim3(j_tiles), dim3(kBlock), 0, stream, vals, static_cast<const uint8_t*>(sb.head), N, sb.carry);
     hipLaunchKernelGGL(join_carry_scan_kernel, dim3(1), dim3(1024), 0, stream, sb.carry, j_tiles);
-    if (u.n_a) JOIN_TRY(e, hipMemsetAsync(out->match_a, 0xFF, u.n_a * sizeof(uint32_t), stream));
+    if (u.n_a) FQD_TRY(e, hipMemsetAsync(out->match_a, 0xFF, u.n_a * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(join_emit_kernel, dim3(j_tiles), dim3(kBlock), 0, stream, vals, static_cast<const uint8_t*>(sb.head), N,
                        static_cast<const JoinCarry*>(sb.carry), out->perm_a, out->perm_b, out->match_a, out->match_b);
     const uint32_t p_tiles = uint32_t((u.n_a + kPairTile - 1) / kPairTile);
-    JOIN_TRY(e, hipMemsetAsync(sb.n_pairs, 0, sizeof(unsigned long long), stream));
+    FQD_TRY(e, hipMemsetAsync(sb.n_pairs, 0, sizeof(unsigned long long), stream));
     if (p_tiles) {
         hipLaunchKernelGGL(pair_count_kernel, dim3(p_tiles), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(out->match_a), u.n_a, sb.pair_tiles);
         hipLaunchKernelGGL(u32_scan_kernel, dim3(1), dim3(1024), 0, stream, sb.pair_tiles, p_tiles, sb.n_pairs);
@@ -1008,10 +983,10 @@ int run_join(fqd_engine* e, const fqd_tags* a, const fqd_tags* b, const fqd_join
                            static_cast<const uint32_t*>(out->perm_a), static_cast<const uint32_t*>(out->perm_b), u.n_a,
                            static_cast<const uint32_t*>(sb.pair_tiles), out->pair_a, out->pair_b);
     }
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     unsigned long long n_pairs = 0;
-    JOIN_TRY(e, hipMemcpyAsync(&n_pairs, sb.n_pairs, sizeof n_pairs, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&n_pairs, sb.n_pairs, sizeof n_pairs, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     if (out->n_pairs) *out->n_pairs = n_pairs;
     return FQD_OK;
 }
@@ -1038,7 +1013,7 @@ FQD_HIDDEN int fqd_internal_radix_sort(fqd_engine* e, hipStream_t stream, uint64
                            keys[cur ^ 1], vals[cur ^ 1]);
         cur ^= 1;
     }
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     *cur_io = cur;
     return FQD_OK;
 }
@@ -1052,10 +1027,10 @@ int fqd_extract_tags(fqd_engine* e, const uint8_t* text, const uint64_t* id_star
     if (n && (!text || !id_start || !id_len || !tag_off || !tag_len))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_extract_tags: bad arguments");
     if (n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipLaunchKernelGGL(extract_tags_kernel, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, fqd_internal_stream(e),
                        text, id_start, id_len, n, tag_off, tag_len);
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     return FQD_OK;
 }
 
@@ -1087,9 +1062,9 @@ int fqd_copy_spans(fqd_engine* e, const uint8_t* src, const uint64_t* src_off, c
     if (!e) return FQD_ERR_ARG;
     if (n && (!src || !src_off || !len || !dst || !dst_off)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_copy_spans: bad arguments");
     if (n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipLaunchKernelGGL(copy_spans_kernel, dim3(grid_for(n * kSpanLanes, kBlock, 8192)), dim3(kBlock), 0, fqd_internal_stream(e), src, src_off, len, n, dst, dst_off);
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     return FQD_OK;
 }
 
@@ -1100,21 +1075,21 @@ int fqd_count_tags_le(fqd_engine* e, const fqd_tags* t, const fqd_tags* other, u
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_count_tags_le: bad arguments");
     *count = 0;
     if (t->n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     void* base = nullptr;
     int rc = fqd_internal_scratch(e, 1, 4096, &base);
     if (rc) return rc;
     unsigned long long* d_count = static_cast<unsigned long long*>(base);
     uint64_t off = 0; uint32_t len = 0;
-    JOIN_TRY(e, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
-    JOIN_TRY(e, hipMemcpyAsync(&off, other->offsets + other_index, sizeof off, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipMemcpyAsync(&len, other->lengths + other_index, sizeof len, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
+    FQD_TRY(e, hipMemcpyAsync(&off, other->offsets + other_index, sizeof off, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipMemcpyAsync(&len, other->lengths + other_index, sizeof len, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     hipLaunchKernelGGL(count_le_kernel, dim3(grid_for(t->n, kBlock, 2048)), dim3(kBlock), 0, stream, *t, other->bytes + off, len, d_count);
     unsigned long long got = 0;
-    JOIN_TRY(e, hipMemcpyAsync(&got, d_count, sizeof got, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&got, d_count, sizeof got, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     *count = got;
     return FQD_OK;
 }
@@ -1126,7 +1101,7 @@ int fqd_output_offsets(fqd_engine* e, const uint8_t* keep, const uint32_t* idx, 
     if (!total || (n && (!keep || !idx || !sizes || !dest))) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_output_offsets: bad arguments");
     *total = 0;
     if (n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const uint32_t tiles = uint32_t((n + kOffTile - 1) / kOffTile);
     void* base = nullptr;
@@ -1138,10 +1113,10 @@ int fqd_output_offsets(fqd_engine* e, const uint8_t* keep, const uint32_t* idx, 
     hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
     hipLaunchKernelGGL(out_offsets_kernel, dim3(tiles), dim3(kBlock), 0, stream, keep, idx, n, sizes,
                        static_cast<const unsigned long long*>(tile), reinterpret_cast<unsigned long long*>(dest));
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     unsigned long long got = 0;
-    JOIN_TRY(e, hipMemcpyAsync(&got, d_total, sizeof got, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&got, d_total, sizeof got, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     *total = got;
     return FQD_OK;
 }
@@ -1154,7 +1129,7 @@ int fqd_output_plan(fqd_engine* e, const uint8_t* keep, const uint32_t* idx, uin
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_output_plan: bad arguments");
     *total = 0;
     if (n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     const uint32_t tiles = uint32_t((n + kOffTile - 1) / kOffTile);
     void* base = nullptr;
@@ -1166,10 +1141,10 @@ int fqd_output_plan(fqd_engine* e, const uint8_t* keep, const uint32_t* idx, uin
     hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
     hipLaunchKernelGGL(plan_offsets_kernel, dim3(tiles), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(len), n,
                        static_cast<const unsigned long long*>(tile), reinterpret_cast<unsigned long long*>(dst_off));
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     unsigned long long got = 0;
-    JOIN_TRY(e, hipMemcpyAsync(&got, d_total, sizeof got, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&got, d_total, sizeof got, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     *total = got;
     return FQD_OK;
 }
@@ -1181,10 +1156,10 @@ int fqd_gather_seqs(fqd_engine* e, const uint32_t* idx, uint64_t n, const uint64
     if (n && (!idx || !off_table || !len_table || !off_out || !len_out))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_gather_seqs: bad arguments");
     if (n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipLaunchKernelGGL(gather_seq_kernel, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, fqd_internal_stream(e),
                        idx, n, off_table, len_table, off_out, len_out);
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     return FQD_OK;
 }
 
@@ -1195,10 +1170,10 @@ int fqd_classify_tags(fqd_engine* e, const fqd_tags* t, const uint8_t* split_byt
     if (!t || (t->n && (!t->offsets || !t->lengths || !range_out)) || (n_split && (!split_bytes || !split_len)))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_classify_tags: bad arguments");
     if (t->n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipLaunchKernelGGL(classify_tags_kernel, dim3(grid_for(t->n, kBlock, 4096)), dim3(kBlock), 0, fqd_internal_stream(e),
                        *t, split_bytes, split_stride, split_len, n_split, range_out);
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     return FQD_OK;
 }
 
@@ -1208,17 +1183,17 @@ int fqd_range_keep(fqd_engine* e, const uint32_t* range, uint64_t n, uint32_t wh
     if (!count || (n && (!range || !keep))) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_range_keep: bad arguments");
     *count = 0;
     if (n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     void* base = nullptr;
     int rc = fqd_internal_scratch(e, 1, 4096, &base);
     if (rc) return rc;
     unsigned long long* d_count = static_cast<unsigned long long*>(base);
-    JOIN_TRY(e, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
+    FQD_TRY(e, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(range_keep_kernel, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, stream, range, n, which, keep, d_count);
     unsigned long long got = 0;
-    JOIN_TRY(e, hipMemcpyAsync(&got, d_count, sizeof got, hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(&got, d_count, sizeof got, hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     *count = got;
     return FQD_OK;
 }
@@ -1228,10 +1203,10 @@ int fqd_sample_tags(fqd_engine* e, const fqd_tags* t, uint32_t n_samples, uint32
     if (!e) return FQD_ERR_ARG;
     if (!t || !t->n || !n_samples || !stride || !out_bytes || !out_len || !t->offsets || !t->lengths)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_sample_tags: bad arguments");
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipLaunchKernelGGL(sample_tags_kernel, dim3((n_samples + kBlock - 1) / kBlock), dim3(kBlock), 0, fqd_internal_stream(e),
                        *t, n_samples, stride, out_bytes, out_len);
-    JOIN_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     return FQD_OK;
 }
 
@@ -1241,16 +1216,16 @@ int fqd_max_u32(fqd_engine* e, const uint32_t* values, uint64_t n, uint32_t* max
     if (!max_out || (n && !values)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_max_u32: bad arguments");
     *max_out = 0;
     if (n == 0) return FQD_OK;
-    JOIN_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t stream = fqd_internal_stream(e);
     void* base = nullptr;
     int rc = fqd_internal_scratch(e, 1, 4096, &base);
     if (rc) return rc;
     uint32_t* d = static_cast<uint32_t*>(base);
-    JOIN_TRY(e, hipMemsetAsync(d, 0, sizeof(uint32_t), stream));
+    FQD_TRY(e, hipMemsetAsync(d, 0, sizeof(uint32_t), stream));
     hipLaunchKernelGGL(max_u32_kernel, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, stream, values, n, d);
-    JOIN_TRY(e, hipMemcpyAsync(max_out, d, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    JOIN_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, hipMemcpyAsync(max_out, d, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    FQD_TRY(e, hipStreamSynchronize(stream));
     return FQD_OK;
 }
 

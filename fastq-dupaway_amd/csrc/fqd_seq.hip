@@ -26,32 +26,14 @@
 #include <cstdio>
 #include <cstring>
 
-#include "../../include/fqdupaway.h"
+#include "fqd_internal.hpp"
 #include "fqd_seq_core.hpp"
-
-#define FQD_HIDDEN __attribute__((visibility("hidden")))
-FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_device(fqd_engine* e);
-FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg);
-FQD_HIDDEN int fqd_internal_scratch(fqd_engine* e, int which, size_t bytes, void** out);
-FQD_HIDDEN size_t fqd_internal_radix_counts(uint64_t N);
-FQD_HIDDEN int fqd_internal_radix_sort(fqd_engine* e, hipStream_t stream, uint64_t* const keys[2], uint32_t* const vals[2],
-                                       uint32_t* counts, uint32_t* tot, uint64_t N, uint32_t nbits, int* cur_io);
 
 namespace {
 
 using fqdseq::View;
 
 constexpr int kBlock = 256;
-
-#define SEQ_TRY(e, expr)                                                                    \
-    do { hipError_t err_ = (expr); if (err_ != hipSuccess) { (void)hipGetLastError();       \
-        return fqd_internal_fail(e, FQD_ERR_HIP, hipGetErrorString(err_)); } } while (0)
-
-inline uint32_t grid_for(uint64_t n, uint32_t per_block = kBlock, uint32_t cap = 4096)
-{
-    return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, cap)));
-}
 
 // The records' sequences: mate 1, and mate 2 when b2 != nullptr.
 struct Mates {
@@ -350,16 +332,6 @@ void count_kernel(const uint8_t* __restrict__ f, uint64_t n, unsigned long long*
 }
 
 // ---------------------------------------------------------------------------------------------
-struct Carver {                                       // 256-byte aligned pieces of one scratch block
-    char* p; size_t used = 0;
-    template <class T> T* take(size_t count)
-    {
-        T* r = p ? reinterpret_cast<T*>(p + used) : nullptr;
-        used += (count * sizeof(T) + 255) & ~size_t(255);
-        return r;
-    }
-};
-
 struct SortBuffers {
     uint64_t* keys[2]; uint32_t* vals[2]; uint32_t *counts, *tot;
     uint32_t *q, *pos, *nq, *npos, *nrid, *bnd_excl, *keep_excl, *tiles, *total;
@@ -390,10 +362,10 @@ int exclusive_scan(fqd_engine* e, hipStream_t s, const uint8_t* f, uint64_t coun
     hipLaunchKernelGGL(tile_sum_kernel, dim3(tiles), dim3(kBlock), 0, s, f, count, b.tiles);
     hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, b.tiles, tiles, b.total);
     hipLaunchKernelGGL(tile_apply_kernel, dim3(tiles), dim3(kBlock), 0, s, f, count, static_cast<const uint32_t*>(b.tiles), excl);
-    SEQ_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     if (total) {
-        SEQ_TRY(e, hipMemcpyAsync(total, b.total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        SEQ_TRY(e, hipStreamSynchronize(s));
+        FQD_TRY(e, hipMemcpyAsync(total, b.total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        FQD_TRY(e, hipStreamSynchronize(s));
     }
     return FQD_OK;
 }
@@ -407,7 +379,7 @@ bool bad_tags(const fqd_tags* t, uint64_t n)
 
 int run_sort(fqd_engine* e, const fqd_tags* t1, const fqd_tags* t2, uint32_t* perm)
 {
-    SEQ_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t s = fqd_internal_stream(e);
     const uint64_t n = t1->n;
     const Mates m{t1->bytes, t1->offsets, t1->lengths, t2 ? t2->bytes : nullptr, t2 ? t2->offsets : nullptr, t2 ? t2->lengths : nullptr};
@@ -418,11 +390,11 @@ int run_sort(fqd_engine* e, const fqd_tags* t1, const fqd_tags* t2, uint32_t* pe
     if (rc) return rc;
     uint32_t* d_info = static_cast<uint32_t*>(small);
     uint32_t info[16] = {};
-    SEQ_TRY(e, hipMemsetAsync(d_info, 0, sizeof info, s));
+    FQD_TRY(e, hipMemsetAsync(d_info, 0, sizeof info, s));
     hipLaunchKernelGGL(census_kernel, dim3(grid_for(n, kBlock, 1024)), dim3(kBlock), 0, s, m, n, d_info);
-    SEQ_TRY(e, hipGetLastError());
-    SEQ_TRY(e, hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, s));
-    SEQ_TRY(e, hipStreamSynchronize(s));
+    FQD_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipMemcpyAsync(info, d_info, sizeof info, hipMemcpyDeviceToHost, s));
+    FQD_TRY(e, hipStreamSynchronize(s));
     for (uint32_t c = 0; c < uint32_t('\n'); ++c)
         if ((info[c >> 5] >> (c & 31u)) & 1u) {
             char msg[200];
@@ -445,19 +417,19 @@ int run_sort(fqd_engine* e, const fqd_tags* t1, const fqd_tags* t2, uint32_t* pe
     void* base = nullptr;
     if ((rc = fqd_internal_scratch(e, 0, bytes, &base))) return rc;
     carve(n, b, static_cast<char*>(base), &bytes);
-    SEQ_TRY(e, hipMemcpyAsync(b.rank, rank, sizeof rank, hipMemcpyHostToDevice, s));
+    FQD_TRY(e, hipMemcpyAsync(b.rank, rank, sizeof rank, hipMemcpyHostToDevice, s));
     const uint8_t* d_rank = b.rank;
 
     // 3. the sort: every record by word 0, then the mixed runs level by level
     const uint32_t npos0 = W ? uint32_t(std::min<uint64_t>(P, T)) : 0u;
     hipLaunchKernelGGL(encode_kernel, dim3(grid_for(n, kBlock, 2048)), dim3(kBlock), 0, s, m, M1, static_cast<const uint32_t*>(nullptr), n,
                        0u, npos0, w, d_rank, b.keys[0], b.vals[0], static_cast<uint64_t*>(nullptr));
-    SEQ_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     int cur = 0;
     if ((rc = fqd_internal_radix_sort(e, s, b.keys, b.vals, b.counts, b.tot, n, npos0 * w, &cur))) return rc;
     hipLaunchKernelGGL(first_list_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, static_cast<const uint64_t*>(b.keys[cur]),
                        static_cast<const uint32_t*>(b.vals[cur]), n, b.q, b.pos, b.bnd, perm);
-    SEQ_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     uint64_t count = n;
     for (uint64_t level = 1; count > 1; ++level) {
         hipLaunchKernelGGL(diff_kernel, dim3(grid_for(count)), dim3(kBlock), 0, s, m, static_cast<const uint32_t*>(b.q),
@@ -480,12 +452,12 @@ int run_sort(fqd_engine* e, const fqd_tags* t1, const fqd_tags* t2, uint32_t* pe
         const uint32_t npos = uint32_t(std::min<uint64_t>(P, T - pos0));
         hipLaunchKernelGGL(encode_kernel, dim3(grid_for(next, kBlock, 2048)), dim3(kBlock), 0, s, m, M1, static_cast<const uint32_t*>(b.nq),
                            uint64_t(next), uint32_t(pos0), npos, w, d_rank, b.keys[0], b.vals[0], b.word);
-        SEQ_TRY(e, hipGetLastError());
+        FQD_TRY(e, hipGetLastError());
         cur = 0;
         if ((rc = fqd_internal_radix_sort(e, s, b.keys, b.vals, b.counts, b.tot, next, npos * w, &cur))) return rc;
         uint32_t max_rid = 0;                            // runs ascend along the list: the last one is the largest
-        SEQ_TRY(e, hipMemcpyAsync(&max_rid, b.nrid + (next - 1), sizeof max_rid, hipMemcpyDeviceToHost, s));
-        SEQ_TRY(e, hipStreamSynchronize(s));
+        FQD_TRY(e, hipMemcpyAsync(&max_rid, b.nrid + (next - 1), sizeof max_rid, hipMemcpyDeviceToHost, s));
+        FQD_TRY(e, hipStreamSynchronize(s));
         if (bits_for(max_rid)) {
             hipLaunchKernelGGL(gather_rid_kernel, dim3(grid_for(next)), dim3(kBlock), 0, s, static_cast<const uint32_t*>(b.vals[cur]),
                                static_cast<const uint32_t*>(b.nrid), uint64_t(next), b.keys[cur]);
@@ -494,10 +466,10 @@ int run_sort(fqd_engine* e, const fqd_tags* t1, const fqd_tags* t2, uint32_t* pe
         hipLaunchKernelGGL(relist_kernel, dim3(grid_for(next)), dim3(kBlock), 0, s, static_cast<const uint32_t*>(b.vals[cur]),
                            static_cast<const uint32_t*>(b.nq), static_cast<const uint32_t*>(b.npos), static_cast<const uint32_t*>(b.nrid),
                            static_cast<const uint64_t*>(b.word), uint64_t(next), b.q, b.pos, b.bnd, perm);
-        SEQ_TRY(e, hipGetLastError());
+        FQD_TRY(e, hipGetLastError());
         count = next;
     }
-    SEQ_TRY(e, hipStreamSynchronize(s));                // the scratch may be reused by the next call
+    FQD_TRY(e, hipStreamSynchronize(s));                // the scratch may be reused by the next call
     return FQD_OK;
 }
 
@@ -524,7 +496,7 @@ int fqd_seq_heads(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, c
     if (n_heads) *n_heads = 0;
     const uint64_t n = mate1->n;
     if (n == 0) return FQD_OK;
-    SEQ_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     hipStream_t s = fqd_internal_stream(e);
     const Mates m{mate1->bytes, mate1->offsets, mate1->lengths, mate2 ? mate2->bytes : nullptr, mate2 ? mate2->offsets : nullptr,
                   mate2 ? mate2->lengths : nullptr};
@@ -540,12 +512,12 @@ int fqd_seq_heads(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, c
         hipLaunchKernelGGL(hamming_walk_kernel, dim3(grid_for(n, 64u)), dim3(kBlock), 0, s, m, perm, n, distance,
                            static_cast<const uint8_t*>(cut), head);
     }
-    SEQ_TRY(e, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
+    FQD_TRY(e, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(count_kernel, dim3(grid_for(n, kBlock, 1024)), dim3(kBlock), 0, s, static_cast<const uint8_t*>(head), n, d_total);
-    SEQ_TRY(e, hipGetLastError());
+    FQD_TRY(e, hipGetLastError());
     unsigned long long got = 0;
-    SEQ_TRY(e, hipMemcpyAsync(&got, d_total, sizeof got, hipMemcpyDeviceToHost, s));
-    SEQ_TRY(e, hipStreamSynchronize(s));
+    FQD_TRY(e, hipMemcpyAsync(&got, d_total, sizeof got, hipMemcpyDeviceToHost, s));
+    FQD_TRY(e, hipStreamSynchronize(s));
     if (n_heads) *n_heads = got;
     return FQD_OK;
 }

@@ -39,12 +39,8 @@
 #include <vector>
 #include <unistd.h>
 
-#include "../../include/fqdupaway.h"
+#include "fqd_internal.hpp"
 #include "fqd_shard_plan.hpp"
-
-hipStream_t fqd_internal_stream(fqd_engine* e);
-int fqd_internal_device(fqd_engine* e);
-uint64_t* fqd_internal_state(fqd_engine* e);
 
 namespace {
 

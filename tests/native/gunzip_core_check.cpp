@@ -44,19 +44,6 @@ struct ArraySink {
     uint64_t count() const { return n; }
 };
 
-// The member's header (RFC 1952): where the deflate stream starts; 0: not a header this reader takes.
-static size_t deflate_start(const std::vector<uint8_t>& in, size_t n)
-{
-    if (n < 18 || in[0] != 31 || in[1] != 139 || in[2] != 8) return 0;
-    const uint8_t flg = in[3];
-    size_t at = 10;
-    if (flg & 4) { if (at + 2 > n) return 0; at += 2 + (in[at] | (size_t(in[at + 1]) << 8)); }
-    if (flg & 8) { while (at < n && in[at]) ++at; ++at; }
-    if (flg & 16) { while (at < n && in[at]) ++at; ++at; }
-    if (flg & 2) at += 2;
-    return at < n ? at : 0;
-}
-
 int main(int argc, char** argv)
 {
     if (argc < 4) return 2;
@@ -66,7 +53,7 @@ int main(int argc, char** argv)
     const uint64_t unit_bytes = std::strtoull(argv[3], nullptr, 10);
     const uint64_t ratio = argc > 4 ? std::strtoull(argv[4], nullptr, 10) : 16;
     std::FILE* out = std::fopen(argv[2], "wb");
-    const size_t ds = deflate_start(file, n);
+    const size_t header = gzip_header_len(file.data(), n), ds = header < n ? header : 0;    // where the deflate stream starts; 0: not a header this reader takes
     if (!ds || unit_bytes < 64) { std::printf("header 0 0 0\n"); std::fclose(out); return 0; }
     // the deflate stream and everything behind it (the trailer, further members) in a buffer of its own: aligned words, 16
     // readable bytes behind — and at an odd byte offset within the words, as it lies in a file
