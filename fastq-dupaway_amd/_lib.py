@@ -136,6 +136,7 @@ def load_library():
     L.fqd_bgzf_bound.argtypes = [u64]
     L.fqd_bgzf_bound.restype = u64
     L.fqd_bgzf_deflate.argtypes = [vp, vp, u64, u32, vp, u64, C.POINTER(u64)]
+    L.fqd_bgzf_deflate_ex.argtypes = [vp, vp, u64, u32, u32, vp, u64, C.POINTER(u64)]
     L.fqd_bgzf_inflate.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
     L.fqd_bgzf_inflate_async.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_gunzip.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), C.POINTER(C.c_int32)]

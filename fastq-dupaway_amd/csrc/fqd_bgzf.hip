@@ -8,12 +8,16 @@
 //                       CRC-32 by chunk and a pairwise combine, BGZF header and trailer
 //   bgzf_offsets_kernel running sum of the member sizes
 //   bgzf_compact_kernel slots -> members back to back
+// The count and emit kernels exist twice: kSearch = false is the fast mode (FQD_BGZF_FAST: two structural match
+// candidates, no table), kSearch = true the search mode (FQD_BGZF_SEARCH, fqd_bgzf_search_core.hpp): before the
+// chunks are parsed, search_member walks the member in rounds over a hash table in LDS and leaves every position's
+// best match in the workgroup's piece of the scratch.  That table takes the CU's LDS for one workgroup instead of two.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 
-#include "fqd_bgzf_core.hpp"
+#include "fqd_bgzf_search_core.hpp"
 #include "fqd_internal.hpp"
 
 namespace {
@@ -89,6 +93,29 @@ __device__ __forceinline__ bool index_lines(MemberLds& s, const Scan& sc, uint32
 }
 
 // -------------------------------------------------------------------------------------------
+struct DeviceMax {
+    __device__ uint32_t operator()(uint32_t* p, uint32_t v) const { return atomicMax(p, v); }
+};
+
+// The search of the member in LDS: kRounds rounds at most, two barriers each.  The inserts of a round commute (the
+// bucket keeps its largest positions), the lookups of a round only read: what lands in found[] does not depend on
+// the order in which the threads run.  found = kMember words of this workgroup's own in global memory.
+__device__ __forceinline__ void search_member(const Skewed& data, uint32_t L, uint32_t* table, uint32_t* __restrict__ found)
+{
+    for (uint32_t i = threadIdx.x; i < kBuckets * kWays; i += kThreads) table[i] = 0u;
+    __syncthreads();
+    for (uint32_t r = 0; r < kRounds; ++r) {
+        const uint32_t p = r * kThreads + threadIdx.x;
+        if (r * kThreads >= L) break;                   // the same for every thread
+        const uint32_t before = p < L ? search_lookup(data, table, p, L, 0u, 0u) : 0u;      // the table holds the rounds before this one
+        __syncthreads();                                // the inserts push entries out of the buckets
+        if (p < L) search_insert(data, table, p, L, DeviceMax{});
+        __syncthreads();
+        if (p < L) found[p] = search_lookup(data, table, p, L, r * kThreads, before);        // the matches inside the round
+    }
+    __syncthreads();                                    // found[] is read by the threads that own the chunks
+}
+
 struct TokenCounter {
     uint32_t* hist;                                     // LDS: kLitLen + kDist
     __device__ void literal(uint32_t b) { atomicAdd(&hist[b], 1u); }
@@ -99,11 +126,19 @@ struct TokenCounter {
     }
 };
 
+template <bool kSearch>
 __global__ __launch_bounds__(kThreads)
 void bgzf_count_kernel(const uint8_t* __restrict__ src, uint64_t n, uint64_t members, uint32_t lines_per_record,
-                       unsigned long long* __restrict__ hist_out)
+                       unsigned long long* __restrict__ hist_out, uint32_t* __restrict__ found_all, const Codes* __restrict__ codes)
 {
     __shared__ MemberLds s;
+    __shared__ uint32_t table[kSearch ? kBuckets * kWays : 1u];
+    __shared__ uint32_t lit[kSearch ? kLitLen : 1u], dst[kSearch ? kDist : 1u];     // the codes a match must beat (search mode)
+    if constexpr (kSearch) {
+        for (uint32_t i = threadIdx.x; i < kLitLen; i += kThreads) lit[i] = codes->lit[i];
+        for (uint32_t i = threadIdx.x; i < kDist; i += kThreads) dst[i] = codes->dist[i];
+    }
+    uint32_t* found = kSearch ? found_all + size_t(blockIdx.x) * kMember : nullptr;
     __shared__ uint32_t hist[kLitLen + kDist];
     for (uint32_t i = threadIdx.x; i < kLitLen + kDist; i += kThreads) hist[i] = 0;
     __syncthreads();
@@ -118,7 +153,12 @@ void bgzf_count_kernel(const uint8_t* __restrict__ src, uint64_t n, uint64_t mem
         const bool lines_on = index_lines(s, sc, lo);
         const Columns col = column_masks(data, lo, hi, s.ls, s.line_at[threadIdx.x], s.n_lines, L, lines_on, lines_per_record);
         TokenCounter sink{hist};
-        parse_chunk(data, lo, hi, sc, col, sink);
+        if constexpr (kSearch) {
+            search_member(data, L, table, found);
+            parse_chunk_search(data, lo, hi, sc, col, found + lo, WorthCodes{lit, dst}, sink);
+        } else {
+            parse_chunk(data, lo, hi, sc, col, sink);
+        }
         __syncthreads();                                // before the next member overwrites data
     }
     for (uint32_t i = threadIdx.x; i < kLitLen + kDist; i += kThreads)
@@ -126,11 +166,15 @@ void bgzf_count_kernel(const uint8_t* __restrict__ src, uint64_t n, uint64_t mem
 }
 
 // -------------------------------------------------------------------------------------------
+template <bool kSearch>
 __global__ __launch_bounds__(kThreads)
 void bgzf_emit_kernel(const uint8_t* __restrict__ src, uint64_t n, uint64_t members, uint32_t lines_per_record,
-                      const Codes* __restrict__ codes, uint8_t* __restrict__ slots, uint32_t* __restrict__ sizes)
+                      const Codes* __restrict__ codes, uint8_t* __restrict__ slots, uint32_t* __restrict__ sizes,
+                      uint32_t* __restrict__ found_all)
 {
     __shared__ MemberLds s;
+    __shared__ uint32_t table[kSearch ? kBuckets * kWays : 1u];
+    uint32_t* found = kSearch ? found_all + size_t(blockIdx.x) * kMember : nullptr;
     __shared__ uint32_t lit[kLitLen], dst[kDist];
     __shared__ uint32_t crc_table[256];
     __shared__ uint32_t crc[kThreads];
@@ -150,8 +194,14 @@ void bgzf_emit_kernel(const uint8_t* __restrict__ src, uint64_t n, uint64_t memb
         const bool lines_on = index_lines(s, sc, lo);
         const Columns col = column_masks(data, lo, hi, s.ls, s.line_at[t], s.n_lines, L, lines_on, lines_per_record);
 
+        const WorthCodes worth{lit, dst};
         BitCounter price{lit, dst};
-        parse_chunk(data, lo, hi, sc, col, price);
+        if constexpr (kSearch) {
+            search_member(data, L, table, found);
+            parse_chunk_search(data, lo, hi, sc, col, found + lo, worth, price);
+        } else {
+            parse_chunk(data, lo, hi, sc, col, price);
+        }
         uint32_t body_bits;
         const uint32_t before = block_scan(price.bits, s.wave_sums, body_bits);
         const uint32_t total_bits = header_bits + body_bits + (lit[256] >> 16);
@@ -168,7 +218,8 @@ void bgzf_emit_kernel(const uint8_t* __restrict__ src, uint64_t n, uint64_t memb
                     w.put(header_bits - at >= 32u ? codes->header[at >> 5] : codes->header[at >> 5] & ((1u << (header_bits - at)) - 1u),
                           header_bits - at >= 32u ? 32u : header_bits - at);
             Emitter<DeviceOr> emit{lit, dst, w};
-            parse_chunk(data, lo, hi, sc, col, emit);
+            if constexpr (kSearch) parse_chunk_search(data, lo, hi, sc, col, found + lo, worth, emit);
+            else parse_chunk(data, lo, hi, sc, col, emit);
             if (t == kThreads - 1u) w.put(lit[256] & 0xFFFFu, lit[256] >> 16);      // end of block
             w.finish();
         } else {
@@ -270,9 +321,19 @@ uint64_t fqd_bgzf_bound(uint64_t n)
 int fqd_bgzf_deflate(fqd_engine* e, const uint8_t* src, uint64_t n, uint32_t lines_per_record,
                      uint8_t* dst, uint64_t dst_capacity, uint64_t* out_bytes)
 {
+    return fqd_bgzf_deflate_ex(e, src, n, lines_per_record, FQD_BGZF_FAST, dst, dst_capacity, out_bytes);
+}
+
+int fqd_bgzf_deflate_ex(fqd_engine* e, const uint8_t* src, uint64_t n, uint32_t lines_per_record, uint32_t effort,
+                        uint8_t* dst, uint64_t dst_capacity, uint64_t* out_bytes)
+{
+    static_assert(FQD_BGZF_FAST == kEffortFast && FQD_BGZF_SEARCH == kEffortSearch, "the header and the core must agree");
     if (!e) return FQD_ERR_ARG;
     if (!out_bytes || (n && (!src || !dst)) || lines_per_record == 0 || lines_per_record > 64)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_bgzf_deflate: bad arguments");
+    if (effort != FQD_BGZF_FAST && effort != FQD_BGZF_SEARCH)
+        return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_bgzf_deflate_ex: effort is neither FQD_BGZF_FAST nor FQD_BGZF_SEARCH");
+    const bool search = effort == FQD_BGZF_SEARCH;
     *out_bytes = 0;
     if (n == 0) return FQD_OK;
     if (dst_capacity < fqd_bgzf_bound(n))
@@ -287,29 +348,47 @@ int fqd_bgzf_deflate(fqd_engine* e, const uint8_t* src, uint64_t n, uint32_t lin
     const size_t sizes_bytes = round_up(roomy * sizeof(uint32_t), 256);
     const size_t offs_bytes = round_up((roomy + 1) * sizeof(uint64_t), 256);
     const size_t slots_bytes = members * size_t(kSlot);
+    // the search mode holds one workgroup per CU (its table) and keeps kMember words of matches per workgroup
+    const uint32_t grid = uint32_t(std::min<uint64_t>(members, search ? 512 : 2048));
+    const size_t found_bytes = search ? size_t(512) * kMember * sizeof(uint32_t) : 0;
     void* base = nullptr;
-    const int rc = fqd_internal_scratch(e, 1, hist_bytes + codes_bytes + sizes_bytes + offs_bytes + roomy * size_t(kSlot), &base);
+    const int rc = fqd_internal_scratch(e, 1, hist_bytes + codes_bytes + sizes_bytes + offs_bytes + found_bytes + roomy * size_t(kSlot), &base);
     if (rc != FQD_OK) return rc;
     uint8_t* at = static_cast<uint8_t*>(base);
     unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(at); at += hist_bytes;
     Codes* d_codes = reinterpret_cast<Codes*>(at); at += codes_bytes;
     uint32_t* d_sizes = reinterpret_cast<uint32_t*>(at); at += sizes_bytes;
     uint64_t* d_offs = reinterpret_cast<uint64_t*>(at); at += offs_bytes;
+    uint32_t* d_found = reinterpret_cast<uint32_t*>(at); at += found_bytes;
     uint8_t* d_slots = at;
 
-    const uint32_t grid = uint32_t(std::min<uint64_t>(members, 2048));
     FQD_TRY(e, hipMemsetAsync(d_hist, 0, hist_bytes, stream));
     FQD_TRY(e, hipMemsetAsync(d_slots, 0, slots_bytes, stream));
-    hipLaunchKernelGGL(bgzf_count_kernel, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record, d_hist);
-    FQD_TRY(e, hipGetLastError());
+    // The search mode is counted as the fast mode parses it, then kSearchCounts times as it parses itself, each under
+    // the codes of the count before (fqd_bgzf_search_core.hpp, WorthCodes).
     uint64_t hist[kLitLen + kDist];
+    static thread_local Codes codes;
+    hipLaunchKernelGGL(bgzf_count_kernel<false>, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record, d_hist, d_found,
+                       static_cast<const Codes*>(d_codes));
+    FQD_TRY(e, hipGetLastError());
     FQD_TRY(e, hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, stream));
     FQD_TRY(e, hipStreamSynchronize(stream));
-    static thread_local Codes codes;
-    build_codes(hist, members, codes);
+    build_codes(hist, members, codes, search);
+    for (uint32_t pass = 0; search && pass < kSearchCounts; ++pass) {
+        FQD_TRY(e, hipMemcpyAsync(d_codes, &codes, sizeof codes, hipMemcpyHostToDevice, stream));
+        FQD_TRY(e, hipMemsetAsync(d_hist, 0, hist_bytes, stream));
+        hipLaunchKernelGGL(bgzf_count_kernel<true>, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record, d_hist, d_found,
+                           static_cast<const Codes*>(d_codes));
+        FQD_TRY(e, hipGetLastError());
+        FQD_TRY(e, hipMemcpyAsync(hist, d_hist, sizeof hist, hipMemcpyDeviceToHost, stream));
+        FQD_TRY(e, hipStreamSynchronize(stream));                  // also: `codes` is free to be rebuilt
+        build_codes(hist, members, codes, search);
+    }
     FQD_TRY(e, hipMemcpyAsync(d_codes, &codes, sizeof codes, hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(bgzf_emit_kernel, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record,
-                       static_cast<const Codes*>(d_codes), d_slots, d_sizes);
+    if (search) hipLaunchKernelGGL(bgzf_emit_kernel<true>, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record,
+                                   static_cast<const Codes*>(d_codes), d_slots, d_sizes, d_found);
+    else hipLaunchKernelGGL(bgzf_emit_kernel<false>, dim3(grid), dim3(kThreads), 0, stream, src, n, members, lines_per_record,
+                            static_cast<const Codes*>(d_codes), d_slots, d_sizes, d_found);
     FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(bgzf_offsets_kernel, dim3(1), dim3(1024), 0, stream, static_cast<const uint32_t*>(d_sizes), members, d_offs, d_offs + members);
     FQD_TRY(e, hipGetLastError());

@@ -394,11 +394,12 @@ inline void assign_codes(const uint8_t* len, uint32_t n, uint16_t* code)
 }
 
 // hist: kLitLen literal/length counts followed by kDist distance counts (end-of-block NOT included:
-// it is counted here, once per member).
-inline void build_codes(const uint64_t* hist, uint64_t members, Codes& c)
+// it is counted here, once per member).  every_symbol: the parse that will be emitted is not the one that was
+// counted (the search mode chooses its matches by the codes themselves), so no symbol may be left without a code.
+inline void build_codes(const uint64_t* hist, uint64_t members, Codes& c, bool every_symbol = false)
 {
     uint64_t lit[kLitLen], dst[kDist];
-    const uint64_t floor = sample_every(members) > 1u ? 1u : 0u;      // a sampled histogram must not leave a symbol without a code
+    const uint64_t floor = sample_every(members) > 1u || every_symbol ? 1u : 0u;      // a sampled histogram must not leave a symbol without a code
     for (uint32_t s = 0; s < kLitLen; ++s) lit[s] = hist[s] + floor;
     for (uint32_t s = 0; s < kDist; ++s) dst[s] = hist[kLitLen + s] + floor;
     lit[256] = members ? members : 1;

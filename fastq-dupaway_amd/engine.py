@@ -274,11 +274,16 @@ class Engine:
     def bgzf_bound(self, n: int) -> int:
         return int(self._L.fqd_bgzf_bound(n))
 
-    def bgzf_deflate(self, src, n: int, dst, lines_per_record: int = 4) -> int:
+    BGZF_EFFORT = {"fast": 0, "high": 1}                 # FQD_BGZF_FAST, FQD_BGZF_SEARCH
+
+    def bgzf_deflate(self, src, n: int, dst, lines_per_record: int = 4, effort="fast") -> int:
         """BGZF members for the n bytes at src (device) written to dst (device, >= bgzf_bound(n) bytes);
-        returns their total size.  The end-of-file marker is the caller's to append."""
+        returns their total size.  The end-of-file marker is the caller's to append.  effort: "fast" (no match
+        search, zlib 1-2 class) or "high" (LZ77 search over every member: smaller than zlib 3); a number is handed
+        to the library as it is, which refuses what it does not know."""
         total = C.c_uint64(0)
-        self._check(self._L.fqd_bgzf_deflate(self._h, self._p(src), n, lines_per_record, self._p(dst), dst.numel(), C.byref(total)))
+        level = self.BGZF_EFFORT[effort] if isinstance(effort, str) else int(effort)
+        self._check(self._L.fqd_bgzf_deflate_ex(self._h, self._p(src), n, lines_per_record, level, self._p(dst), dst.numel(), C.byref(total)))
         return int(total.value)
 
     def bgzf_inflate(self, comp, comp_off, comp_len, out_off, out_len, crc, n_members: int, text) -> int:

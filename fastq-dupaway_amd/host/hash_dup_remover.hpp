@@ -76,4 +76,8 @@ private:
     Summary             summary_;
 };
 
+// FQD_GZ_DEVICE_RATIO=fast|high -> FQD_BGZF_FAST / FQD_BGZF_SEARCH for the device deflate of `.gz` outputs; throws on any
+// other value (survivor_writer.cpp; main() asks before a run starts, the writer when it deflates).
+namespace detail { uint32_t device_deflate_effort(); }
+
 } // namespace fqdhost

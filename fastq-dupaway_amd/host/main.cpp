@@ -240,6 +240,7 @@ int main(int argc, char** argv)                                // main.cpp:181-2
         if (!(opts.mode & HASH) && opts.compare_seq.empty())
             throw std::runtime_error("no deduplication mode chosen: this build runs the --fast mode only unless "
                                      "--compare-seq tight|loose|tail-hamming is given");
+        fqdhost::detail::device_deflate_effort();                      // a misspelt FQD_GZ_DEVICE_RATIO ends the run before any output is opened
         fqdhost::Tuning tune;
         if (const char* d = std::getenv("FQD_DEVICE")) tune.device = std::atoi(d);
         tune.devices = fqdhost::devices_from_env();

@@ -58,6 +58,18 @@ bool deflate_on_device()
     return std::getenv("FQD_GZ_LEVEL") == nullptr;
 }
 
+// FQD_GZ_DEVICE_RATIO=fast|high: the effort of that device deflate.  fast (or unset) is the coder without a match search,
+// high the one with it (FQD_BGZF_SEARCH: smaller than zlib level 3, a few per cent above level 6, and still far from the
+// host codec's time).  Read here and nowhere else; main() asks once before any output is opened, so that a misspelt
+// value ends the run with nothing written.
+uint32_t device_deflate_effort()
+{
+    const char* v = std::getenv("FQD_GZ_DEVICE_RATIO");
+    if (!v || std::strcmp(v, "fast") == 0) return FQD_BGZF_FAST;
+    if (std::strcmp(v, "high") == 0) return FQD_BGZF_SEARCH;
+    throw std::runtime_error(std::string("FQD_GZ_DEVICE_RATIO must be fast or high, not '") + v + "'");
+}
+
 void plan_survivors(fqd_engine* e, int S, FileOnDevice* const* file, const uint32_t* const* idx, const uint8_t* keep, uint64_t upto,
                            const bool* gz_out, long long memlimit, SurvivorBuffers& b)
 {
@@ -96,6 +108,7 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
     }
     const uint64_t window = planned->window, roomy = planned->roomy;
     const uint32_t lines_per_record = format == Format::Fastq ? 4u : 2u;
+    const uint32_t effort = device_deflate_effort();
     struct Out {
         Device<uint64_t>& src_off; Device<uint64_t>& dst_off; Device<uint32_t>& len; uint64_t total;
         Pinned<char>* buf; Device<char>* d_win; Device<char>* d_members;
@@ -188,8 +201,8 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
                         Device<char>& d_members = o[s].d_members[*id];
                         const uint64_t cap = fqd_bgzf_bound(room);
                         d_members.reserve(cap);
-                        engine_ok(fqd_bgzf_deflate(e, reinterpret_cast<const uint8_t*>(d_win.p), bytes, lines_per_record,
-                                                   reinterpret_cast<uint8_t*>(d_members.p), cap, &out_bytes));
+                        engine_ok(fqd_bgzf_deflate_ex(e, reinterpret_cast<const uint8_t*>(d_win.p), bytes, lines_per_record, effort,
+                                                      reinterpret_cast<uint8_t*>(d_members.p), cap, &out_bytes));
                         from = d_members.p;
                         o[s].buf[*id].reserve(out_bytes + 64);           // (text that does not shrink to half)
                     }

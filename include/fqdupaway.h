@@ -411,6 +411,19 @@ uint64_t fqd_bgzf_bound(uint64_t n);
 int  fqd_bgzf_deflate(fqd_engine* e, const uint8_t* src, uint64_t n, uint32_t lines_per_record,
                       uint8_t* dst, uint64_t dst_capacity, uint64_t* out_bytes);
 
+/* The same with a choice of effort (added within ABI version 5: purely additive, nothing else changed).
+ *   FQD_BGZF_FAST    what fqd_bgzf_deflate writes, byte for byte (it forwards here).
+ *   FQD_BGZF_SEARCH  a real LZ77 search: a hash table of every member in LDS, 16 candidates a position anywhere
+ *                    earlier in the member (distance <= 32768), the two structural candidates of the fast mode beside
+ *                    them, one position of lazy look-ahead, a match taken only where the codes make it cheaper than its
+ *                    literals.  Same framing, same bound, same stored fallback; 3-6 % smaller than zlib level 3 on
+ *                    FASTQ text and 1-3 % above level 6 (member by member), at 3-4 GB/s instead of the fast mode's 140.
+ * Any other effort: FQD_ERR_ARG.  Both modes are deterministic: equal input, equal bytes. */
+#define FQD_BGZF_FAST   0u
+#define FQD_BGZF_SEARCH 1u
+int  fqd_bgzf_deflate_ex(fqd_engine* e, const uint8_t* src, uint64_t n, uint32_t lines_per_record, uint32_t effort,
+                         uint8_t* dst, uint64_t dst_capacity, uint64_t* out_bytes);
+
 /* BGZF input inflated in HBM: member m (m < n_members; all arrays device) is the raw deflate stream of comp_len[m]
  * bytes at comp + comp_off[m] and inflates to exactly out_len[m] (<= 65536) bytes at text + out_off[m] whose CRC-32
  * is crc[m] — what the host read off the member's header and trailer.  One wave per member.  *n_bad (host) =

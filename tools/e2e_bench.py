@@ -36,6 +36,16 @@ def write_fastq(path, n, L, rng, pool_idx, pool, tag):
             f.write(rec[:, : idw + 5 + 2 * L].tobytes())
 
 
+def zlib_member_by_member(job):
+    import zlib
+    text, level = job
+    total = 0
+    for at in range(0, len(text), 65280):
+        c = zlib.compressobj(level, zlib.DEFLATED, -15)
+        total += len(c.compress(text[at:at + 65280]) + c.flush()) + 26
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=5_000_000)
@@ -44,6 +54,8 @@ def main():
     ap.add_argument("--gz", action="store_true", help="gzip-compress inputs (with the CLI itself: BGZF) and outputs")
     ap.add_argument("--dir", default="/tmp")
     ap.add_argument("--oracle-reads", type=int, default=2_000_000)
+    ap.add_argument("--against-zlib", type=int, default=0, metavar="LEVEL", help="--gz: also print what zlib at LEVEL makes of the first output's text "
+                    "member by member (65280-byte pieces, raw deflate + 26 bytes of framing each: what bgzip writes)")
     ap.add_argument("--host-threads", default="", help="comma list: also time the CLI under FQD_HOST_THREADS=<each>")
     a = ap.parse_args()
     from fastq_dupaway_amd import _lib
@@ -87,6 +99,16 @@ def main():
             t0 = time.perf_counter(); r = subprocess.run(args, capture_output=True, text=True, env=env); dt = time.perf_counter() - t0
             print(f"cli run {rep} (host threads {threads or 'default'}): rc={r.returncode} {dt:.2f} s  {n / dt / 1e6:.2f} Mreads/s  "
                   f"{size / dt / 1e9:.2f} GB/s  | {r.stdout.strip()} {r.stderr.strip()[:2000]}")
+            print("output bytes:", [o.stat().st_size if o.exists() else None for o in outs], flush=True)
+    if a.gz and a.against_zlib and outs[0].exists():
+        import gzip
+        from concurrent.futures import ProcessPoolExecutor
+        text = gzip.open(outs[0], "rb").read()
+        pieces = [(text[at:at + 64 * 65280], a.against_zlib) for at in range(0, len(text), 64 * 65280)]
+        with ProcessPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+            total = sum(pool.map(zlib_member_by_member, pieces))
+        print(f"zlib level {a.against_zlib} member by member on the {len(text)} bytes of {outs[0].name}: {total + 28} bytes "
+              f"(the file: {outs[0].stat().st_size}, {100 * (outs[0].stat().st_size / (total + 28) - 1):+.2f} %)", flush=True)
     oracle = binding.load_oracle()
     files = plain_files
     m = n if a.unordered else min(a.oracle_reads, n)         # a prefix of shuffled files would not pair up

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times fqd_bgzf_deflate / fqd_bgzf_inflate / fqd_scan_records on FASTQ text built on the device.
-  python tools/inflate_probe.py [--records 1900000] [--reps 3]"""
+  python tools/inflate_probe.py [--records 1900000] [--reps 3] [--quality mixed|flat|binned] [--ratio high]"""
 import argparse
 import struct
 import sys
@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--host-packed", action="store_true", help="also inflate the same text packed by the host codec (libdeflate / zlib level 1: many more matches)")
     ap.add_argument("--quality", choices=["mixed", "flat", "binned"], default="mixed", help="flat: every quality 'I' (long runs, as the configs[4] generator writes); "
                     "binned: nine in ten 'F', the rest ':', ',' or '#' (what current sequencers write)")
+    ap.add_argument("--ratio", choices=["fast", "high"], default="fast", help="the effort of the device deflate: high = the LZ77 search (FQD_BGZF_SEARCH); "
+                    "its size and time are printed next to the fast mode's")
     ap.add_argument("--gz-level", default="1", help="--host-packed: the level the host codec packs at (FQD_GZ_LEVEL; 6 is what bgzip uses)")
     a = ap.parse_args()
     import torch
@@ -59,9 +61,10 @@ def main():
     with Engine(segments=1, device=0) as e:
         dst = torch.empty(e.bgzf_bound(nbytes), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize()
-        for _ in range(a.reps):
-            t0 = time.perf_counter(); size = e.bgzf_deflate(src, nbytes, dst, 4); dt = time.perf_counter() - t0
-            print(f"deflate {nbytes / 1e6:.0f} MB -> {size / 1e6:.0f} MB: {dt * 1e3:.1f} ms = {nbytes / dt / 1e9:.1f} GB/s", flush=True)
+        for effort in (["fast", "high"] if a.ratio == "high" else ["fast"]):      # the last one's members are inflated below
+            for _ in range(a.reps):
+                t0 = time.perf_counter(); size = e.bgzf_deflate(src, nbytes, dst, 4, effort=effort); dt = time.perf_counter() - t0
+                print(f"deflate ({effort}) {nbytes / 1e6:.0f} MB -> {size / 1e6:.1f} MB: {dt * 1e3:.1f} ms = {nbytes / dt / 1e9:.1f} GB/s", flush=True)
         raw = dst[:size].cpu().numpy().tobytes()
         arrs, total = walk(raw)
         t = lambda v: torch.from_numpy(v.view(np.int64) if v.dtype == np.uint64 else v.view(np.int32)).to(dev)
