@@ -39,6 +39,16 @@ class TagsDesc(C.Structure):
     _fields_ = [("bytes", C.c_void_p), ("offsets", C.c_void_p), ("lengths", C.c_void_p), ("n", C.c_uint64)]
 
 
+class SeqBlockInfo(C.Structure):                             # fqd_seq_block_info
+    _fields_ = [("longest", C.c_uint32 * 2), ("bad_byte", C.c_int32), ("reserved", C.c_uint32), ("record_bytes", C.c_uint64),
+                ("first_with", C.c_uint64 * 10)]
+
+
+class SeqRange(C.Structure):                                 # fqd_seq_range
+    _fields_ = [("key_lo", C.c_uint64), ("key_hi", C.c_uint64), ("pairs", C.c_uint64), ("bytes", C.c_uint64),
+                ("bytes_mate1", C.c_uint64)]
+
+
 class JoinDesc(C.Structure):
     _fields_ = [("perm_a", C.c_void_p), ("perm_b", C.c_void_p), ("match_a", C.c_void_p), ("match_b", C.c_void_p),
                 ("pair_a", C.c_void_p), ("pair_b", C.c_void_p), ("n_pairs", C.POINTER(C.c_uint64))]
@@ -125,6 +135,8 @@ def load_library():
     L.fqd_sort_tags.argtypes = [vp, C.POINTER(TagsDesc), vp]
     L.fqd_sort_seqs.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp]
     L.fqd_seq_heads.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp, i32, u32, vp, C.POINTER(u64)]
+    L.fqd_seq_prefix_keys.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp, vp, i32, vp, vp, C.POINTER(SeqBlockInfo)]
+    L.fqd_seq_plan_ranges.argtypes = [vp, vp, vp, vp, u64, u64, vp, C.POINTER(SeqRange), u32, C.POINTER(u32)]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

@@ -20,6 +20,9 @@
 //   4. heads    head[k] = sorted record k is written (fqd_seq_core.hpp has the rules and their proofs): tight and loose
 //               compare k with k-1; tail-hamming cuts the order at certain heads and one wave walks each segment,
 //               64 records per step, jumping to the first record beyond the distance (a ballot).
+//
+// Inputs larger than HBM go through it in RANGES of the sort order (fqd_seq_range_core.hpp): fqd_seq_prefix_keys and
+// fqd_seq_plan_ranges at the end of this file.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +31,7 @@
 
 #include "fqd_internal.hpp"
 #include "fqd_seq_core.hpp"
+#include "fqd_seq_range_core.hpp"
 
 namespace {
 
@@ -398,8 +402,7 @@ int run_sort(fqd_engine* e, const fqd_tags* t1, const fqd_tags* t2, uint32_t* pe
     for (uint32_t c = 0; c < uint32_t('\n'); ++c)
         if ((info[c >> 5] >> (c & 31u)) & 1u) {
             char msg[200];
-            std::snprintf(msg, sizeof msg, "a sequence line holds the byte %u (NUL or a control byte below '\\n'), which the "
-                                           "sequence-based modes of this build do not support", c);
+            std::snprintf(msg, sizeof msg, FQD_SEQ_LOW_BYTE_FORMAT, c);
             return fqd_internal_fail(e, FQD_ERR_ARG, msg);
         }
 
@@ -519,6 +522,300 @@ int fqd_seq_heads(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, c
     FQD_TRY(e, hipMemcpyAsync(&got, d_total, sizeof got, hipMemcpyDeviceToHost, s));
     FQD_TRY(e, hipStreamSynchronize(s));
     if (n_heads) *n_heads = got;
+    return FQD_OK;
+}
+
+} // extern "C"
+
+// =====================================================================================================================
+// The ranged run: prefix keys of an uploaded block, and the exact plan of the ranges (fqd_seq_range_core.hpp).
+namespace {
+
+constexpr uint32_t kKeyLanes = 8;                        // lanes per record: 8 x 8 bytes = one 64-byte line per step
+
+// slots of the block info on the device (unsigned long long each)
+enum : uint32_t { kInfoLongest1 = 0, kInfoLongest2 = 1, kInfoBytes = 2, kInfoFirstWith = 3, kInfoSlots = 13 };
+
+// Every byte of one sequence, eight lanes to a record, 8 bytes a lane and step (the lanes of a record read one 64-byte
+// line, the eight records of a wave's step lie next to each other in the block); sub 0 takes the tail.
+__device__ __forceinline__ void check_sequence(const uint8_t* p, uint32_t len, uint32_t sub, uint64_t record, unsigned long long* info)
+{
+    for (uint32_t k = sub * 8u; k + 8u <= len; k += kKeyLanes * 8u) {
+        uint64_t x;
+        __builtin_memcpy(&x, p + k, 8);
+        if (fqdseq::word_has_byte_below_newline(x))
+            for (uint32_t j = 0; j < 8u; ++j) { const uint32_t c = uint32_t(x >> (8u * j)) & 255u; if (c < uint32_t('\n')) atomicMin(&info[kInfoFirstWith + c], (unsigned long long)record); }
+    }
+    if (sub == 0)
+        for (uint32_t k = len & ~7u; k < len; ++k) { const uint32_t c = p[k]; if (c < uint32_t('\n')) atomicMin(&info[kInfoFirstWith + c], (unsigned long long)record); }
+}
+
+__global__ __launch_bounds__(kBlock)
+void prefix_keys_kernel(Mates m, const uint32_t* __restrict__ size1, const uint32_t* __restrict__ size2, int accumulate, uint64_t n,
+                        uint64_t* __restrict__ key, uint32_t* __restrict__ bytes, unsigned long long* __restrict__ info)
+{
+    const uint32_t sub = threadIdx.x & (kKeyLanes - 1u);
+    const uint64_t group = (blockIdx.x * uint64_t(kBlock) + threadIdx.x) / kKeyLanes, groups = uint64_t(gridDim.x) * kBlock / kKeyLanes;
+    uint32_t mx1 = 0, mx2 = 0;
+    unsigned long long sum = 0;
+    for (uint64_t i = group; i < n; i += groups) {
+        const uint8_t* p1 = m.b1 + m.o1[i];
+        const uint32_t l1 = m.l1[i];
+        check_sequence(p1, l1, sub, i, info);
+        uint32_t l2 = 0;
+        if (m.b2) { l2 = m.l2[i]; check_sequence(m.b2 + m.o2[i], l2, sub, i, info); }
+        if (sub == 0) {
+            mx1 = max(mx1, l1); mx2 = max(mx2, l2);
+            if (key) {
+                uint64_t k;
+                if (l1 >= fqdseq::kKeyBytes) { __builtin_memcpy(&k, p1, 8); k = __builtin_bswap64(k); }
+                else k = fqdseq::prefix_key(p1, l1);
+                key[i] = k;
+            }
+            const uint64_t sz = uint64_t(size1 ? size1[i] : 0u) + (size2 ? size2[i] : 0u);
+            sum += sz;
+            if (bytes) { const uint64_t all = sz + (accumulate ? bytes[i] : 0u); bytes[i] = all > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(all); }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        mx1 = max(mx1, __shfl_down(mx1, d, 64)); mx2 = max(mx2, __shfl_down(mx2, d, 64)); sum += __shfl_down(sum, d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (mx1) atomicMax(&info[kInfoLongest1], (unsigned long long)mx1);
+        if (mx2) atomicMax(&info[kInfoLongest2], (unsigned long long)mx2);
+        if (sum) atomicAdd(&info[kInfoBytes], sum);
+    }
+}
+
+__global__ __launch_bounds__(kBlock)
+void fill_u64_kernel(unsigned long long* __restrict__ p, uint32_t n, unsigned long long v)
+{
+    if (threadIdx.x < n) p[threadIdx.x] = v;
+}
+
+// ---- the plan: exclusive scan of uint32 values in 64 bits (tile sums, one block over the tiles, every element) ------------
+__device__ __forceinline__ unsigned long long block_exclusive64(unsigned long long v, unsigned long long* ws, unsigned long long& total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
+    if (lane == 63u) ws[wave] = inc;
+    __syncthreads();
+    unsigned long long before = 0;
+    for (uint32_t k = 0; k < wave; ++k) before += ws[k];
+    total = ws[0] + ws[1] + ws[2] + ws[3];
+    __syncthreads();
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(kBlock)
+void bytes_tile_sum_kernel(const uint32_t* __restrict__ v, uint64_t n, unsigned long long* __restrict__ tile_sum)
+{
+    __shared__ unsigned long long ws[4];
+    const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
+    unsigned long long s = 0;
+    for (uint32_t e = 0; e < kScanPer; ++e) s += base + e < n ? v[base + e] : 0u;
+    unsigned long long total = 0;
+    (void)block_exclusive64(s, ws, total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+// One block: tile_sum[] becomes its exclusive scan, tile_sum[tiles] the total.
+__global__ __launch_bounds__(kBlock)
+void bytes_tile_scan_kernel(unsigned long long* __restrict__ tile_sum, uint64_t tiles)
+{
+    __shared__ unsigned long long ws[4];
+    unsigned long long carry = 0;
+    for (uint64_t c0 = 0; c0 < tiles; c0 += kBlock) {
+        const uint64_t i = c0 + threadIdx.x;
+        const unsigned long long v = i < tiles ? tile_sum[i] : 0ull;
+        unsigned long long total = 0;
+        const unsigned long long ex = block_exclusive64(v, ws, total);
+        if (i < tiles) tile_sum[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) tile_sum[tiles] = carry;
+}
+
+__global__ __launch_bounds__(kBlock)
+void bytes_tile_apply_kernel(const uint32_t* __restrict__ v, uint64_t n, const unsigned long long* __restrict__ tile_base,
+                             unsigned long long* __restrict__ prefix)
+{
+    __shared__ unsigned long long ws[4];
+    const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
+    unsigned long long s = 0;
+    for (uint32_t e = 0; e < kScanPer; ++e) s += base + e < n ? v[base + e] : 0u;
+    unsigned long long total = 0;
+    unsigned long long at = tile_base[blockIdx.x] + block_exclusive64(s, ws, total);
+    for (uint32_t e = 0; e < kScanPer; ++e)
+        if (base + e < n) { prefix[base + e] = at; at += v[base + e]; }
+}
+
+constexpr uint64_t kRow = 5;                              // uint64 words of a row of the table = fqd_seq_range
+
+// The cuts, one after the other (each is a few binary searches from the last one: fqdseq::next_cut); one lane.  Rows of
+// the table: key_lo, key_hi, pairs, bytes, bytes of mate 1 (summed later).  *n_ranges counts every range, written or not,
+// up to `give_up`: a walk that gets there ends (the plan is refused).
+__global__ void cut_ranges_kernel(const uint64_t* __restrict__ key, const unsigned long long* __restrict__ prefix,
+                                  const unsigned long long* __restrict__ total, uint64_t n, uint64_t target,
+                                  uint64_t* __restrict__ table, uint32_t max_ranges, uint32_t give_up, uint32_t* __restrict__ n_ranges)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const unsigned long long all = *total;
+    auto key_at = [&](uint64_t i) { return key[i]; };
+    auto prefix_at = [&](uint64_t i) -> uint64_t { return i < n ? prefix[i] : all; };
+    uint64_t start = 0;
+    uint32_t r = 0;
+    while (start < n && r <= give_up) {
+        const uint64_t e = fqdseq::next_cut(start, n, target, key_at, prefix_at);
+        if (r < max_ranges) {
+            table[kRow * r + 0] = key[start]; table[kRow * r + 1] = key[e - 1];
+            table[kRow * r + 2] = e - start;  table[kRow * r + 3] = prefix_at(e) - prefix_at(start);
+            table[kRow * r + 4] = 0;
+        }
+        ++r;
+        start = e;
+    }
+    *n_ranges = r;
+}
+
+// The range of every pair, in input order: a range is a set of whole key values, so the pair's own key says it.  The same
+// pass sums mate 1's bytes per range (row word 4): in LDS first when the ranges fit there, one add a range and block after.
+constexpr uint32_t kLdsRanges = 2048;
+
+__global__ __launch_bounds__(kBlock)
+void range_of_kernel(const uint64_t* __restrict__ key, const uint32_t* __restrict__ bytes_mate1, uint64_t n, uint64_t* __restrict__ table,
+                     uint32_t n_ranges, uint32_t* __restrict__ range_of)
+{
+    __shared__ unsigned long long acc[kLdsRanges];
+    const bool in_lds = bytes_mate1 && n_ranges <= kLdsRanges;
+    if (in_lds) { for (uint32_t r = threadIdx.x; r < n_ranges; r += kBlock) acc[r] = 0; __syncthreads(); }
+    auto hi = [&](uint32_t r) { return table[kRow * r + 1]; };
+    for (uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kBlock) {
+        const uint32_t r = fqdseq::range_of_key(key[i], n_ranges, hi);
+        range_of[i] = r;
+        if (bytes_mate1 && r < n_ranges) {
+            if (in_lds) atomicAdd(&acc[r], (unsigned long long)bytes_mate1[i]);
+            else atomicAdd(reinterpret_cast<unsigned long long*>(&table[kRow * r + 4]), (unsigned long long)bytes_mate1[i]);
+        }
+    }
+    if (in_lds) {
+        __syncthreads();
+        for (uint32_t r = threadIdx.x; r < n_ranges; r += kBlock)
+            if (acc[r]) atomicAdd(reinterpret_cast<unsigned long long*>(&table[kRow * r + 4]), acc[r]);
+    }
+}
+
+struct PlanBuffers {
+    uint64_t* keys[2]; uint32_t* vals[2]; uint32_t *counts, *tot;
+    unsigned long long* tiles; uint64_t* table; uint32_t* n_ranges;
+};
+
+void carve_plan(uint64_t n, uint32_t max_ranges, PlanBuffers& b, char* base, size_t* bytes)
+{
+    Carver c{base};
+    const size_t tiles = (n + kScanTile - 1) / kScanTile + 2;
+    b.keys[0] = c.take<uint64_t>(n); b.keys[1] = c.take<uint64_t>(n);
+    b.vals[0] = c.take<uint32_t>(n); b.vals[1] = c.take<uint32_t>(n);
+    b.counts = c.take<uint32_t>(fqd_internal_radix_counts(n)); b.tot = c.take<uint32_t>(256);
+    b.tiles = c.take<unsigned long long>(tiles);
+    b.table = c.take<uint64_t>(kRow * std::max<uint32_t>(max_ranges, 1u));
+    b.n_ranges = c.take<uint32_t>(64);
+    *bytes = c.used + 256;
+}
+
+} // namespace
+
+extern "C" {
+
+int fqd_seq_prefix_keys(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, const uint32_t* size1, const uint32_t* size2,
+                        int accumulate, uint64_t* key, uint32_t* bytes, fqd_seq_block_info* info)
+{
+    if (!e) return FQD_ERR_ARG;
+    if (!mate1 || !info || bad_tags(mate1, mate1->n) || (mate2 && bad_tags(mate2, mate1->n)))
+        return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_seq_prefix_keys: bad arguments (mates of equal count)");
+    *info = fqd_seq_block_info{};
+    info->bad_byte = -1;
+    for (uint64_t& f : info->first_with) f = ~0ull;
+    const uint64_t n = mate1->n;
+    if (n == 0) return FQD_OK;
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    hipStream_t s = fqd_internal_stream(e);
+    void* small = nullptr;
+    int rc = fqd_internal_scratch(e, 1, 4096, &small);
+    if (rc) return rc;
+    unsigned long long* d_info = static_cast<unsigned long long*>(small);
+    FQD_TRY(e, hipMemsetAsync(d_info, 0, kInfoFirstWith * sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(fill_u64_kernel, dim3(1), dim3(kBlock), 0, s, d_info + kInfoFirstWith, 10u, ~0ull);
+    const Mates m{mate1->bytes, mate1->offsets, mate1->lengths, mate2 ? mate2->bytes : nullptr, mate2 ? mate2->offsets : nullptr,
+                  mate2 ? mate2->lengths : nullptr};
+    hipLaunchKernelGGL(prefix_keys_kernel, dim3(grid_for(n * kKeyLanes, kBlock, 4096)), dim3(kBlock), 0, s, m, size1, size2, accumulate, n,
+                       key, bytes, d_info);
+    FQD_TRY(e, hipGetLastError());
+    unsigned long long got[kInfoSlots] = {};
+    FQD_TRY(e, hipMemcpyAsync(got, d_info, sizeof got, hipMemcpyDeviceToHost, s));
+    FQD_TRY(e, hipStreamSynchronize(s));
+    info->longest[0] = uint32_t(got[kInfoLongest1]); info->longest[1] = uint32_t(got[kInfoLongest2]);
+    info->record_bytes = got[kInfoBytes];
+    for (uint32_t c = 0; c < 10u; ++c) {
+        info->first_with[c] = got[kInfoFirstWith + c];
+        if (info->bad_byte < 0 && got[kInfoFirstWith + c] != ~0ull) info->bad_byte = int32_t(c);
+    }
+    return FQD_OK;
+}
+
+int fqd_seq_plan_ranges(fqd_engine* e, const uint64_t* key, const uint32_t* bytes, const uint32_t* bytes_mate1, uint64_t n,
+                        uint64_t target_bytes, uint32_t* range_of, fqd_seq_range* table, uint32_t max_ranges, uint32_t* n_ranges)
+{
+    if (!e) return FQD_ERR_ARG;
+    if (!n_ranges || (max_ranges && !table) || (n && (!key || !bytes || !range_of)) || n >= 0x100000000ull)
+        return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_seq_plan_ranges: bad arguments (at most 2^32-1 pairs)");
+    *n_ranges = 0;
+    if (n == 0) return FQD_OK;
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    hipStream_t s = fqd_internal_stream(e);
+    PlanBuffers b{};
+    size_t need = 0;
+    carve_plan(n, max_ranges, b, nullptr, &need);
+    void* base = nullptr;
+    int rc = fqd_internal_scratch(e, 0, need, &base);
+    if (rc) return rc;
+    carve_plan(n, max_ranges, b, static_cast<char*>(base), &need);
+    FQD_TRY(e, hipMemcpyAsync(b.keys[0], key, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    FQD_TRY(e, hipMemcpyAsync(b.vals[0], bytes, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    int cur = 0;
+    if ((rc = fqd_internal_radix_sort(e, s, b.keys, b.vals, b.counts, b.tot, n, 64u, &cur))) return rc;
+    // the bytes before every sorted place, in 64 bits, into the key buffer the sort has left over
+    const uint64_t tiles = (n + kScanTile - 1) / kScanTile;
+    unsigned long long* prefix = reinterpret_cast<unsigned long long*>(b.keys[cur ^ 1]);
+    hipLaunchKernelGGL(bytes_tile_sum_kernel, dim3(uint32_t(tiles)), dim3(kBlock), 0, s, static_cast<const uint32_t*>(b.vals[cur]), n, b.tiles);
+    hipLaunchKernelGGL(bytes_tile_scan_kernel, dim3(1), dim3(kBlock), 0, s, b.tiles, tiles);
+    hipLaunchKernelGGL(bytes_tile_apply_kernel, dim3(uint32_t(tiles)), dim3(kBlock), 0, s, static_cast<const uint32_t*>(b.vals[cur]), n,
+                       static_cast<const unsigned long long*>(b.tiles), prefix);
+    hipLaunchKernelGGL(cut_ranges_kernel, dim3(1), dim3(64), 0, s, static_cast<const uint64_t*>(b.keys[cur]),
+                       static_cast<const unsigned long long*>(prefix), static_cast<const unsigned long long*>(b.tiles + tiles), n, target_bytes,
+                       b.table, max_ranges, FQD_SEQ_MAX_RANGES, b.n_ranges);
+    FQD_TRY(e, hipGetLastError());
+    uint32_t R = 0;
+    FQD_TRY(e, hipMemcpyAsync(&R, b.n_ranges, sizeof R, hipMemcpyDeviceToHost, s));
+    FQD_TRY(e, hipStreamSynchronize(s));
+    if (R > FQD_SEQ_MAX_RANGES) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "fqd_seq_plan_ranges: a target of %llu bytes cuts the input into more than %u ranges",
+                      (unsigned long long)target_bytes, FQD_SEQ_MAX_RANGES);
+        return fqd_internal_fail(e, FQD_ERR_ARG, msg);
+    }
+    *n_ranges = R;
+    const uint32_t rows = std::min(R, max_ranges);
+    static_assert(sizeof(fqd_seq_range) == kRow * sizeof(uint64_t), "a row of the table is kRow uint64");
+    if (R <= max_ranges) {
+        hipLaunchKernelGGL(range_of_kernel, dim3(grid_for(n, kBlock, 1024)), dim3(kBlock), 0, s, key, bytes_mate1, n, b.table, R, range_of);
+        FQD_TRY(e, hipGetLastError());
+    }
+    if (rows) FQD_TRY(e, hipMemcpyAsync(table, b.table, size_t(rows) * sizeof(fqd_seq_range), hipMemcpyDeviceToHost, s));
+    FQD_TRY(e, hipStreamSynchronize(s));
     return FQD_OK;
 }
 

@@ -253,6 +253,29 @@ class Engine:
                                           self._p(head), C.byref(heads)))
         return int(heads.value)
 
+    def seq_prefix_keys(self, mate1, key=None, mate2=None, size1=None, size2=None, bytes_=None, accumulate: bool = False):
+        """The ranged run's pass over an uploaded block: key[i] (uint64) = the first 8 sequence bytes of mate 1, big-endian,
+        padded with '\\n'; bytes_[i] = size1[i] + size2[i].  Returns the block's fqd_seq_block_info (_lib.SeqBlockInfo)."""
+        t1 = self._tags(*mate1)
+        t2 = self._tags(*mate2) if mate2 is not None else None
+        info = _lib.SeqBlockInfo()
+        self._check(self._L.fqd_seq_prefix_keys(self._h, C.byref(t1), C.byref(t2) if t2 is not None else None, self._p(size1), self._p(size2),
+                                                int(accumulate), self._p(key), self._p(bytes_), C.byref(info)))
+        return info
+
+    def seq_plan_ranges(self, key, bytes_, n: int, target_bytes: int, range_of, max_ranges: int = 4096, bytes_mate1=None):
+        """The exact plan of the ranges; returns (number of ranges, rows (key_lo, key_hi, pairs, bytes) of the first max_ranges),
+        and with bytes_mate1 a third value: mate 1's bytes of every such row."""
+        table = (_lib.SeqRange * max(max_ranges, 1))()
+        R = C.c_uint32(0)
+        self._check(self._L.fqd_seq_plan_ranges(self._h, self._p(key), self._p(bytes_), self._p(bytes_mate1), n, target_bytes, self._p(range_of),
+                                                table, max_ranges, C.byref(R)))
+        got = table[:min(R.value, max_ranges)]
+        rows = [(t.key_lo, t.key_hi, t.pairs, t.bytes) for t in got]
+        if bytes_mate1 is None:
+            return int(R.value), rows
+        return int(R.value), rows, [t.bytes_mate1 for t in got]
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

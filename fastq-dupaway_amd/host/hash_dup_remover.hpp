@@ -78,6 +78,6 @@ private:
 
 // FQD_GZ_DEVICE_RATIO=fast|high -> FQD_BGZF_FAST / FQD_BGZF_SEARCH for the device deflate of `.gz` outputs; throws on any
 // other value (survivor_writer.cpp; main() asks before a run starts, the writer when it deflates).
-namespace detail { uint32_t device_deflate_effort(); }
+namespace detail { uint32_t device_deflate_effort(); uint64_t seq_range_target_bytes(); }
 
 } // namespace fqdhost

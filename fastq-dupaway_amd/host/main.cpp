@@ -251,6 +251,7 @@ int main(int argc, char** argv)                                // main.cpp:181-2
         fqdhost::TemporaryDirectory tempdir;                   // main.cpp:192 (created lazily here)
         const fqdhost::Format fmt = (opts.mode & FASTA) ? fqdhost::Format::Fasta : fqdhost::Format::Fastq;
         if (!(opts.mode & HASH)) {                             // main.cpp:194-216
+            fqdhost::detail::seq_range_target_bytes();         // an FQD_SEQ_RANGE_KB that is no positive integer ends the run before any GPU call
             const fqdhost::CompareSeq cmp = opts.compare_seq == "tight" ? fqdhost::CompareSeq::Tight
                                           : opts.compare_seq == "loose" ? fqdhost::CompareSeq::Loose : fqdhost::CompareSeq::Hamming;
             fqdhost::SeqDupRemover remover(fmt, opts.memLimit, cmp, opts.hammdist, opts.write_clusters, opts.verbose, tune);

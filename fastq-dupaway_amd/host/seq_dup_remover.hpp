@@ -3,11 +3,15 @@
 // filterPE(in1, in2, out1, out2), with the record type as a runtime Format and the comparator as a mode.
 // The inputs go to HBM whole (the resident front end of the `--fast` runs: plain, BGZF and ordinary `.gz` inflated on
 // the device), are sorted and compared there (fqd_sort_seqs, fqd_seq_heads), and the records that are written leave
-// in sorted order through the same writer.  Limits: one GPU, fewer than 2^31 records (pairs), the text and the working
-// set in HBM (`-m` does not bound device memory), no sequence byte below '\n'.
+// in sorted order through the same writer.  Inputs that do not fit go through HBM in ranges of the sort order (run_ranged;
+// FQD_SEQ_RANGE_KB forces it).  Limits: one GPU, no sequence byte below '\n'; per range fewer than 2^31 records (pairs)
+// and the text and the working set in HBM (`-m` does not bound device memory); a ranged run reads regular files only.
 #pragma once
+#include <cstdint>
 #include <string>
 #include <sys/types.h>
+
+#include <hip/hip_runtime_api.h>
 
 #include "hash_dup_remover.hpp"
 
@@ -26,6 +30,8 @@ public:
     const Summary& summary() const { return summary_; }
 private:
     void run(int n_files, const std::string* in, const std::string* out);
+    bool run_in_core(int n_files, const std::string* in, const std::string* out, int device, hipStream_t stream);
+    void run_ranged(int n_files, const std::string* in, const std::string* out, int device, hipStream_t stream, uint64_t target_bytes);
     Format     format_;
     ssize_t    memlimit_;
     CompareSeq mode_;

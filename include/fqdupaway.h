@@ -499,6 +499,49 @@ int  fqd_sort_seqs(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, 
 int  fqd_seq_heads(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, const uint32_t* perm, int mode, uint32_t distance,
                    uint8_t* head, uint64_t* n_heads);
 
+/* ---- `--compare-seq` on inputs larger than HBM: the sort order cut into ranges (added within ABI version 5: purely
+ * additive).  The text goes through HBM one range of the sort order at a time; a range is chosen by the PREFIX KEY of
+ * mate 1: its first 8 sequence bytes as a big-endian uint64, a sequence shorter than 8 padded with '\n'.  No accepted
+ * byte is below '\n', so the key is monotone (non-strict) in the order of fqd_sort_seqs and equal sequences have equal
+ * keys (rules and proofs: csrc/fqd_seq_range_core.hpp).
+ *
+ * fqd_seq_prefix_keys: for the n records of an uploaded block (mate1; the spans fqd_sort_seqs takes) key[i] (device, may
+ * be NULL: check only).  Every sequence byte of the block is looked at, mate2's (may be NULL) as well: info->first_with[c]
+ * (c < '\n') = the first record of the block that holds byte c in either mate, or ~0; info->bad_byte = the lowest such c,
+ * or -1 — what the census of fqd_sort_seqs refuses, in its order.  info->longest[m] = the longest sequence of mate m.
+ * size1 / size2 (device, may be NULL) are the records' sizes: bytes[i] (device, may be NULL) = size1[i] + size2[i]
+ * (saturated at 2^32-1), added to what bytes[i] holds when `accumulate` is set (the mates of a pair arrive in blocks of
+ * their own); info->record_bytes = their sum over the block.  Returns after the stream has drained. */
+typedef struct fqd_seq_block_info {
+    uint32_t longest[2];
+    int32_t  bad_byte;
+    uint32_t reserved;
+    uint64_t record_bytes;
+    uint64_t first_with[10];
+} fqd_seq_block_info;
+int  fqd_seq_prefix_keys(fqd_engine* e, const fqd_tags* mate1, const fqd_tags* mate2, const uint32_t* size1, const uint32_t* size2,
+                         int accumulate, uint64_t* key, uint32_t* bytes, fqd_seq_block_info* info);
+
+/* fqd_seq_plan_ranges: the EXACT plan from every pair's key and bytes (device, n < 2^32 pairs; every position is 64 bits
+ * wide).  Ranges are cut only where the key changes; each is the longest run of whole key values whose bytes stay within
+ * target_bytes; one key value that alone exceeds it is a range of its own.  range_of[i] (device, n uint32) = the range of
+ * pair i, in input order.  table (HOST, max_ranges rows) = the ranges in key order; *n_ranges (host) = how many there are —
+ * when that is more than max_ranges only the first max_ranges rows were written and range_of is not to be used: call again
+ * with a larger table.  bytes_mate1 (device, may be NULL) = the part of bytes[i] that is mate 1's record: a row's
+ * bytes_mate1 is its sum over the range (what the first file's store has to hold; the second's is bytes - bytes_mate1).
+ * A plan of more than FQD_SEQ_MAX_RANGES ranges is refused with FQD_ERR_ARG as soon as the walk gets there (the inputs
+ * are read once per range: such a target is a mistake, and the walk from cut to cut is one lane's work).  A copy of
+ * (key, bytes) is sorted by the radix passes of the tag sort, the bytes are scanned in 64 bits, the cuts are found by
+ * binary search from cut to cut; 24 bytes of scratch per pair during the call. */
+#define FQD_SEQ_MAX_RANGES 65536u
+typedef struct fqd_seq_range {
+    uint64_t key_lo, key_hi;    /* the smallest and the largest key of the range */
+    uint64_t pairs, bytes;
+    uint64_t bytes_mate1;
+} fqd_seq_range;
+int  fqd_seq_plan_ranges(fqd_engine* e, const uint64_t* key, const uint32_t* bytes, const uint32_t* bytes_mate1, uint64_t n,
+                         uint64_t target_bytes, uint32_t* range_of, fqd_seq_range* table, uint32_t max_ranges, uint32_t* n_ranges);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
