@@ -170,7 +170,9 @@ void gz_decode_planes_kernel(const uint8_t* __restrict__ deflate, uint64_t avail
         const uint64_t byte0 = ui.start_bit >> 3;
         const uint64_t left = avail_bytes - byte0;
         const uint32_t comp_len = uint32_t(left < (1ull << 28) ? left : (1ull << 28));
-        const uint64_t rel = ui.stop_bit == ~0ull ? 0xFFFFFFFFull : ui.stop_bit - byte0 * 8u;
+        // (a unit that is decoded again from where the one before it ended may start BEHIND its own stop — a long stretch of stored blocks
+        //  with a wrong guess in it: it ends at the next boundary, not, the difference wrapped around, with the member)
+        const uint64_t rel = ui.stop_bit == ~0ull ? 0xFFFFFFFFull : ui.stop_bit > byte0 * 8u ? ui.stop_bit - byte0 * 8u : 0ull;
         // ONE decode, two texts: the codes are read once, every literal is stored and every match copied in both planes (round 4's
         // first version decoded the unit once per plane: 210 of the 360 ms of a 9.5 GB file)
         const uint32_t st = fqd::winf::inflate_stretch(ctx, sh, deflate + byte0, comp_len, uint32_t(ui.start_bit & 7u), uint32_t(rel < 0xFFFFFFFFull ? rel : 0xFFFFFFFFull),

@@ -34,7 +34,8 @@ constexpr uint32_t kInflateWavesPerCu = 16;            // 10 KB of LDS each; fou
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void bgzf_inflate_kernel(const uint8_t* __restrict__ comp, const uint64_t* __restrict__ comp_off, const uint32_t* __restrict__ comp_len,
                          const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ out_len, uint64_t members,
-                         uint8_t* __restrict__ text, fqd::winf::Token* __restrict__ tokens, unsigned long long* __restrict__ n_bad)
+                         uint8_t* __restrict__ text, fqd::winf::Token* __restrict__ tokens, unsigned long long* __restrict__ n_bad,
+                         uint8_t* __restrict__ member_bad /* [members]: 1 where the stream itself is bad, for the CRC check to leave alone */)
 {
     __shared__ fqd::winf::Shared<kWave> sh;
     WaveCtx ctx{threadIdx.x};
@@ -45,9 +46,10 @@ void bgzf_inflate_kernel(const uint8_t* __restrict__ comp, const uint64_t* __res
     uint32_t bad = 0;
     for (uint64_t m = blockIdx.x; m < members; m += gridDim.x) {
         const uint32_t len = out_len[m];
-        if (len > 65536u) { ++bad; continue; }                // no BGZF member holds more (the CLI's header walk says so too; an ABI caller may not)
+        if (len > 65536u) { ++bad; if (threadIdx.x == 0) member_bad[m] = 1; continue; }    // no BGZF member holds more (the CLI's header walk says so too; an ABI caller may not)
         const uint32_t st = fqd::winf::inflate_member(ctx, sh, comp + comp_off[m], comp_len[m], text + out_off[m], len, tok);
         bad += st != fqd::winf::kOk ? 1u : 0u;
+        if (threadIdx.x == 0) member_bad[m] = st != fqd::winf::kOk ? 1 : 0;
     }
     if (threadIdx.x == 0 && bad) atomicAdd(n_bad, static_cast<unsigned long long>(bad));
 #ifdef FQD_STAMPS
@@ -84,7 +86,8 @@ __device__ const CrcTables g_crc_tables = make_crc_tables();
 
 __global__ __launch_bounds__(fqd::bgzf::kThreads)
 void bgzf_check_crc_kernel(const uint8_t* __restrict__ text, const uint64_t* __restrict__ out_off, const uint32_t* __restrict__ out_len,
-                           const uint32_t* __restrict__ want, uint64_t members, unsigned long long* __restrict__ n_bad)
+                           const uint32_t* __restrict__ want, uint64_t members, unsigned long long* __restrict__ n_bad,
+                           const uint8_t* __restrict__ member_bad)
 {
     using namespace fqd::bgzf;
     __shared__ alignas(16) uint8_t data[kThreads * kChunk + 16];
@@ -96,7 +99,7 @@ void bgzf_check_crc_kernel(const uint8_t* __restrict__ text, const uint64_t* __r
     __syncthreads();
     for (uint64_t m = blockIdx.x; m < members; m += gridDim.x) {
         const uint32_t L = out_len[m];
-        if (L > 65536u) continue;                             // counted as bad by the inflater; more would not fit `data`
+        if (L > 65536u || member_bad[m]) continue;            // counted as bad by the inflater (a member is counted once); more would not fit `data`
         const uint8_t* __restrict__ p = text + out_off[m];
         // aligned 16-byte loads from the first aligned address on; the ragged head byte by byte
         const uint32_t head = uint32_t((16u - (reinterpret_cast<uintptr_t>(p) & 15u)) & 15u);
@@ -300,15 +303,16 @@ int fqd_bgzf_inflate_async(fqd_engine* e, const uint8_t* comp, const uint64_t* c
     const uint32_t grid = uint32_t(std::min<uint64_t>(n_members, 256u * kInflateWavesPerCu));
     const size_t lens_bytes = round_up(sizeof(fqd::winf::Token) * fqd::winf::kTokenRoom * grid, 256);
     void* base = nullptr;
-    const int rc = fqd_internal_scratch(e, 1, 256 + lens_bytes, &base);     // batches of one stream share it: they run one after the other
+    const int rc = fqd_internal_scratch(e, 1, 256 + lens_bytes + round_up(n_members, 256), &base);     // batches of one stream share it: they run one after the other
     if (rc != FQD_OK) return rc;
     fqd::winf::Token* d_tokens = reinterpret_cast<fqd::winf::Token*>(static_cast<uint8_t*>(base) + 256);
+    uint8_t* d_member_bad = static_cast<uint8_t*>(base) + 256 + lens_bytes;
     unsigned long long* d_bad = reinterpret_cast<unsigned long long*>(bad_counters);
     hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid), dim3(kWave), 0, stream, comp, comp_off, comp_len, out_off, out_len, n_members,
-                       text, d_tokens, d_bad);
+                       text, d_tokens, d_bad, d_member_bad);
     FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(bgzf_check_crc_kernel, dim3(uint32_t(std::min<uint64_t>(n_members, 2048))), dim3(fqd::bgzf::kThreads), 0, stream,
-                       static_cast<const uint8_t*>(text), out_off, out_len, crc, n_members, d_bad + 1);
+                       static_cast<const uint8_t*>(text), out_off, out_len, crc, n_members, d_bad + 1, d_member_bad);
     FQD_TRY(e, hipGetLastError());
     return FQD_OK;
 }
@@ -327,16 +331,17 @@ int fqd_bgzf_inflate(fqd_engine* e, const uint8_t* comp, const uint64_t* comp_of
     const uint32_t grid = uint32_t(std::min<uint64_t>(n_members, 256u * kInflateWavesPerCu));
     const size_t lens_bytes = round_up(sizeof(fqd::winf::Token) * fqd::winf::kTokenRoom * grid, 256);
     void* base = nullptr;
-    const int rc = fqd_internal_scratch(e, 1, 256 + lens_bytes, &base);
+    const int rc = fqd_internal_scratch(e, 1, 256 + lens_bytes + round_up(n_members, 256), &base);
     if (rc != FQD_OK) return rc;
     unsigned long long* d_bad = static_cast<unsigned long long*>(base);
     fqd::winf::Token* d_tokens = reinterpret_cast<fqd::winf::Token*>(static_cast<uint8_t*>(base) + 256);
+    uint8_t* d_member_bad = static_cast<uint8_t*>(base) + 256 + lens_bytes;
     FQD_TRY(e, hipMemsetAsync(d_bad, 0, 256, stream));
     hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid), dim3(kWave), 0, stream, comp, comp_off, comp_len, out_off, out_len, n_members,
-                       text, d_tokens, d_bad);
+                       text, d_tokens, d_bad, d_member_bad);
     FQD_TRY(e, hipGetLastError());
     hipLaunchKernelGGL(bgzf_check_crc_kernel, dim3(uint32_t(std::min<uint64_t>(n_members, 2048))), dim3(fqd::bgzf::kThreads), 0, stream,
-                       static_cast<const uint8_t*>(text), out_off, out_len, crc, n_members, d_bad + 1);
+                       static_cast<const uint8_t*>(text), out_off, out_len, crc, n_members, d_bad + 1, d_member_bad);
     FQD_TRY(e, hipGetLastError());
     unsigned long long bad[2] = {0, 0};
     FQD_TRY(e, hipMemcpyAsync(bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, stream));

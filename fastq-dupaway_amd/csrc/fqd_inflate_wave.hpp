@@ -206,7 +206,8 @@ FQD_HD uint32_t canonical(const S& sh, uint32_t which, uint32_t w, uint32_t& len
 
 // Tables of one code from the lengths lens[0..n) (0 = unused symbol): sorted[], lim[], base[] and the first-level
 // table `lut` of 2^bits entries.  false for an over-subscribed set; an incomplete one passes only where zlib lets
-// it pass here: a distance code with no code at all or a single one-bit code.
+// it pass (may_be_single: the literal/length and the distance code, not the code-length code): no code at all, or a
+// single one-bit code, whose unused bit stays no code in lut and in canonical().
 template <class Ctx, class S>
 FQD_HD bool build_code(Ctx& ctx, S& sh, uint32_t which, uint32_t n, const uint8_t* lens, uint16_t* lut, uint32_t bits, bool may_be_single)
 {
@@ -666,7 +667,7 @@ FQD_HD uint32_t inflate_impl(Ctx& ctx, S& sh, const uint8_t* comp, uint32_t comp
             bitpos = ctx.same(sh.same[6]);
             // (the distance lengths move out of the way first: building the literal code reads lens[0..nlen) only, but
             //  the distance code is built into tables the code-length code no longer needs)
-            if (!build_code(ctx, sh, 0, nlen, sh.lens, sh.single, kLitBits, false)) return kBadLengths;
+            if (!build_code(ctx, sh, 0, nlen, sh.lens, sh.single, kLitBits, true)) return kBadLengths;     // (true: the lone one-bit code, which can only be the end-of-block symbol's)
             pack_literals(ctx, sh);
             if (!build_code(ctx, sh, 1, ndist, sh.lens + nlen, sh.dist_lut, kDistBits, true)) return kBadLengths;
         }

@@ -646,6 +646,29 @@ def test_ordinary_gzip_inputs_inflated_on_the_device(exe, oracle, tmp_path, case
         assert rc != 0
 
 
+@pytest.mark.gpu
+def test_bgzf_input_of_handmade_members_stays_on_the_device(exe, oracle, tmp_path):
+    """A `.gz` whose members are deflate streams written by hand (tests/handmade_deflate_cases.py: a literal/length alphabet of
+    one code, empty blocks by the hundred, no run-length coding, stored / dynamic / fixed in turn — what libdeflate, zopfli and
+    sequencers' converters may write and zlib's deflater never does) around real FASTQ records: inflated on the device, not
+    handed to the host reader as a file with bad members, and the oracle's bytes and line."""
+    import handmade_deflate_cases as handmade
+    rnd = random.Random(97)
+    seqs = random_reads(rnd, 4000, 900, 40, 100)
+    text = fastq([(b"M01:7:FC:1:%d:%d 1:N:0" % (1100 + k % 7, 1000 + k), s) for k, s in enumerate(seqs)])
+    src, plain = tmp_path / "in.fq.gz", tmp_path / "in.fq"
+    src.write_bytes(handmade.fastq_in_handmade_members(text))
+    assert gzip.open(src, "rb").read() == text
+    plain.write_bytes(text)
+    exp, got = tmp_path / "exp.fq", tmp_path / "got.fq"
+    tot, dup = oracle.filter_single(plain, exp, FASTQ)
+    r = run(exe, "-i", src, "-o", got, "--fast", "-v", env={"FQD_HOST_TIMING": "1"}, cwd=tmp_path)
+    assert r.returncode == 0, r.stderr
+    assert "ordered/resident: survivors out of HBM" in r.stderr, r.stderr
+    assert got.read_bytes() == exp.read_bytes()
+    assert r.stdout == f"{tot} reads processed, out of which {dup} duplicates were removed.\n" and dup > 1000
+
+
 # ---------------------------------------------------------------- GPU: several engines in one run (FQD_DEVICES)
 
 def uniform_fastq(rnd, n, L, pool, ident):

@@ -192,3 +192,66 @@ def test_large_member_is_fast_enough_to_matter(eng):
     dt = time.perf_counter() - t0
     assert ok and len(got) == len(data) and crc == zlib.crc32(data) & 0xFFFFFFFF
     print(f"\n[gunzip] {len(data) / 1e6:.0f} MB of text from {len(raw) / 1e6:.0f} MB in {dt * 1e3:.0f} ms (upload and read-back included)")
+
+
+# ---- streams written by hand (tests/handmade_deflate_cases.py) as ordinary gzip members; zlib's inflater is the specification
+
+import handmade_deflate_cases as handmade
+
+
+@pytest.mark.parametrize("name,data,raw", handmade.gzip_valid(), ids=[c[0] for c in handmade.gzip_valid()])
+def test_handmade_streams_inflate_as_zlib_does(eng, monkeypatch, name, data, raw):
+    """Units of 1 KiB, the smallest there are: a few hundred KB span hundreds of guessed starts, and a stored block that LOOKS like
+    block starts plants wrong ones the chain has to throw out.  (Room for 64 bytes of text per packed byte: chains of matches pack
+    more than the eightfold that FASTQ needs.)"""
+    monkeypatch.setenv("FQD_GUNZIP_UNIT_KB", "1")
+    monkeypatch.setenv("FQD_GUNZIP_RATIO", "64")
+    ok, got, deflate_bytes, crc, h = device_gunzip(eng, raw, len(data) + 100, misalign=len(name) % 8)
+    assert ok and got == data
+    assert h + deflate_bytes + 8 == len(raw) and crc == zlib.crc32(data) & 0xFFFFFFFF
+
+
+@pytest.mark.parametrize("name,raw", handmade.gzip_invalid(), ids=[c[0] for c in handmade.gzip_invalid()])
+def test_handmade_streams_zlib_refuses_fail_the_call(eng, monkeypatch, name, raw):
+    """Error paths, none of them a fault: each ran clean through the same decoders on the CPU under the sanitizers
+    (tests/test_gunzip_core.py)."""
+    monkeypatch.setenv("FQD_GUNZIP_UNIT_KB", "1")
+    monkeypatch.setenv("FQD_GUNZIP_RATIO", "64")
+    ok, _, _, _, _ = device_gunzip(eng, raw, 100_000)
+    assert not ok
+
+
+def test_handmade_planted_block_starts_while_the_file_arrives(eng, monkeypatch):
+    """fqd_gunzip_arriving on the stream whose stored blocks hold what looks like block starts: wrong guesses thrown out while
+    pieces are still on their way."""
+    import ctypes
+    import threading
+    import torch
+    monkeypatch.setenv("FQD_GUNZIP_UNIT_KB", "1")
+    monkeypatch.setenv("FQD_GUNZIP_RATIO", "64")
+    name, data, raw = next(c for c in handmade.gzip_valid() if c[0] == "stored_payload_that_looks_like_block_starts")
+    h = header_len(raw)
+    dev = torch.device("cuda", 0)
+    n = len(raw) - h
+    real = torch.frombuffer(bytearray(raw[h:] + b"\0" * 32), dtype=torch.uint8).to(dev)
+    buf = torch.randint(0, 256, (n + 32,), dtype=torch.uint8, device=dev)              # garbage where nothing has arrived
+    text = torch.full((len(data) + 64,), 0xEE, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    arrived = ctypes.c_uint64(0)
+    side = torch.cuda.Stream(device=dev)
+
+    def feed():
+        for at in range(0, n, 20_000):
+            hi = min(n, at + 20_000)
+            with torch.cuda.stream(side):
+                buf[at:hi + (32 if hi == n else 0)].copy_(real[at:hi + (32 if hi == n else 0)])
+            side.synchronize()
+            arrived.value = hi
+    t = threading.Thread(target=feed)
+    t.start()
+    ok, nb, deflate_bytes, crc = eng.gunzip(buf, n, text[: len(data)], arrived=arrived)
+    t.join()
+    eng.sync()
+    assert ok and nb == len(data) and text[:nb].cpu().numpy().tobytes() == data
+    assert h + deflate_bytes + 8 == len(raw) and crc == zlib.crc32(data) & 0xFFFFFFFF
+    assert bool((text[len(data):] == 0xEE).all())

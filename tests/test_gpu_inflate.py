@@ -178,3 +178,48 @@ def test_text_that_is_not_whole_records_is_reported(eng, damage):
     n = lines // 4
     out = [torch.empty(max(n, 1), dtype=d, device=dev) for d in (torch.int64, torch.int64, torch.int32, torch.int32, torch.int32)]
     assert not eng.scan_records(text, len(data), 4, n, *out)
+
+
+# ---- streams written by hand (tests/handmade_deflate_cases.py): shapes zlib's deflater never emits; zlib's inflater is the specification
+
+import handmade_deflate_cases as handmade
+
+
+@pytest.mark.parametrize("name,data,raw", handmade.bgzf_valid(), ids=[c[0] for c in handmade.bgzf_valid()])
+def test_handmade_members_inflate_as_zlib_does(eng, name, data, raw):
+    bad, got = device_inflate(eng, raw)
+    assert bad == 0 and got == data
+
+
+def test_all_handmade_members_in_one_launch(eng):
+    """Every table shape side by side: waves that build a one-code alphabet next to waves with fifteen-bit codes."""
+    data, raw = handmade.bgzf_all_valid_in_one_file()
+    bad, got = device_inflate(eng, raw)
+    assert bad == 0 and got == data
+
+
+@pytest.mark.parametrize("name,data,raw,planted", handmade.bgzf_invalid(), ids=[c[0] for c in handmade.bgzf_invalid()])
+def test_handmade_members_zlib_refuses_are_counted(eng, name, data, raw, planted):
+    """Error paths, none of them a fault: every one of these ran clean through the same decoder on the CPU under the address and
+    undefined-behaviour sanitizers (tests/test_inflate_core.py).  The bad member lies between two good ones, whose bytes are exact."""
+    co, cl, oo, ol, crc, total = walk(raw)
+    bad, got = device_inflate(eng, raw)
+    good_first, bad_len = int(ol[0]), int(ol[1])
+    assert bad == planted
+    assert got[:good_first] + got[good_first + bad_len:] == data
+
+
+def test_all_handmade_bad_members_in_one_launch(eng):
+    data, raw, planted = handmade.bgzf_all_invalid_in_one_file()
+    co, cl, oo, ol, crc, total = walk(raw)
+    bad, got = device_inflate(eng, raw)
+    assert bad == planted
+    good = b"".join(got[int(o):int(o) + int(n)] for k, (o, n) in enumerate(zip(oo, ol)) if k % 2 == 0)
+    assert good == data
+
+
+@pytest.mark.parametrize("seed", handmade.RANDOM_SEEDS)
+def test_handmade_random_codes_and_tokens_come_back(eng, seed):
+    for trial, (data, raw) in enumerate(handmade.random_cases(seed, handmade.RANDOM_TRIALS)):
+        bad, got = device_inflate(eng, raw)
+        assert bad == 0 and got == data, (seed, trial)

@@ -73,3 +73,27 @@ def test_damage_is_reported_or_harmless(tmp_path):
     # cut short
     verdict, _, got, _ = run(bytes(raw[: len(raw) // 2]), tmp_path, 65536)
     assert verdict in ("bad", "chain")
+
+
+# ---- streams written by hand (tests/handmade_deflate_cases.py) as ordinary gzip members; zlib's inflater is the specification
+
+import handmade_deflate_cases as handmade
+
+
+@pytest.mark.parametrize("how", ["planes", "serial"])
+@pytest.mark.parametrize("unit", [65536, 4096])
+@pytest.mark.parametrize("name,data,raw", handmade.gzip_valid(), ids=[c[0] for c in handmade.gzip_valid()])
+def test_handmade_streams_inflate_as_zlib_does(tmp_path, name, data, raw, unit, how):
+    verdict, units, got, deflate_bytes = run(raw, tmp_path, unit, 64, how)
+    assert verdict == "ok" and got == data
+    assert 10 + deflate_bytes + 8 == len(raw)
+    if name in handmade.GUESSING[:3] and unit == 4096:
+        assert units >= 4                                                  # decoded from several guessed starts
+
+
+@pytest.mark.parametrize("how", ["planes", "serial"])
+@pytest.mark.parametrize("unit", [65536, 4096])
+@pytest.mark.parametrize("name,raw", handmade.gzip_invalid(), ids=[c[0] for c in handmade.gzip_invalid()])
+def test_handmade_streams_zlib_refuses_are_refused(tmp_path, name, raw, unit, how):
+    verdict, units, got, deflate_bytes = run(raw, tmp_path, unit, 64, how)
+    assert verdict in ("bad", "chain", "header") and got == b""          # (header: a file that ends before a member's 18 bytes are there)

@@ -83,3 +83,34 @@ def test_whatever_zlib_writes_comes_back(tmp_path):
         for lanes in (64, 8):
             members, bad, got = run(raw, tmp_path, lanes)
             assert bad == 0 and got == data, (trial, lanes)
+
+
+# ---- streams written by hand (tests/handmade_deflate_cases.py): shapes zlib's deflater never emits; zlib's inflater is the specification
+
+import handmade_deflate_cases as handmade
+
+
+def test_the_token_room_the_cases_assume_is_the_decoders():
+    assert f"kTokenRoom = {handmade.TOKEN_ROOM};" in CORE.read_text()
+
+
+@pytest.mark.parametrize("lanes", [64, 8])
+@pytest.mark.parametrize("name,data,raw", handmade.bgzf_valid(), ids=[c[0] for c in handmade.bgzf_valid()])
+def test_handmade_members_inflate_as_zlib_does(tmp_path, name, data, raw, lanes):
+    members, bad, got = run(raw, tmp_path, lanes)
+    assert bad == 0 and got == data and members == 2
+
+
+@pytest.mark.parametrize("lanes", [64, 8])
+@pytest.mark.parametrize("name,data,raw,planted", handmade.bgzf_invalid(), ids=[c[0] for c in handmade.bgzf_invalid()])
+def test_handmade_members_zlib_refuses_are_reported(tmp_path, name, data, raw, planted, lanes):
+    """The bad member between two good ones: it is counted, they come out whole (and the harness ran under the sanitizers)."""
+    members, bad, got = run(raw, tmp_path, lanes)
+    assert bad == planted and got == data and members == 4
+
+
+@pytest.mark.parametrize("seed", handmade.RANDOM_SEEDS)
+def test_handmade_random_codes_and_tokens_come_back(tmp_path, seed):
+    for trial, (data, raw) in enumerate(handmade.random_cases(seed, handmade.RANDOM_TRIALS)):
+        members, bad, got = run(raw, tmp_path, (64, 8)[trial & 1])
+        assert bad == 0 and got == data, (seed, trial)
