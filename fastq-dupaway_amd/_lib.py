@@ -137,6 +137,8 @@ def load_library():
     L.fqd_seq_heads.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp, i32, u32, vp, C.POINTER(u64)]
     L.fqd_seq_prefix_keys.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp, vp, i32, vp, vp, C.POINTER(SeqBlockInfo)]
     L.fqd_seq_plan_ranges.argtypes = [vp, vp, vp, vp, u64, u64, vp, C.POINTER(SeqRange), u32, C.POINTER(u32)]
+    L.fqd_seq_scores.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp]
+    L.fqd_seq_pick_best.argtypes = [vp, vp, vp, u64, vp, C.POINTER(u64)]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

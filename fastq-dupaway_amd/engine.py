@@ -276,6 +276,20 @@ class Engine:
             return int(R.value), rows
         return int(R.value), rows, [t.bytes_mate1 for t in got]
 
+    def seq_scores(self, rec1, score, rec2=None):
+        """FQD_SEQ_KEEP=best: rec1 / rec2 = (bytes, offsets, lengths, n) of the WHOLE records (length with the final '\\n');
+        score[i] (n uint32, input order) = the sum of the quality bytes above '!' of record (pair) i, saturating."""
+        t1 = self._tags(*rec1)
+        t2 = self._tags(*rec2) if rec2 is not None else None
+        self._check(self._L.fqd_seq_scores(self._h, C.byref(t1), C.byref(t2) if t2 is not None else None, self._p(score)))
+
+    def seq_pick_best(self, score, head, n: int, perm) -> int:
+        """Per cluster of head (fqd_seq_heads) the member with the highest score, the earliest on a tie, takes the head's
+        place in perm (a swap); returns the number of clusters whose written member changed."""
+        moved = C.c_uint64(0)
+        self._check(self._L.fqd_seq_pick_best(self._h, self._p(score), self._p(head), n, self._p(perm), C.byref(moved)))
+        return int(moved.value)
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

@@ -9,6 +9,7 @@
 #include "seq_dup_remover.hpp"
 
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 
 #include "run_common.hpp"
@@ -35,6 +36,17 @@ uint64_t seq_range_target_bytes()
     if (!ok || kb == 0)
         throw std::runtime_error(std::string("FQD_SEQ_RANGE_KB must be a positive integer (KB of record text per range), not '") + v + "'");
     return kb << 10;
+}
+
+// FQD_SEQ_KEEP=first|best: which member of a cluster of duplicates `--compare-seq` writes.  first (and unset): the first in
+// the sort order, as the reference's scan does; best: the one with the best quality line (csrc/fqd_seq_pick_core.hpp).
+// Read here and nowhere else; SeqDupRemover::run asks before any GPU call.
+bool seq_keep_best()
+{
+    const char* v = std::getenv("FQD_SEQ_KEEP");
+    if (!v || std::strcmp(v, "first") == 0) return false;
+    if (std::strcmp(v, "best") == 0) return true;
+    throw std::runtime_error(std::string("FQD_SEQ_KEEP must be 'first' or 'best', not '") + v + "'");
 }
 
 } // namespace detail
@@ -131,6 +143,24 @@ void write_clusters(fqd_engine* e, hipStream_t stream, FileOnDevice& f, const ui
 }
 
 
+// FQD_SEQ_KEEP=best: per cluster of `head` the member with the best quality line takes the head's place in `perm`
+// (fqd_seq_scores over the whole records of the n pairs, fqd_seq_pick_best); everything after it reads perm as before.
+// Returns the number of clusters whose written member changed.
+uint64_t pick_best_members(fqd_engine* e, int S, FileOnDevice* const* files, uint64_t n, const uint8_t* head, uint32_t* perm)
+{
+    StageClock::Scope t("sequence: best-quality pick on the GPU");
+    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(e)); };
+    fqd_tags recs[2];
+    for (int s = 0; s < S; ++s)
+        recs[s] = fqd_tags{reinterpret_cast<const uint8_t*>(files[s]->text.p), files[s]->start.p, files[s]->size.p, n};
+    Device<uint32_t> score;
+    score.reserve(n);
+    uint64_t moved = 0;
+    engine_ok(fqd_seq_scores(e, &recs[0], S == 2 ? &recs[1] : nullptr, score.p));
+    engine_ok(fqd_seq_pick_best(e, score.p, head, n, perm, &moved));
+    return moved;
+}
+
 // ---- the ranged run ---------------------------------------------------------------------------------------------------
 
 // A block of the host reader in HBM: its text and, per record, the offsets (from the block's first record) and lengths.
@@ -185,10 +215,11 @@ uint64_t stream_blocks(const std::string& name, Format format, int device, size_
 // the text; per record and file the five arrays of its store (28 B) and the three of the
 // output plan (20 B); per pair the order (4 B), the head flags and the heads' scratch (2 B) and the scratch of
 // fqd_sort_seqs (64 B and a little); the windows of the writer; with --write-clusters the ID lines (at most the text)
-// and their plan (21 B a pair).
-uint64_t range_need(int S, uint64_t pairs, uint64_t bytes, bool clusters, uint64_t writer_bytes)
+// and their plan (21 B a pair); with FQD_SEQ_KEEP=best the scores (4 B a pair; the pick's own 4 B a pair lie in the scratch
+// the sort has left).
+uint64_t range_need(int S, uint64_t pairs, uint64_t bytes, bool clusters, bool best, uint64_t writer_bytes)
 {
-    const uint64_t per_pair = uint64_t(S) * (28u + 20u) + 4u + 2u + 65u + (clusters ? 21u : 0u);
+    const uint64_t per_pair = uint64_t(S) * (28u + 20u) + 4u + 2u + 65u + (clusters ? 21u : 0u) + (best ? 4u : 0u);
     return bytes + (clusters ? bytes / 2 : 0) + (pairs + 1) * per_pair + writer_bytes + (64ull << 20);
 }
 
@@ -253,6 +284,9 @@ void SeqDupRemover::filterPE(const std::string& infile1, const std::string& infi
 
 void SeqDupRemover::run(int S, const std::string* in, const std::string* out)
 {
+    keep_best_ = seq_keep_best();                                       // a misspelt FQD_SEQ_KEEP ends the run before any GPU call
+    if (keep_best_ && format_ == Format::Fasta)
+        throw std::runtime_error("FQD_SEQ_KEEP=best needs the quality lines of FASTQ records: --format fasta has none");
     for (int s = 0; s < S; ++s) InputFile probe(in[s], true);          // "Cannot open file X" before anything else
     if (tuning_.devices.size() > 1)
         throw std::runtime_error("--compare-seq runs on one GPU: FQD_DEVICES may name one device only");
@@ -315,6 +349,10 @@ bool SeqDupRemover::run_in_core(int S, const std::string* in, const std::string*
     }
     const uint64_t dups = n - heads;
     FileOnDevice* files[2] = {&dev[0], &dev[1]};
+    if (keep_best_) {
+        const uint64_t moved = pick_best_members(eng.e, S, files, n, head.p, perm.p);
+        if (StageClock::on()) std::cerr << "sequence: best-quality pick, " << moved << " of " << heads << " clusters changed\n";
+    }
     const uint32_t* idx[2] = {perm.p, perm.p};
     SurvivorBuffers buffers;
     {
@@ -356,6 +394,11 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
             throw std::runtime_error("--compare-seq: the input does not fit in GPU memory at once (or FQD_SEQ_RANGE_KB is set) and is then read "
                                      "once per range of the sort order, which a pipe cannot be: " + in[s] + " is not a regular file");
     }
+    // A loose or tail-hamming cluster can go on behind a cut (through the carried record), and the range in front of the
+    // cut is on disk by the time its later members are seen: the best member of such a cluster cannot take its place.
+    if (keep_best_ && mode_ != CompareSeq::Tight)
+        throw std::runtime_error("FQD_SEQ_KEEP=best with --compare-seq loose or tail-hamming needs the whole input in GPU memory at once; "
+                                 "this run goes through it in ranges of the sort order (FQD_SEQ_RANGE_KB is set, or the input does not fit)");
     const size_t block_bytes = std::max<size_t>(1u << 20, tuning_.block_bytes);
     BlockOnDevice blk;
     Device<uint32_t> range_of;
@@ -411,10 +454,10 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
             // is free once the plan's scratch (24 B a pair, released before pass B) and the range numbers (4 B) are there
             size_t free_b = 0, total_b = 0;
             HIP_OK(hipMemGetInfo(&free_b, &total_b));
-            const uint64_t fixed = range_need(S, 0, 0, write_clusters_, writer_bytes) + n * 4u;
+            const uint64_t fixed = range_need(S, 0, 0, write_clusters_, keep_best_, writer_bytes) + n * 4u;
             const uint64_t usable = free_b / 5 * 4;
             if (usable <= fixed) throw DeviceOutOfMemory("--compare-seq: too little GPU memory is free for the ranged run");
-            const double per_byte = double(range_need(S, n, record_bytes, write_clusters_, writer_bytes) - range_need(S, 0, 0, write_clusters_, writer_bytes)) /
+            const double per_byte = double(range_need(S, n, record_bytes, write_clusters_, keep_best_, writer_bytes) - range_need(S, 0, 0, write_clusters_, keep_best_, writer_bytes)) /
                                     double(std::max<uint64_t>(record_bytes, 1));
             target = std::max<uint64_t>(1u << 20, static_cast<uint64_t>(double(usable - fixed) / per_byte));
             // and few enough pairs a range for the sort (fewer than 2^31): 2^30 of the input's average pair
@@ -442,7 +485,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
             if (r.pairs + 1 >= 0x80000000ull)
                 throw std::runtime_error("--compare-seq: at most 2^31-2 records (pairs) per range; the sequences that start with '" +
                                          show_prefix(r.key_lo) + "' to '" + show_prefix(r.key_hi) + "' are " + std::to_string(r.pairs));
-            const uint64_t need = range_need(S, r.pairs, r.bytes, write_clusters_, writer_bytes);
+            const uint64_t need = range_need(S, r.pairs, r.bytes, write_clusters_, keep_best_, writer_bytes);
             if (need > free_b)
                 throw std::runtime_error("--compare-seq: the records whose sequence starts with '" + show_prefix(r.key_lo) +
                                          (r.key_hi != r.key_lo ? "' to '" + show_prefix(r.key_hi) : std::string()) + "' are " + std::to_string(r.bytes) +
@@ -465,7 +508,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
     std::unique_ptr<OutputFile> sink[2];
     OutputFile* sinks[2] = {nullptr, nullptr};
     const bool gz_out[2] = {has_gz_extension(out[0]), S == 2 && has_gz_extension(out[1])};
-    uint64_t total = 0, total_dups = 0;
+    uint64_t total = 0, total_dups = 0, moved_clusters = 0, all_clusters = 0;
     std::vector<uint8_t> tail;
 
     // The stores, the order and the flags for the LARGEST range, before any output exists: a later, larger range must not be
@@ -571,6 +614,10 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
         }
         const uint64_t dups = (m - phantom) - heads;
         FileOnDevice* files[2] = {&store[0], &store[1]};
+        if (keep_best_) {                                        // tight only: no phantom, and no cluster crosses a cut
+            moved_clusters += pick_best_members(eng.e, S, files, m, head.p, perm.p);
+            all_clusters += heads;
+        }
         const uint32_t* idx[2] = {perm.p, perm.p};
         plan_survivors(eng.e, S, files, idx, head.p, m, gz_out, memlimit_, buffers);
         if (r == 0) {                                            // outputs exist from here on
@@ -620,6 +667,8 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
     }
     for (int s = 0; s < S; ++s) sinks[s]->close();
     if (tuning_.leave_memory_to_exit) g_leave_memory_to_exit = true;
+    if (keep_best_ && StageClock::on())
+        std::cerr << "sequence: best-quality pick, " << moved_clusters << " of " << all_clusters << " clusters changed\n";
     StageClock::report();
     summary_.total = total; summary_.duplicates = total_dups; summary_.unmatched = 0;
     if (verbose_) {                                                      // seq_dup_remover.hpp:107-108,216-217

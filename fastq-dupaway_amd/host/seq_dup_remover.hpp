@@ -4,7 +4,8 @@
 // The inputs go to HBM whole (the resident front end of the `--fast` runs: plain, BGZF and ordinary `.gz` inflated on
 // the device), are sorted and compared there (fqd_sort_seqs, fqd_seq_heads), and the records that are written leave
 // in sorted order through the same writer.  Inputs that do not fit go through HBM in ranges of the sort order (run_ranged;
-// FQD_SEQ_RANGE_KB forces it).  Limits: one GPU, no sequence byte below '\n'; per range fewer than 2^31 records (pairs)
+// FQD_SEQ_RANGE_KB forces it).  FQD_SEQ_KEEP=best writes, of every cluster, the member with the best quality line instead of
+// the first in the sort order (fqd_seq_scores, fqd_seq_pick_best).  Limits: one GPU, no sequence byte below '\n'; per range fewer than 2^31 records (pairs)
 // and the text and the working set in HBM (`-m` does not bound device memory); a ranged run reads regular files only.
 #pragma once
 #include <cstdint>
@@ -37,6 +38,7 @@ private:
     CompareSeq mode_;
     unsigned   distance_;
     bool       write_clusters_, verbose_;
+    bool       keep_best_ = false;       // FQD_SEQ_KEEP=best (read by run(), before any GPU call)
     Tuning     tuning_;
     Summary    summary_;
 };

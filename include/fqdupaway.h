@@ -542,6 +542,26 @@ typedef struct fqd_seq_range {
 int  fqd_seq_plan_ranges(fqd_engine* e, const uint64_t* key, const uint32_t* bytes, const uint32_t* bytes_mate1, uint64_t n,
                          uint64_t target_bytes, uint32_t* range_of, fqd_seq_range* table, uint32_t max_ranges, uint32_t* n_ranges);
 
+/* ---- FQD_SEQ_KEEP=best: the member of a cluster that is written (added within ABI version 5: purely additive).  Which
+ * records form a cluster stays what fqd_seq_heads found; these two calls only choose the member that stands at the
+ * head's place in the order, and so the record that the output plan and the writers take (rules and proofs:
+ * csrc/fqd_seq_pick_core.hpp).
+ *
+ * fqd_seq_scores: score[i] (device, n uint32, input order) = the score of record (pair) i.  rec1 / rec2 (NULL: single-end)
+ * give the WHOLE records as spans: offset = the record's first byte, length = its size with the final '\n'.  A record's
+ * score is the sum of (b - 33) over the bytes b >= 33 of its last line without the '\n' (the quality line, Phred+33;
+ * bytes below 33, a '\r' among them, count 0; an empty line scores 0), saturating at 2^32-1; a pair's is the saturating
+ * sum of its mates'.  Reads every quality byte once.  Returns after the stream has drained.
+ *
+ * fqd_seq_pick_best: perm and head (device) are those of fqd_sort_seqs / fqd_seq_heads over n < 2^31 records; a cluster
+ * is a run of places that starts at a set head flag (place 0 starts one whatever its flag says).  Per cluster the member
+ * with the highest score, on equal scores the one earliest in the order, is the representative: perm[head place] and
+ * perm[representative's place] are swapped.  The head flags do not move and no other entry of perm changes, so a cluster
+ * of equal scores keeps its order.  *n_moved (host, may be NULL) = the clusters whose entry at the head's place changed.
+ * 4 bytes of scratch per record during the call.  Returns after the stream has drained. */
+int  fqd_seq_scores(fqd_engine* e, const fqd_tags* rec1, const fqd_tags* rec2, uint32_t* score);
+int  fqd_seq_pick_best(fqd_engine* e, const uint32_t* score, const uint8_t* head, uint64_t n, uint32_t* perm, uint64_t* n_moved);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);

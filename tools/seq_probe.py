@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Times the device half of the sequence-based modes on synthetic reads and checks it.
-  python tools/seq_probe.py <n_reads> <len> [se|pe] [reps]
+  python tools/seq_probe.py <n_reads> <len> [se|pe] [reps] [--keep best]
 Reads come from fqd_synth_reads (bench.py's duplicate model: 30 % copies of earlier reads), then 5 % get one
 substitution (near duplicates for tail-hamming) and 5 % are cut short (prefixes for loose).  Per mode it times keys +
 sort (fqd_sort_seqs), heads (fqd_seq_heads) and the output plan (fqd_output_plan); it times fqd_sort_tags on the same
 uncut spans against fqd_sort_seqs and checks that both permutations are identical; it checks the heads of a sorted
-prefix against the CPU restatement (tests/seq_reference.py).  Prints one JSON line."""
+prefix against the CPU restatement (tests/seq_reference.py).  With `--keep best` it also builds whole FASTQ records
+(a 20-byte ID line, the read, '+', a random quality line) around the reads of mate 1, times fqd_seq_scores and
+fqd_seq_pick_best alone (the pick on the heads of `tight`, on a fresh copy of the order each time) and checks both against
+numpy and the restatement (tests/seq_keep_reference.py) on a prefix.  Prints one JSON line."""
 import json
 import sys
 import time
@@ -34,7 +37,56 @@ def timed(fn, reps):
     return best, out
 
 
+def keep_best_leg(e, line, bases, n, L, perm, head, reps, dev):
+    """FQD_SEQ_KEEP=best: the two calls alone, on whole records of 2 L + 25 bytes around the reads."""
+    import seq_keep_reference as keep
+    R = 2 * L + 25
+    g = torch.Generator(device=dev); g.manual_seed(12)
+    rec = torch.empty((n, R), dtype=torch.uint8, device=dev)
+    rec[:, 0] = ord("@"); rec[:, 1:20] = ord("r"); rec[:, 20] = ord("\n")
+    rec[:, 21:21 + L] = bases[:n * L].view(n, L)
+    rec[:, 21 + L] = ord("\n"); rec[:, 22 + L] = ord("+"); rec[:, 23 + L] = ord("\n")
+    for lo in range(0, n, 1 << 24):                          # the quality lines, a piece at a time
+        hi = min(n, lo + (1 << 24))
+        rec[lo:hi, 24 + L:24 + 2 * L] = torch.randint(33, 75, (hi - lo, L), device=dev, generator=g, dtype=torch.uint8)
+    rec[:, 24 + 2 * L] = ord("\n")
+    text = torch.cat([rec.view(-1), torch.zeros(64, dtype=torch.uint8, device=dev)])
+    del rec
+    offs = torch.arange(n, dtype=torch.int64, device=dev) * R
+    sizes = torch.full((n,), R, dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.int32, device=dev)
+    ms, _ = timed(lambda: e.seq_scores((text, offs, sizes, n), score), reps)
+    line["keep_scores_ms"] = round(ms, 3)
+    line["keep_scores_quality_gb_per_s"] = round(n * L / ms / 1e6, 1)      # the quality bytes alone, over the call's time
+    order = torch.empty_like(perm)
+    best, moved = None, 0
+    for _ in range(reps):
+        order.copy_(perm)
+        ms, moved = timed(lambda: e.seq_pick_best(score, head, n, order), 1)
+        best = ms if best is None else min(best, ms)
+    line["keep_pick_ms"] = round(best, 3); line["keep_clusters_changed"] = moved
+    # a prefix: the scores by numpy, the pick of the whole clusters among the first places by the restatement
+    k = min(n, 4000)
+    qual = text[:k * R].view(k, R)[:, 24 + L:24 + 2 * L].cpu().numpy().astype(np.int64)
+    line["keep_scores_prefix_ok"] = bool(np.array_equal(score[:k].cpu().numpy().view(np.uint32), (qual - 33).sum(axis=1)))
+    h = head[:k + 1].cpu().numpy()
+    m = k if n == k else int(np.nonzero(h)[0][-1])            # the last head among them ends whole clusters
+    p0 = perm[:m].cpu().numpy().view(np.uint32).tolist()
+    sc = dict(zip(p0, score[perm[:m].long()].cpu().numpy().view(np.uint32).tolist()))
+    exp, _ = keep.pick(p0, h[:m].tolist(), sc)
+    line["keep_pick_prefix_ok"] = order[:m].cpu().numpy().view(np.uint32).tolist() == exp
+
+
 def main():
+    argv = list(sys.argv)
+    keep_best = False
+    if "--keep" in argv:
+        at = argv.index("--keep")
+        if argv[at + 1:at + 2] != ["best"]:
+            sys.exit("--keep takes 'best'")
+        keep_best = True
+        del argv[at:at + 2]
+    sys.argv = argv
     n, L = int(sys.argv[1]), int(sys.argv[2])
     paired = len(sys.argv) > 3 and sys.argv[3] == "pe"
     reps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
@@ -88,6 +140,9 @@ def main():
             line["sort_tags_uncut_ms"] = round(timed(lambda: e.sort_tags(b, o, l, n, perm_t), reps)[0], 3)
             line["perms_identical"] = bool(torch.equal(perm_s, perm_t))
             line["speedup_vs_sort_tags"] = round(line["sort_tags_uncut_ms"] / line["sort_seqs_uncut_ms"], 2)
+        if keep_best:
+            e.seq_heads(mates[0], perm, SEQ_TIGHT, 2, head, m2)
+            keep_best_leg(e, line, mates[0][0], n, L, perm, head, reps, dev)
     line["when"] = time.strftime("%Y-%m-%d %H:%M:%S")
     print(json.dumps(line), flush=True)
 
