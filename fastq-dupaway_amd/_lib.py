@@ -139,6 +139,10 @@ def load_library():
     L.fqd_seq_plan_ranges.argtypes = [vp, vp, vp, vp, u64, u64, vp, C.POINTER(SeqRange), u32, C.POINTER(u32)]
     L.fqd_seq_scores.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), vp]
     L.fqd_seq_pick_best.argtypes = [vp, vp, vp, u64, vp, C.POINTER(u64)]
+    L.fqd_submit_linked.argtypes = [vp, C.POINTER(ReadsDesc), u64, i32, vp, vp, i32]
+    L.fqd_owners.argtypes = [vp, vp, vp, u64, vp]
+    L.fqd_group_owners.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
+    L.fqd_heads_to_keep.argtypes = [vp, vp, vp, u64, vp]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

@@ -734,7 +734,8 @@ int fqd_engine_reset(fqd_engine* e)
 
 static const char kFinalised[] = "this engine was given its last batch (fqd_submit_final): fqd_engine_reset before anything else is added";
 
-static int submit_impl(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memory, uint8_t* keep, bool last_batch)
+// link (device, n uint32, or nullptr): Verdicts::first of every insert path below, see fqd_submit_linked.
+static int submit_impl(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memory, uint8_t* keep, bool last_batch, uint32_t* link = nullptr)
 {
     if (!e) return FQD_ERR_ARG;
     if (!seg || (n && !keep) || (memory != FQD_MEM_HOST && memory != FQD_MEM_DEVICE))
@@ -836,7 +837,7 @@ static int submit_impl(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memo
         const Hist1 fold{plan.hist1, plan.g, ~0ull};
         static const bool fold_on = [] { const char* v = std::getenv("FQD_FOLD_HIST1"); return !(v && v[0] == '0'); }();
         if ((rc = launch_encode(e, sv, uniform, seg, n, first, ks, e->hashes.as<uint64_t>(), nullptr, 8, fold_on ? &fold : nullptr))) return rc;
-        if ((rc = launch_bulk_insert(e, ks, e->hashes.as<uint64_t>(), 1, n, first, d_keep, plan, fold_on, nullptr, last_batch))) return rc;
+        if ((rc = launch_bulk_insert(e, ks, e->hashes.as<uint64_t>(), 1, n, first, d_keep, plan, fold_on, link, last_batch))) return rc;
     } else if (n >= 2 * e->chunk_reads && e->aux) {
         // Overlap: the encoder streams HBM, the insert is bound by memory-side atomics, so the
         // two run side by side on two streams, sub-batch k+1 being encoded while k is inserted.
@@ -863,11 +864,11 @@ static int submit_impl(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memo
             HIP_TRY(e, hipEventRecord(done, e->aux));
             HIP_TRY(e, hipStreamWaitEvent(e->stream, done, 0));
             if ((rc = launch_insert(e, ks, e->hashes.as<uint64_t>() + a, 1, c, first + a, d_keep + a, false,
-                                    e->ins_blocks_per_cu))) return rc;
+                                    e->ins_blocks_per_cu, link ? link + a : nullptr))) return rc;
         }
     } else {
         if ((rc = launch_encode(e, sv, uniform, seg, n, first, ks, e->hashes.as<uint64_t>()))) return rc;
-        if ((rc = launch_insert(e, ks, e->hashes.as<uint64_t>(), 1, n, first, d_keep))) return rc;
+        if ((rc = launch_insert(e, ks, e->hashes.as<uint64_t>(), 1, n, first, d_keep, true, 8, link))) return rc;
     }
     e->n_records += n;
     e->keys_used += new_words;
@@ -890,6 +891,18 @@ int fqd_submit(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memory, uint
 int fqd_submit_final(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memory, uint8_t* keep)
 {
     return submit_impl(e, seg, n, memory, keep, true);
+}
+
+// Every insert path clears a flag through Verdicts::lose alone (insert_kernel, bucket_dedup_kernel's walk and verify,
+// heavy_bucket_insert_kernel), and lose() writes first[loser] beside it; a displaced loser is younger than the record
+// that displaces it, which is of this batch, so it is of this batch too and first[] (indexed from the batch's first
+// record) covers it.
+int fqd_submit_linked(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memory, uint8_t* keep, uint32_t* link, int last)
+{
+    if (!e) return FQD_ERR_ARG;
+    if (memory != FQD_MEM_DEVICE || (n && !link))
+        return e->fail(FQD_ERR_ARG, "fqd_submit_linked: device memory only (FQD_MEM_DEVICE), with room for n links");
+    return submit_impl(e, seg, n, memory, keep, last != 0, link);
 }
 
 // An event recorded on `from`, waited for by `to`: a later record of the same event does not move a wait already queued.

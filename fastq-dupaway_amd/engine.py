@@ -290,6 +290,30 @@ class Engine:
         self._check(self._L.fqd_seq_pick_best(self._h, self._p(score), self._p(head), n, self._p(perm), C.byref(moved)))
         return int(moved.value)
 
+    # -- FQD_FAST_KEEP / FQD_FAST_CLUSTERS (csrc/fqd_owner.hip) -----------------------------------
+    def submit_linked(self, segs: Sequence[Reads], n: int, keep, link, last: bool = False, memory: Optional[int] = None):
+        """submit (last: submit_final) of device input that also fills link[i] (n uint32) with the engine index of an
+        earlier record of the same key for every cleared flag.  memory: the fqd_mem value handed on (default: device)."""
+        if len(segs) != self.segments:
+            raise ValueError(f"engine has {self.segments} mate(s) per record, got {len(segs)}")
+        self._check(self._L.fqd_submit_linked(self._h, self._desc(segs), n, _lib.MEM_DEVICE if memory is None else memory,
+                                              self._p(keep), self._p(link), int(last)))
+        return keep
+
+    def owners(self, keep, link, n: int, owner):
+        """owner[i] (n uint32) = the first record with record i's key, over all n records submitted so far."""
+        self._check(self._L.fqd_owners(self._h, self._p(keep), self._p(link), n, self._p(owner)))
+
+    def group_owners(self, owner, n: int, perm, head) -> int:
+        """perm = the records ordered by owner (members in input order), head = 1 at every run's first place; returns the runs."""
+        clusters = C.c_uint64(0)
+        self._check(self._L.fqd_group_owners(self._h, self._p(owner), n, self._p(perm), self._p(head), C.byref(clusters)))
+        return int(clusters.value)
+
+    def heads_to_keep(self, perm, head, n: int, keep):
+        """keep[perm[k]] = head[k]."""
+        self._check(self._L.fqd_heads_to_keep(self._h, self._p(perm), self._p(head), n, self._p(keep)))
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

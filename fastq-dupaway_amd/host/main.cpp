@@ -259,6 +259,7 @@ int main(int argc, char** argv)                                // main.cpp:181-2
             else                    remover.filterSE(opts.input_1, opts.output_1);
             return 0;
         }
+        (void)fqdhost::detail::fast_keep_best();               // a misspelt FQD_FAST_KEEP ends the run before any GPU call
         fqdhost::HashDupRemover remover(fmt, opts.memLimit, &tempdir, opts.verbose, tune);   // main.cpp:218-242
         if (opts.mode & PAIRED) remover.filterPE(opts.input_1, opts.input_2, opts.output_1, opts.output_2, opts.unordered);
         else                    remover.filterSE(opts.input_1, opts.output_1);

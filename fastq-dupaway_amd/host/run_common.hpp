@@ -368,5 +368,14 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
                      const uint8_t* keep, uint64_t upto, uint64_t dups, OutputFile* const* sinks, Format format, long long memlimit,
                      bool close_sinks = true, SurvivorBuffers* planned = nullptr);
 
+// ---- whole clusters (cluster_output.cpp): the sequence-based modes, and `--fast` with FQD_FAST_KEEP / FQD_FAST_CLUSTERS ----
+// (perm, head): an order of the n records (pairs) and a flag at the first place of every cluster.
+std::string cluster_lines(fqd_engine* e, hipStream_t stream, FileOnDevice& f, const uint32_t* perm, const uint8_t* head, uint64_t n);
+void write_cluster_lines(const std::string& lines, const std::string& name, bool append = false);
+void write_clusters(fqd_engine* e, hipStream_t stream, FileOnDevice& f, const uint32_t* perm, const uint8_t* head, uint64_t n,
+                    const std::string& name, bool append = false);
+uint64_t pick_best_members(fqd_engine* e, int S, FileOnDevice* const* files, uint64_t n, const uint8_t* head, uint32_t* perm,
+                           const char* stage = "sequence: best-quality pick on the GPU");
+
 } // namespace detail
 } // namespace fqdhost

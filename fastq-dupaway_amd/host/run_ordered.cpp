@@ -172,7 +172,7 @@ void HashDupRemover::run_ordered(int S, const std::string* in, const std::string
 
 void HashDupRemover::filterSE(const std::string& infile, const std::string& outfile)
 {
-    try { if (tuning_.devices.empty()) { if (!run_ordered_resident(1, &infile, &outfile)) run_ordered(1, &infile, &outfile); } else run_ordered_multi(1, &infile, &outfile); }
+    try { read_fast_modes(false); if (tuning_.devices.empty()) { if (!run_ordered_resident(1, &infile, &outfile)) run_ordered(1, &infile, &outfile); } else run_ordered_multi(1, &infile, &outfile); }
     catch (const DiagnosedError& e) { std::cerr << e.diag; throw; }
 }
 
@@ -181,6 +181,7 @@ void HashDupRemover::filterPE(const std::string& infile1, const std::string& inf
 {
     const std::string in[2] = {infile1, infile2}, out[2] = {outfile1, outfile2};
     try {
+        read_fast_modes(unordered);
         if (unordered) run_unordered(in, out);
         else if (tuning_.devices.empty()) { if (!run_ordered_resident(2, in, out)) run_ordered(2, in, out); }
         else           run_ordered_multi(2, in, out);

@@ -350,7 +350,54 @@ bool fetch_gzip_ordinary(const std::string& name, size_t block_bytes, int device
     return true;
 }
 
+// FQD_FAST_KEEP=first|best: which member of a cluster of identical reads (pairs) `--fast` writes.  first (and unset): the
+// first in the input, as the reference does; best: the one with the best quality line, at its own place in the input
+// (csrc/fqd_owner_core.hpp, csrc/fqd_seq_pick_core.hpp).  Read here and nowhere else.
+bool fast_keep_best()
+{
+    const char* v = std::getenv("FQD_FAST_KEEP");
+    if (!v || std::strcmp(v, "first") == 0) return false;
+    if (std::strcmp(v, "best") == 0) return true;
+    throw std::runtime_error(std::string("FQD_FAST_KEEP must be 'first' or 'best', not '") + v + "'");
+}
+
+// FQD_FAST_CLUSTERS=1: `--fast` writes `<output>.clusters` beside every output.  Read here and nowhere else.
+bool fast_clusters()
+{
+    const char* v = std::getenv("FQD_FAST_CLUSTERS");
+    return v && std::atoi(v) != 0;
+}
+
 } // namespace detail
+
+namespace {
+
+// Why a run with FQD_FAST_KEEP=best or FQD_FAST_CLUSTERS=1 ends: these modes need every record's flag to stay open until
+// the last record is in, which only the GPU-resident run offers (the streaming run's flags are final batch by batch).
+struct FastModeRefusal : std::runtime_error { using std::runtime_error::runtime_error; };
+
+std::string fast_switches(bool best, bool clusters)
+{
+    return best && clusters ? "FQD_FAST_KEEP=best and FQD_FAST_CLUSTERS=1" : best ? "FQD_FAST_KEEP=best" : "FQD_FAST_CLUSTERS=1";
+}
+
+} // namespace
+
+// Everything about the two switches that their values and the command line decide, before any GPU call.
+void HashDupRemover::read_fast_modes(bool unordered)
+{
+    keep_best_ = fast_keep_best();
+    write_clusters_ = fast_clusters();
+    if (!keep_best_ && !write_clusters_) return;
+    const std::string which = fast_switches(keep_best_, write_clusters_);
+    if (unordered)
+        throw FastModeRefusal(which + " with --unordered: these modes run on ordered inputs only");
+    if (tuning_.devices.size() > 1)
+        throw FastModeRefusal(which + " runs on one GPU: FQD_DEVICES may name one device only");
+    if (keep_best_ && format_ == Format::Fasta)
+        throw FastModeRefusal("FQD_FAST_KEEP=best needs the quality lines of FASTQ records: --format fasta has none");
+    if (tuning_.devices.size() == 1) { tuning_.device = tuning_.devices[0]; tuning_.devices.clear(); }
+}
 
 // An ordered run (single-end, or paired files read side by side) with a codec at either end — BGZF inputs, or `.gz`
 // outputs of plain regular inputs: the files go to HBM as they lie on disk, are inflated (if compressed) and cut into
@@ -359,20 +406,44 @@ bool fetch_gzip_ordinary(const std::string& name, size_t block_bytes, int device
 // everything is plain sailing — regular BGZF files of whole records, as many in file 2 as in file 1, no unknown
 // base, everything fits in HBM; otherwise false is returned BEFORE any output is touched and the streaming run
 // (run_ordered), which reproduces the reference's behaviour for every irregular input, does the job.
+//
+// With FQD_FAST_KEEP=best or FQD_FAST_CLUSTERS=1 (`modes`) the run is taken for plain files as well, links every duplicate
+// to an earlier record of its key (fqd_submit_linked), resolves the links to the first record (fqd_owners), groups the
+// records by it (fqd_group_owners) and, for `best`, moves the keep flag of every cluster to its best member
+// (pick_best_members, fqd_heads_to_keep).  There is no hand-over then: whatever would have sent the input to the
+// streaming run ends the run with a message that names the switch and the reason, still before any output exists.
 bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
 {
-    if (const char* v = std::getenv("FQD_ORDERED_RESIDENT")) if (std::atoi(v) == 0) return false;
-    if (!inflate_on_device()) return false;
+    const bool modes = keep_best_ || write_clusters_;
+    auto give_up = [&](const std::string& why) -> bool {
+        if (modes) throw FastModeRefusal(fast_switches(keep_best_, write_clusters_) + ": the GPU-resident run cannot take this input (" + why +
+                                         "), and the streaming run cannot serve these modes");
+        return false;
+    };
+    // (both are decided before any GPU call)
+    if (const char* v = std::getenv("FQD_ORDERED_RESIDENT")) if (std::atoi(v) == 0) return give_up("FQD_ORDERED_RESIDENT=0 turns that run off");
+    if (!inflate_on_device()) {
+        bool gz = !modes;                                         // with a switch set only a `.gz` input needs the device inflate
+        for (int s = 0; s < S; ++s) gz |= has_gz_extension(in[s]);
+        if (gz) return give_up("FQD_GUNZIP_DEVICE=0 keeps `.gz` inputs off the GPU");
+    }
     // worth it when a codec is involved: a BGZF input, or a `.gz` output the GPU can deflate (plain files in and
     // out are better off in the streaming run, where reading, the GPU and writing overlap)
-    bool any_gz_in = false, any_gz_out = false;
+    bool any_gz_in = false, any_gz_out = false, all_empty = true;
     for (int s = 0; s < S; ++s) {
         uint64_t size = 0;
-        if (!is_regular_file(in[s], size)) return false;
+        if (!is_regular_file(in[s], size)) return give_up(in[s] + " is not a regular file: a pipe cannot be held in GPU memory");
+        all_empty &= size == 0;
         any_gz_in |= has_gz_extension(in[s]);
         any_gz_out |= has_gz_extension(out[s]);
     }
-    if (!any_gz_in && !(any_gz_out && deflate_on_device())) return false;
+    if (!modes && !any_gz_in && !(any_gz_out && deflate_on_device())) return false;
+    if (modes && all_empty) {
+        // no record, no cluster, nothing to choose: what the default run makes of empty files, and empty cluster files
+        run_ordered(S, in, out);
+        if (write_clusters_) for (int s = 0; s < S; ++s) write_cluster_lines(std::string(), out[s] + ".clusters");
+        return true;
+    }
     HIP_OK(hipSetDevice(tuning_.device));
     hipStream_t stream = nullptr;
     HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -382,6 +453,8 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     const size_t fetch_bytes = std::max<size_t>(block_bytes, std::min<size_t>(64u << 20, static_cast<size_t>(memlimit_ > 0 ? memlimit_ / 16 : (64 << 20))));
     FileOnDevice dev[2];
     Device<uint8_t> keep;
+    Device<uint32_t> link, owner, perm; Device<uint8_t> head;     // FQD_FAST_KEEP / FQD_FAST_CLUSTERS
+    std::string clusters[2];
     uint64_t n = 0, dups = 0;
     std::unique_ptr<EngineHandle> eng;
     SurvivorBuffers buffers;
@@ -389,7 +462,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     struct JoinGuard { std::thread& t; ~JoinGuard() { if (t.joinable()) t.join(); } } join_guard{make_engine};
     try {
         CompressedOnDevice packed[2];
-        bool fetched[2] = {false, false};
+        bool fetched[2] = {false, false}, no_room[2] = {false, false};
         bool text_ready[2] = {false, false};                       // a `.gz` input whose TEXT is in HBM already (fetch_gzip_ordinary)
         std::exception_ptr fetch_error[2];
         uint64_t plain_bytes[2] = {0, 0};
@@ -410,7 +483,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
                         packed[s] = CompressedOnDevice(); dev[s].forget();
                         fetched[s] = text_ready[s] = fetch_gzip_ordinary(in[s], fetch_bytes, tuning_.device, dev[s], plain_bytes[s]);
                     }
-                } catch (const DeviceOutOfMemory&) { fetched[s] = false; }
+                } catch (const DeviceOutOfMemory&) { fetched[s] = false; no_room[s] = true; }
                 catch (const DeviceError&) { fetched[s] = false; fetch_error[s] = std::current_exception(); }
                 catch (const std::exception&) { fetched[s] = false; }      // the host reader will say what is wrong with the file
             };
@@ -421,20 +494,24 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         }
         if (make_engine.joinable()) make_engine.join();
         for (int s = 0; s < S; ++s) if (fetch_error[s]) std::rethrow_exception(fetch_error[s]);
-        for (int s = 0; s < S; ++s) if (!fetched[s]) return false;
+        for (int s = 0; s < S; ++s)
+            if (!fetched[s]) return give_up(no_room[s] ? in[s] + " does not fit in GPU memory" : in[s] + " could not be taken to GPU memory as it lies on disk (empty, damaged, or changed while it was read)");
         if (engine_error) std::rethrow_exception(engine_error);
         {
             StageClock::Scope t("ordered/resident: inflate + record scan on the GPU");
             for (int s = 0; s < S; ++s) {
                 const bool ok = has_gz_extension(in[s]) && !text_ready[s] ? finish_on_device(eng->e, stream, format_, packed[s], dev[s])
                                                                           : records_on_device(eng->e, stream, format_, plain_bytes[s], dev[s]);
-                if (!ok) return false;
+                if (!ok) return give_up(in[s] + " does not hold whole, well-formed records");
             }
         }
-        if (S == 2 && dev[0].n != dev[1].n) return false;
+        if (S == 2 && dev[0].n != dev[1].n) return give_up("the two files hold different numbers of records");
         n = dev[0].n;
+        if (modes && n >= 0x80000000ull)
+            throw FastModeRefusal(fast_switches(keep_best_, write_clusters_) + ": at most 2^31-1 records (pairs) per run, the input holds " + std::to_string(n));
         StageClock::Scope t("ordered/resident: dedup on the GPU");
         keep.reserve(n);
+        if (modes) { link.reserve(n); owner.reserve(n); perm.reserve(n); head.reserve(n); }
         const size_t kBatch = 16u << 20;
         int rc = FQD_OK;
         for (size_t a = 0; a < n && rc == FQD_OK; a += kBatch) {
@@ -443,34 +520,63 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
                 seg[s].bases = reinterpret_cast<const uint8_t*>(dev[s].text.p);
                 seg[s].offsets = dev[s].seq_off.p + a; seg[s].lengths = dev[s].seq_len.p + a;
             }
-            rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
+            if (modes) rc = fqd_submit_linked(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, link.p + a, a + kBatch < n ? 0 : 1);
+            else rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
         }
         if (rc == FQD_OK) rc = fqd_engine_sync(eng->e);
-        if (rc == FQD_ERR_BAD_BASE) return false;                 // the streaming run cuts the output where the reference does
+        if (rc == FQD_ERR_BAD_BASE) return give_up(std::string(fqd_last_error(eng->e)));   // the streaming run cuts the output where the reference does
         if (rc != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e));
         if (std::getenv("FQD_TEST_FAIL_RESIDENT")) throw DeviceError("GPU engine: forced by FQD_TEST_FAIL_RESIDENT");      // tests: the hand-over is announced
         fqd_stats st{};
         fqd_get_stats(eng->e, &st);
         dups = st.duplicates;
+        FileOnDevice* all_files[2] = {&dev[0], &dev[1]};
+        if (modes) {
+            auto engine_ok = [&](int rc2) { if (rc2 != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e)); };
+            uint64_t n_clusters = 0;
+            {
+                StageClock::Scope t2("fast: owners and clusters on the GPU");
+                engine_ok(fqd_owners(eng->e, keep.p, link.p, n, owner.p));
+                engine_ok(fqd_group_owners(eng->e, owner.p, n, perm.p, head.p, &n_clusters));
+            }
+            if (n_clusters + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
+            link.release(); owner.release();
+            if (keep_best_) {
+                const uint64_t moved = pick_best_members(eng->e, S, all_files, n, head.p, perm.p, "fast: best-quality pick on the GPU");
+                engine_ok(fqd_heads_to_keep(eng->e, perm.p, head.p, n, keep.p));
+                if (StageClock::on()) std::cerr << "fast: best-quality pick, " << moved << " of " << n_clusters << " clusters changed\n";
+            }
+            if (write_clusters_) {
+                StageClock::Scope t2("fast: ID lines of the clusters out of HBM");
+                for (int s = 0; s < S; ++s) clusters[s] = cluster_lines(eng->e, stream, dev[s], perm.p, head.p, n);
+            }
+            perm.release(); head.release();
+        }
         // everything the writer needs is reserved HERE, while the run can still hand over: once an output exists it cannot
         bool gz_out[2] = {false, false};
         for (int s = 0; s < S; ++s) gz_out[s] = has_gz_extension(out[s]);
         FileOnDevice* files[2] = {&dev[0], &dev[1]};
         const uint32_t* idx[2] = {nullptr, nullptr};
         plan_survivors(eng->e, S, files, idx, keep.p, n, gz_out, memlimit_, buffers);
+    } catch (const FastModeRefusal&) {
+        throw;                                                    // nothing has been written
     } catch (const DeviceOutOfMemory&) {
-        return false;                                             // HBM that does not suffice: the streaming run needs a few blocks of it only
+        return give_up("the text, the record arrays and up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory");   // the streaming run needs a few blocks of HBM only
     } catch (const DeviceError& e) {
+        if (modes) return give_up(e.what());
         announce_handover("the GPU-resident ordered run", e);     // nothing has been written yet
         return false;
-    } catch (const std::exception&) {
-        return false;                                             // an input the host reader will report on in the reference's words
+    } catch (const std::exception& e) {
+        if (modes) if (const DiagnosedError* d = dynamic_cast<const DiagnosedError*>(&e)) std::cerr << d->diag;   // what the host reader found, in full
+        return give_up(e.what());                                 // an input the host reader will report on in the reference's words
     }
     // from here on the run is this one's: outputs are created, filled and closed
     OutputFile sink0(out[0]);
     std::unique_ptr<OutputFile> sink1;
     if (S == 2) sink1 = std::make_unique<OutputFile>(out[1]);
     OutputFile* sinks[2] = {&sink0, sink1.get()};
+    if (write_clusters_)
+        for (int s = 0; s < S; ++s) { write_cluster_lines(clusters[s], out[s] + ".clusters"); std::string().swap(clusters[s]); }
     {
         StageClock::Scope t("ordered/resident: survivors out of HBM");
         FileOnDevice* files[2] = {&dev[0], &dev[1]};

@@ -10,7 +10,6 @@
 
 #include <cstdio>
 #include <cstring>
-#include <fstream>
 
 #include "run_common.hpp"
 #include "../csrc/fqd_seq_range_core.hpp"
@@ -108,57 +107,6 @@ void load_file(fqd_engine* e, hipStream_t stream, const std::string& name, Forma
         side.pos += nb;
     }
     if (side.failed) { std::cerr << side.failure.diag; throw std::runtime_error(side.failure.what); }
-}
-
-// `<output>.clusters` (file_utils.cpp:98-112): per sorted record its ID line, "--" in front of the duplicates.  The ID
-// lines are gathered in sorted order on the device (fqd_output_plan + fqd_copy_spans) and written as they come back.
-void write_clusters(fqd_engine* e, hipStream_t stream, FileOnDevice& f, const uint32_t* perm, const uint8_t* head, uint64_t n,
-                    const std::string& name, bool append = false)
-{
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(e)); };
-    Device<uint8_t> all; Device<uint64_t> src_off, dst_off; Device<uint32_t> len;
-    all.reserve(n); src_off.reserve(n); dst_off.reserve(n + 1); len.reserve(n);
-    HIP_OK(hipMemsetAsync(all.p, 1, n, stream));
-    uint64_t total = 0;
-    engine_ok(fqd_output_plan(e, all.p, perm, n, f.start.p, f.id_len.p, src_off.p, len.p, dst_off.p, &total));
-    Device<char> ids; ids.reserve(total + 64);
-    engine_ok(fqd_copy_spans(e, reinterpret_cast<const uint8_t*>(f.text.p), src_off.p, len.p, n, reinterpret_cast<uint8_t*>(ids.p), dst_off.p));
-    std::vector<char> h_ids(total);
-    std::vector<uint32_t> h_len(n);
-    std::vector<uint8_t> h_head(n);
-    HIP_OK(hipMemcpyAsync(h_ids.data(), ids.p, total, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipMemcpyAsync(h_len.data(), len.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipMemcpyAsync(h_head.data(), head, n, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    std::ofstream out(name, append ? std::ios::binary | std::ios::app : std::ios::binary);
-    std::string buf;
-    buf.reserve(total + 2 * n);
-    uint64_t at = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-        if (!h_head[k]) buf += "--";
-        buf.append(h_ids.data() + at, h_len[k]);
-        at += h_len[k];
-    }
-    out.write(buf.data(), static_cast<std::streamsize>(buf.size()));
-}
-
-
-// FQD_SEQ_KEEP=best: per cluster of `head` the member with the best quality line takes the head's place in `perm`
-// (fqd_seq_scores over the whole records of the n pairs, fqd_seq_pick_best); everything after it reads perm as before.
-// Returns the number of clusters whose written member changed.
-uint64_t pick_best_members(fqd_engine* e, int S, FileOnDevice* const* files, uint64_t n, const uint8_t* head, uint32_t* perm)
-{
-    StageClock::Scope t("sequence: best-quality pick on the GPU");
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(e)); };
-    fqd_tags recs[2];
-    for (int s = 0; s < S; ++s)
-        recs[s] = fqd_tags{reinterpret_cast<const uint8_t*>(files[s]->text.p), files[s]->start.p, files[s]->size.p, n};
-    Device<uint32_t> score;
-    score.reserve(n);
-    uint64_t moved = 0;
-    engine_ok(fqd_seq_scores(e, &recs[0], S == 2 ? &recs[1] : nullptr, score.p));
-    engine_ok(fqd_seq_pick_best(e, score.p, head, n, perm, &moved));
-    return moved;
 }
 
 // ---- the ranged run ---------------------------------------------------------------------------------------------------

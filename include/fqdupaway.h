@@ -562,6 +562,31 @@ int  fqd_seq_plan_ranges(fqd_engine* e, const uint64_t* key, const uint32_t* byt
 int  fqd_seq_scores(fqd_engine* e, const fqd_tags* rec1, const fqd_tags* rec2, uint32_t* score);
 int  fqd_seq_pick_best(fqd_engine* e, const uint32_t* score, const uint8_t* head, uint64_t n, uint32_t* perm, uint64_t* n_moved);
 
+/* ---- FQD_FAST_KEEP / FQD_FAST_CLUSTERS: which record a `--fast` duplicate repeats (added within ABI version 5: purely
+ * additive; fqd_submit and fqd_submit_final launch the same kernels with the same arguments as before).  Rules and
+ * proofs: csrc/fqd_owner_core.hpp.
+ *
+ * fqd_submit_linked: fqd_submit (last == 0) or fqd_submit_final (last != 0) for FQD_MEM_DEVICE input, plus link (device,
+ * n uint32): for every record of the batch whose flag is cleared, link[i] = the ENGINE index of an earlier record with
+ * the identical key.  Entries of kept records are not written.  Which earlier record a link names depends on how the
+ * batch was scheduled; callers rely on "earlier, same key" only.  Any other memory space is FQD_ERR_ARG.
+ *
+ * fqd_owners: keep and link (device) are those of ALL n records submitted so far (every batch through
+ * fqd_submit_linked, flags and links at the records' engine indices).  owner[i] (device, n uint32) = i where keep[i],
+ * else the kept record the chain of links from i ends at: the first record with i's key.  Does not use the table (works
+ * after the final batch).  Returns after the stream has drained; a link that does not decrease is FQD_ERR_ARG.
+ *
+ * fqd_group_owners: perm (device, n uint32) = the records ordered by owner, the members of an owner in input order;
+ * head[k] (device, n bytes) = 1 at the first place of every run; *n_clusters (host, may be NULL) = the runs.  n < 2^31.
+ * 24 bytes of scratch per record during the call.  Returns after the stream has drained.
+ *
+ * fqd_heads_to_keep: keep[perm[k]] = head[k] for k < n (all device): after fqd_seq_pick_best over (perm, head) the
+ * record at every head's place is the one to write.  Returns after the stream has drained. */
+int  fqd_submit_linked(fqd_engine* e, const fqd_reads* seg, uint64_t n, int memory, uint8_t* keep, uint32_t* link, int last);
+int  fqd_owners(fqd_engine* e, const uint8_t* keep, const uint32_t* link, uint64_t n, uint32_t* owner);
+int  fqd_group_owners(fqd_engine* e, const uint32_t* owner, uint64_t n, uint32_t* perm, uint8_t* head, uint64_t* n_clusters);
+int  fqd_heads_to_keep(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint64_t n, uint8_t* keep);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
