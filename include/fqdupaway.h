@@ -51,7 +51,9 @@ extern "C" {
 #define FQD_FLAG_NO_STAGE   2u  /* testing: force the per-lane global-load encoder    */
 #define FQD_FLAG_WEAK_HASH  4u  /* testing: zero every hash's tag and its low 6 position bits,
                                    so unequal keys keep meeting in the table and the
-                                   verify-then-probe-on branch runs on every insert    */
+                                   verify-then-probe-on branch runs on every insert.
+                                   The flag alone does not make NEAR-EQUAL keys meet: the
+                                   input has to hold them (tests/test_gpu_key_compare.py) */
 
 typedef struct fqd_engine fqd_engine;
 

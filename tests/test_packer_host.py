@@ -13,10 +13,11 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from key_layout import CODE, expected_hash, expected_words  # noqa: F401  (the layout's statement lives in tests/key_layout.py)
+
 HERE = Path(__file__).resolve().parent
 SRC = HERE / "native" / "host_pack_check.cpp"
 EXE = HERE / "native" / "host_pack_check"
-CODE = {ord("A"): 0, ord("C"): 1, ord("T"): 2, ord("G"): 3, ord("N"): 3}
 
 
 @pytest.fixture(scope="module")
@@ -39,26 +40,6 @@ def packer():
     return run
 
 
-def expected_words(seq: bytes):
-    """Independent statement of the layout in fqd_device.hpp: per 64-base block
-    [codes group 0][codes group 1 if any][N mask]; inside a 32-base group, base
-    4k+j (dword k, byte j) -> codes bits 32*(k//4) + 8j + 2(k%4), mask bit 8j + k."""
-    words = []
-    for blk in range(0, len(seq), 64):
-        part = seq[blk:blk + 64]
-        mask = 0
-        for gi, g in enumerate(range(0, len(part), 32)):
-            w = 0
-            for b, c in enumerate(part[g:g + 32]):
-                k, j = divmod(b, 4)
-                w |= CODE[c] << (32 * (k // 4) + 8 * j + 2 * (k % 4))
-                if c == ord("N"):
-                    mask |= 1 << (32 * gi + 8 * j + k)
-            words.append(w)
-        words.append(mask)
-    return words
-
-
 def test_words_match_independent_packing(packer):
     rnd = random.Random(1)
     cases = []
@@ -71,6 +52,7 @@ def test_words_match_independent_packing(packer):
         assert r["bad_pos"] == 0xFFFFFFFF
         assert r["words"] == expected_words(seq), (sh, seq)
         assert r["n"] == (len(seq) + 31) // 32 + (len(seq) + 63) // 64
+        assert r["hash"] == expected_hash(len(seq), 0, expected_words(seq)), (sh, seq)     # the restated hash (key_layout)
 
 
 def test_alignment_does_not_change_key_or_hash(packer):
