@@ -14,14 +14,13 @@ namespace detail {
 // call this BEFORE it creates an output.
 std::string cluster_lines(fqd_engine* e, hipStream_t stream, FileOnDevice& f, const uint32_t* perm, const uint8_t* head, uint64_t n)
 {
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(e)); };
     Device<uint8_t> all; Device<uint64_t> src_off, dst_off; Device<uint32_t> len;
     all.reserve(n); src_off.reserve(n); dst_off.reserve(n + 1); len.reserve(n);
     HIP_OK(hipMemsetAsync(all.p, 1, n, stream));
     uint64_t total = 0;
-    engine_ok(fqd_output_plan(e, all.p, perm, n, f.start.p, f.id_len.p, src_off.p, len.p, dst_off.p, &total));
+    engine_ok(e, fqd_output_plan(e, all.p, perm, n, f.start.p, f.id_len.p, src_off.p, len.p, dst_off.p, &total));
     Device<char> ids; ids.reserve(total + 64);
-    engine_ok(fqd_copy_spans(e, reinterpret_cast<const uint8_t*>(f.text.p), src_off.p, len.p, n, reinterpret_cast<uint8_t*>(ids.p), dst_off.p));
+    engine_ok(e, fqd_copy_spans(e, reinterpret_cast<const uint8_t*>(f.text.p), src_off.p, len.p, n, reinterpret_cast<uint8_t*>(ids.p), dst_off.p));
     std::vector<char> h_ids(total);
     std::vector<uint32_t> h_len(n);
     std::vector<uint8_t> h_head(n);
@@ -58,15 +57,14 @@ void write_clusters(fqd_engine* e, hipStream_t stream, FileOnDevice& f, const ui
 uint64_t pick_best_members(fqd_engine* e, int S, FileOnDevice* const* files, uint64_t n, const uint8_t* head, uint32_t* perm, const char* stage)
 {
     StageClock::Scope t(stage);
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(e)); };
     fqd_tags recs[2];
     for (int s = 0; s < S; ++s)
         recs[s] = fqd_tags{reinterpret_cast<const uint8_t*>(files[s]->text.p), files[s]->start.p, files[s]->size.p, n};
     Device<uint32_t> score;
     score.reserve(n);
     uint64_t moved = 0;
-    engine_ok(fqd_seq_scores(e, &recs[0], S == 2 ? &recs[1] : nullptr, score.p));
-    engine_ok(fqd_seq_pick_best(e, score.p, head, n, perm, &moved));
+    engine_ok(e, fqd_seq_scores(e, &recs[0], S == 2 ? &recs[1] : nullptr, score.p));
+    engine_ok(e, fqd_seq_pick_best(e, score.p, head, n, perm, &moved));
     return moved;
 }
 

@@ -1,6 +1,8 @@
-// run_common.hpp — what the ways of running the `--fast` path share (host/run_*.cpp, survivor_writer.cpp): typed device
-// errors, RAII over HIP memory and the C ABI, the block pipeline of an input file (Side), a batch on its way from the
-// feeder over the GPU to the writers (Work), the writer threads, and the GPU-resident runs' view of a file.
+// run_common.hpp — what the ways of running share (host/run_*.cpp, resident_input.cpp, survivor_writer.cpp,
+// cluster_output.cpp): typed device errors, RAII over HIP memory, streams and the C ABI, block sizes and the `-v` lines,
+// the block pipeline of an input file (Side), a batch on its way from the feeder over the GPU to the writers (Work), the
+// writer threads, the GPU-resident runs' view of a file (FileOnDevice) and everything that brings an input into one
+// (resident_input.cpp).
 // Everything lives in fqdhost::detail; the public surface stays hash_dup_remover.hpp.
 #pragma once
 #include "hash_dup_remover.hpp"
@@ -10,6 +12,7 @@
 #include <cstring>
 #include <deque>
 #include <filesystem>
+#include <functional>
 #include <hip/hip_runtime_api.h>
 #include <iostream>
 #include <memory>
@@ -58,6 +61,53 @@ struct EngineHandle {
     }
     ~EngineHandle() { if (!g_leave_memory_to_exit) fqd_engine_destroy(e); }
 };
+
+// An engine call's return code: anything but FQD_OK throws E with the engine's last error.  E: std::runtime_error, or
+// DeviceError where the caller hands the run over on one (run_ordered_resident before its outputs exist, plan_survivors).
+template <class E = std::runtime_error>
+inline void engine_ok(fqd_engine* e, int rc)
+{
+    if (rc != FQD_OK) throw E(std::string("GPU engine: ") + fqd_last_error(e));
+}
+
+// A non-blocking stream of the current device, destroyed with its scope.
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    StreamGuard() { HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    ~StreamGuard() { (void)hipStreamDestroy(s); }
+    StreamGuard(const StreamGuard&) = delete;
+    StreamGuard& operator=(const StreamGuard&) = delete;
+    operator hipStream_t() const { return s; }
+};
+
+// Pinned blocks of the host reader: three per file in flight at most, sized so that they stay well inside --mem-limit
+// (memlimit <= 0: no limit).  A file fetched whole (resident_input.cpp) is read in larger pieces than the streaming
+// run's blocks: the parallel read of a piece needs 16 MB per thread.
+inline size_t block_bytes_for(const Tuning& tuning, long long memlimit)
+{
+    return std::max<size_t>(1u << 20, std::min<size_t>(tuning.block_bytes, memlimit > 0 ? static_cast<size_t>(memlimit / 16) : tuning.block_bytes));
+}
+inline size_t fetch_bytes_for(size_t block_bytes, long long memlimit)
+{
+    return std::max<size_t>(block_bytes, std::min<size_t>(64u << 20, memlimit > 0 ? static_cast<size_t>(memlimit / 16) : (64u << 20)));
+}
+
+// What `-v` prints (hash_dup_remover.hpp:146-147,253-254,342-346; seq_dup_remover.hpp:107-108,216-217).
+inline void print_summary(int S, uint64_t total, uint64_t duplicates)
+{
+    std::cout << total << (S == 1 ? " reads" : " read pairs") << " processed, out of which " << duplicates << " duplicates were removed.\n";
+}
+inline void print_unordered_summary(const Summary& s)
+{
+    std::cout << s.total << " valid read pairs processed, out of which " << s.duplicates << " duplicates were removed.\n";
+    std::cout << s.unmatched << " Non-matching entries from both files were skipped.\n";
+}
+
+// A malformed record the host reader met: the reference's line on stderr, its exception text.
+inline void throw_if_set(const ParseFailure& f)
+{
+    if (f.set) { std::cerr << f.diag; throw std::runtime_error(f.what); }
+}
 
 // The reference's two lines for a byte outside {A,C,G,T,N} (seq_utils.cpp:17-19).
 [[noreturn]] inline void throw_unknown_base(uint8_t byte)
@@ -307,7 +357,7 @@ struct GrowDevice {
 
 bool is_regular_file(const std::string& name, uint64_t& size);
 
-// ---- text resident in HBM (run_resident.cpp, survivor_writer.cpp) -------------------------------------------------
+// ---- text resident in HBM (resident_input.cpp, run_resident.cpp, survivor_writer.cpp) -----------------------------
 
 // One pass, text resident in HBM (see run_unordered).
 // A file whose text stays in HBM: the text and, per record, where it starts, where its sequence starts, the
@@ -337,6 +387,7 @@ struct CompressedOnDevice {
     uint64_t bad_members = 0;
 };
 
+// resident_input.cpp: a file to HBM as it lies on disk, by the fetch that applies to it ...
 bool inflate_on_device();                                     // FQD_GUNZIP_DEVICE
 bool deflate_on_device();                                     // FQD_GZ_DEVICE / FQD_GZ_LEVEL
 bool fetch_bgzf(const std::string& name, size_t block_bytes, int device, CompressedOnDevice& c, FileOnDevice* into = nullptr);
@@ -345,6 +396,37 @@ bool fetch_gzip_ordinary(const std::string& name, size_t block_bytes, int device
 bool records_on_device(fqd_engine* e, hipStream_t stream, Format format, uint64_t text_bytes, FileOnDevice& f);
 bool finish_on_device(fqd_engine* e, hipStream_t stream, Format format, CompressedOnDevice& c, FileOnDevice& f);
 void guess_capacity(int S, const std::string* in, uint64_t& reads, uint64_t& bases);
+
+// ... the cascade of the three fetches, in two phases because the runs overlap them differently (both files fetched on
+// two threads and then cut one after the other on the engine's stream, or file after file): fetch_file says which way
+// took the file — none (the host reader's, below), BGZF (the members in `packed`) or its text already in f.text — and
+// cut_records goes on from there (finish_on_device / records_on_device; false: not whole, well-formed records).
+// Exceptions pass through both: what they mean differs from run to run.
+struct Fetched {
+    enum Way { None, Packed, Text } way = None;
+    CompressedOnDevice packed;
+    uint64_t text_bytes = 0;
+};
+void fetch_file(const std::string& name, size_t fetch_bytes, int device, FileOnDevice& f, Fetched& got);
+bool cut_records(fqd_engine* e, hipStream_t stream, Format format, Fetched& got, FileOnDevice& f);
+
+// ... and the host reader's way, block by block.  The per-record arrays of a block on their way to the device:
+// fill() lays them out for a block whose first record's text goes to `base`, copy_to() sends them.
+struct RecordStaging {
+    Pinned<uint64_t> h_start, h_seq; Pinned<uint32_t> h_idl, h_sql, h_size;
+    void fill(const RecordRef* r, size_t nb, uint64_t base);
+    void copy_to(uint64_t* start, uint64_t* seq_off, uint32_t* id_len, uint32_t* seq_len, uint32_t* size, size_t nb, hipStream_t stream) const;
+};
+// Records [from, from + nb) of a block to the tail of f; waits for the copies (the block and the staging arrays are reused).
+void append_block(FileOnDevice& f, const PooledBlock* b, size_t from, size_t nb, RecordStaging& staging, hipStream_t up);
+// Every block of a file through the host reader.  body(block, first unread record, records, index of that record in the
+// file) must be done with the block when it returns.  What the reader found wrong with the file is RETURNED (set or not):
+// an `--unordered` run holds a failure of file 2 back until everything about file 1 has been said (hpp:161-173), the
+// others throw at once (throw_if_set).
+using BlockBody = std::function<void(const PooledBlock*, size_t, size_t, uint64_t)>;
+ParseFailure stream_blocks(const std::string& name, Format format, bool want_tag, int device, size_t block_bytes, const BlockBody& body);
+// stream_blocks with append_block as its body.
+ParseFailure append_file(const std::string& name, Format format, bool want_tag, int device, size_t block_bytes, FileOnDevice& f, hipStream_t up);
 
 // The outputs of a run whose text is in HBM: pair k < upto (record idx[s][k] of file s; idx[s] == nullptr: record k)
 // is written iff keep[k].  The device assembles windows of survivors in output order (and deflates them, for `.gz`

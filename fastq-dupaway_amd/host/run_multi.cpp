@@ -256,10 +256,7 @@ void HashDupRemover::run_ordered_multi(int S, const std::string* in, const std::
         }
     }
     summary_.total = next_index; summary_.duplicates = total_dups; summary_.unmatched = 0;
-    if (verbose_) {
-        if (S == 1) std::cout << summary_.total << " reads processed, out of which " << summary_.duplicates << " duplicates were removed.\n";
-        else        std::cout << summary_.total << " read pairs processed, out of which " << summary_.duplicates << " duplicates were removed.\n";
-    }
+    if (verbose_) print_summary(S, summary_.total, summary_.duplicates);
 }
 
 // ---------------------------------------------------------------------------
@@ -280,7 +277,7 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
 {
     const std::vector<int>& devs = tuning_.devices;
     const int N = static_cast<int>(devs.size());
-    const size_t block_bytes = std::max<size_t>(1u << 20, std::min<size_t>(tuning_.block_bytes, static_cast<size_t>(memlimit_ > 0 ? memlimit_ / 16 : tuning_.block_bytes)));
+    const size_t block_bytes = block_bytes_for(tuning_, memlimit_);
     struct Rank {
         int device = 0; hipStream_t stream = nullptr; std::unique_ptr<EngineHandle> eng;
         FileOnDevice part[2];                                  // what was dealt to this GPU of each file
@@ -300,7 +297,6 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
         HIP_OK(hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking));
         k.eng = std::make_unique<EngineHandle>(2, k.device, k.stream);
     }
-    auto eng_ok = [&](Rank& k, int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(k.eng->e)); };
 
     // ---- 1. both files, block by block, dealt to the GPUs ---------------------------------------------------------
     {
@@ -312,41 +308,14 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
                 std::vector<hipStream_t> up(size_t(N), nullptr);
                 struct Guard { std::vector<hipStream_t>& v; std::vector<std::unique_ptr<Rank>>& rk; ~Guard() { for (size_t g = 0; g < v.size(); ++g) if (v[g]) { (void)hipSetDevice(rk[g]->device); (void)hipStreamDestroy(v[g]); } } } guard{up, rank};
                 for (int g = 0; g < N; ++g) { HIP_OK(hipSetDevice(rank[size_t(g)]->device)); HIP_OK(hipStreamCreateWithFlags(&up[size_t(g)], hipStreamNonBlocking)); }
-                Pinned<uint64_t> h_start, h_seq; Pinned<uint32_t> h_idl, h_sql, h_size;
-                Side side;
-                side.open_file(in[s], format_, true, block_bytes);
-                HIP_OK(hipSetDevice(rank[0]->device));
-                side.prime(3, rank[0]->device);
+                RecordStaging staging;
+                HIP_OK(hipSetDevice(rank[0]->device));             // (the reader's threads and pinned blocks: prime(3, rank[0]->device))
                 uint64_t block_no = 0;
-                while (side.available() > 0) {
-                    const int g = int(block_no++ % uint64_t(N));
-                    HIP_OK(hipSetDevice(rank[size_t(g)]->device));
-                    FileOnDevice& f = rank[size_t(g)]->part[s];
-                    hipStream_t st = up[size_t(g)];
-                    PooledBlock* b = side.cur;
-                    const size_t from = side.pos, nb = b->recs.size() - from;
-                    const RecordRef* r = &b->recs[from];
-                    const uint64_t text_lo = r[0].start, bytes = r[nb - 1].start + r[nb - 1].size - text_lo;
-                    f.text.room_for(bytes + 64, st);
-                    HIP_OK(hipMemcpyAsync(f.text.p + f.text.used, b->text.p + text_lo, bytes, hipMemcpyHostToDevice, st));
-                    h_start.reserve(nb); h_seq.reserve(nb); h_idl.reserve(nb); h_sql.reserve(nb); h_size.reserve(nb);
-                    for (size_t k = 0; k < nb; ++k) {
-                        h_start.p[k] = f.text.used + (r[k].start - text_lo); h_seq.p[k] = h_start.p[k] + r[k].id_len;
-                        h_idl.p[k] = r[k].id_len; h_sql.p[k] = r[k].seq_len; h_size.p[k] = r[k].size;
-                    }
-                    f.start.room_for(nb, st); f.seq_off.room_for(nb, st); f.id_len.room_for(nb, st); f.seq_len.room_for(nb, st); f.size.room_for(nb, st);
-                    HIP_OK(hipMemcpyAsync(f.start.p + f.n, h_start.p, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-                    HIP_OK(hipMemcpyAsync(f.seq_off.p + f.n, h_seq.p, nb * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-                    HIP_OK(hipMemcpyAsync(f.id_len.p + f.n, h_idl.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                    HIP_OK(hipMemcpyAsync(f.seq_len.p + f.n, h_sql.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                    HIP_OK(hipMemcpyAsync(f.size.p + f.n, h_size.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-                    HIP_OK(hipStreamSynchronize(st));            // the block and the staging arrays are reused
-                    f.text.used += bytes;
-                    f.start.used = f.seq_off.used = f.id_len.used = f.seq_len.used = f.size.used = f.n + nb;
-                    f.n += nb;
-                    side.pos += nb;
-                }
-                if (side.failed) parse_failure[s] = side.failure;
+                parse_failure[s] = stream_blocks(in[s], format_, true, rank[0]->device, block_bytes, [&](const PooledBlock* b, size_t from, size_t nb, uint64_t) {
+                    const size_t g = size_t(block_no++ % uint64_t(N));   // dealt round-robin
+                    HIP_OK(hipSetDevice(rank[g]->device));
+                    append_block(rank[g]->part[s], b, from, nb, staging, up[g]);
+                });
             } catch (...) { err[s] = std::current_exception(); }
         };
         std::thread second(load, 1);
@@ -354,7 +323,7 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
         second.join();
         for (int s = 0; s < 2; ++s) {                            // everything about file 1 before anything about file 2 (hpp:161-173)
             if (err[s]) std::rethrow_exception(err[s]);
-            if (parse_failure[s].set) { std::cerr << parse_failure[s].diag; throw std::runtime_error(parse_failure[s].what); }
+            throw_if_set(parse_failure[s]);
         }
     }
     uint64_t n_file[2] = {0, 0};
@@ -374,12 +343,12 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
                 FileOnDevice& f = k.part[s];
                 if (!f.n) continue;
                 f.tag_off.reserve(f.n); f.tag_len.reserve(f.n);
-                eng_ok(k, fqd_extract_tags(k.eng->e, reinterpret_cast<const uint8_t*>(f.text.p), f.start.p, f.id_len.p, f.n, f.tag_off.p, f.tag_len.p));
+                engine_ok(k.eng->e, fqd_extract_tags(k.eng->e, reinterpret_cast<const uint8_t*>(f.text.p), f.start.p, f.id_len.p, f.n, f.tag_off.p, f.tag_len.p));
                 const uint32_t want = uint32_t(std::min<uint64_t>(f.n, 4096));
                 Device<uint8_t> d_bytes; Device<uint32_t> d_len;
                 d_bytes.reserve(size_t(want) * kSampleStride); d_len.reserve(want);
                 const fqd_tags tg{reinterpret_cast<const uint8_t*>(f.text.p), f.tag_off.p, f.tag_len.p, f.n};
-                eng_ok(k, fqd_sample_tags(k.eng->e, &tg, want, kSampleStride, d_bytes.p, d_len.p));
+                engine_ok(k.eng->e, fqd_sample_tags(k.eng->e, &tg, want, kSampleStride, d_bytes.p, d_len.p));
                 std::vector<uint8_t> hb(size_t(want) * kSampleStride); std::vector<uint32_t> hl(want);
                 HIP_OK(hipMemcpyAsync(hb.data(), d_bytes.p, hb.size(), hipMemcpyDeviceToHost, k.stream));
                 HIP_OK(hipMemcpyAsync(hl.data(), d_len.p, hl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, k.stream));
@@ -416,7 +385,7 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
                 if (!f.n) continue;
                 k.cls[s].reserve(f.n);
                 const fqd_tags tg{reinterpret_cast<const uint8_t*>(f.text.p), f.tag_off.p, f.tag_len.p, f.n};
-                eng_ok(k, fqd_classify_tags(k.eng->e, &tg, d_sb.p, kSampleStride, d_sl.p, n_split, k.cls[s].p));
+                engine_ok(k.eng->e, fqd_classify_tags(k.eng->e, &tg, d_sb.p, kSampleStride, d_sl.p, n_split, k.cls[s].p));
             }
             HIP_OK(hipStreamSynchronize(k.stream));             // d_sb / d_sl go out of scope
         }
@@ -434,12 +403,12 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
                     HIP_OK(hipSetDevice(k.device));
                     Plan p; p.keep.reserve(f.n); p.src_off.reserve(f.n); p.dst_off.reserve(f.n + 1); p.len.reserve(f.n);
                     uint64_t cnt = 0, bytes = 0;
-                    eng_ok(k, fqd_range_keep(k.eng->e, k.cls[s].p, f.n, uint32_t(j), p.keep.p, &cnt));
+                    engine_ok(k.eng->e, fqd_range_keep(k.eng->e, k.cls[s].p, f.n, uint32_t(j), p.keep.p, &cnt));
                     if (!cnt) continue;
-                    eng_ok(k, fqd_output_plan(k.eng->e, p.keep.p, nullptr, f.n, f.start.p, f.size.p, p.src_off.p, p.len.p, p.dst_off.p, &bytes));
+                    engine_ok(k.eng->e, fqd_output_plan(k.eng->e, p.keep.p, nullptr, f.n, f.start.p, f.size.p, p.src_off.p, p.len.p, p.dst_off.p, &bytes));
                     piece[size_t(g)] = std::make_unique<Device<char>>();
                     piece[size_t(g)]->reserve(bytes + 64);
-                    eng_ok(k, fqd_copy_spans(k.eng->e, reinterpret_cast<const uint8_t*>(f.text.p), p.src_off.p, p.len.p, f.n,
+                    engine_ok(k.eng->e, fqd_copy_spans(k.eng->e, reinterpret_cast<const uint8_t*>(f.text.p), p.src_off.p, p.len.p, f.n,
                                              reinterpret_cast<uint8_t*>(piece[size_t(g)]->p), p.dst_off.p));
                     HIP_OK(hipStreamSynchronize(k.stream));     // the plan arrays go out of scope; the piece is complete
                     piece_bytes[size_t(g)] = bytes; total += bytes;
@@ -478,7 +447,7 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
                 const uint64_t bytes = f.text.used;
                 if (!records_on_device(k.eng->e, k.stream, format_, bytes, f)) throw std::runtime_error("--unordered: internal: a range's text is not whole records");
                 f.tag_off.reserve(f.n); f.tag_len.reserve(f.n);
-                eng_ok(k, fqd_extract_tags(k.eng->e, reinterpret_cast<const uint8_t*>(f.text.p), f.start.p, f.id_len.p, f.n, f.tag_off.p, f.tag_len.p));
+                engine_ok(k.eng->e, fqd_extract_tags(k.eng->e, reinterpret_cast<const uint8_t*>(f.text.p), f.start.p, f.id_len.p, f.n, f.tag_off.p, f.tag_len.p));
             }
             const uint64_t na = k.range[0].n, nb = k.range[1].n;
             base_a[size_t(j) + 1] = base_a[size_t(j)] + na; base_b[size_t(j) + 1] = base_b[size_t(j)] + nb;
@@ -488,7 +457,7 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
                 const fqd_tags ta{reinterpret_cast<const uint8_t*>(k.range[0].text.p), k.range[0].tag_off.p, k.range[0].tag_len.p, na};
                 const fqd_tags tb{reinterpret_cast<const uint8_t*>(k.range[1].text.p), k.range[1].tag_off.p, k.range[1].tag_len.p, nb};
                 const fqd_join jo{k.jp.perm[0].p, k.jp.perm[1].p, k.jp.match[0].p, k.jp.match[1].p, k.jp.pair[0].p, k.jp.pair[1].p, &k.n_pairs};
-                eng_ok(k, fqd_join_tags(k.eng->e, &ta, &tb, &jo));
+                engine_ok(k.eng->e, fqd_join_tags(k.eng->e, &ta, &tb, &jo));
                 k.joined = true;
             }
             base_p[size_t(j) + 1] = base_p[size_t(j)] + k.n_pairs;
@@ -526,7 +495,7 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
             const fqd_tags tg[2] = {{reinterpret_cast<const uint8_t*>(k.range[0].text.p), k.range[0].tag_off.p, k.range[0].tag_len.p, k.range[0].n},
                                     {reinterpret_cast<const uint8_t*>(k.range[1].text.p), k.range[1].tag_off.p, k.range[1].tag_len.p, k.range[1].n}};
             const uint64_t local = pos_other - base_other[size_t(j)];
-            eng_ok(k, fqd_count_tags_le(k.eng->e, &tg[of], &tg[other], peek_u32(k.jp.perm[other].p, local, k.stream), &c));
+            engine_ok(k.eng->e, fqd_count_tags_le(k.eng->e, &tg[of], &tg[other], peek_u32(k.jp.perm[other].p, local, k.stream), &c));
             return base_of[size_t(j)] + c;
         };
         look.count_b_le_a = [&](uint64_t i) { return count_le(1, base_a, base_b, i); };
@@ -552,11 +521,11 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
             most = std::max(most, k.n_proc);
             for (int s = 0; s < 2; ++s) {
                 uint32_t m = 0;
-                eng_ok(k, fqd_max_u32(k.eng->e, k.range[s].seq_len.p, k.range[s].n, &m));
+                engine_ok(k.eng->e, fqd_max_u32(k.eng->e, k.range[s].seq_len.p, k.range[s].n, &m));
                 max_len[s] = std::max(max_len[s], m);
                 if (!k.n_proc) continue;
                 k.d_off[s].reserve(k.n_proc); k.d_len[s].reserve(k.n_proc);
-                eng_ok(k, fqd_gather_seqs(k.eng->e, k.jp.pair[s].p, k.n_proc, k.range[s].seq_off.p, k.range[s].seq_len.p, k.d_off[s].p, k.d_len[s].p));
+                engine_ok(k.eng->e, fqd_gather_seqs(k.eng->e, k.jp.pair[s].p, k.n_proc, k.range[s].seq_off.p, k.range[s].seq_len.p, k.d_off[s].p, k.d_len[s].p));
             }
             k.jp.keep.reserve(std::max<uint64_t>(k.n_proc, 1));
         }
@@ -622,10 +591,7 @@ void HashDupRemover::run_unordered_multi(const std::string* in, const std::strin
     StageClock::report();
     if (bad) throw_unknown_base(bad_byte);
     summary_.total = total; summary_.duplicates = dups; summary_.unmatched = outcome.unmatched;
-    if (verbose_) {
-        std::cout << summary_.total << " valid read pairs processed, out of which " << summary_.duplicates << " duplicates were removed.\n";
-        std::cout << summary_.unmatched << " Non-matching entries from both files were skipped.\n";
-    }
+    if (verbose_) print_unordered_summary(summary_);
 }
 
 } // namespace fqdhost

@@ -50,9 +50,7 @@ void HashDupRemover::run_ordered(int S, const std::string* in, const std::string
         }
     }
 
-    hipStream_t stream = nullptr;
-    HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{stream};
+    StreamGuard stream;
     std::unique_ptr<EngineHandle> eng_holder;
     { StageClock::Scope t("main: engine create"); eng_holder = std::make_unique<EngineHandle>(S, tuning_.device, stream); }
     EngineHandle& eng = *eng_holder;
@@ -164,10 +162,7 @@ void HashDupRemover::run_ordered(int S, const std::string* in, const std::string
     }
 
     summary_.total = next_index; summary_.duplicates = st.duplicates; summary_.unmatched = 0;
-    if (verbose_) {
-        if (S == 1) std::cout << summary_.total << " reads processed, out of which " << summary_.duplicates << " duplicates were removed.\n";
-        else        std::cout << summary_.total << " read pairs processed, out of which " << summary_.duplicates << " duplicates were removed.\n";
-    }
+    if (verbose_) print_summary(S, summary_.total, summary_.duplicates);
 }
 
 void HashDupRemover::filterSE(const std::string& infile, const std::string& outfile)

@@ -61,52 +61,16 @@ void load_file(fqd_engine* e, hipStream_t stream, const std::string& name, Forma
     if (inflate_on_device()) {
         bool ok = false;
         try {
-            uint64_t text_bytes = 0;
-            if (has_gz_extension(name)) {
-                CompressedOnDevice packed;
-                if (fetch_bgzf(name, fetch_bytes, device, packed, &f)) ok = finish_on_device(e, stream, format, packed, f);
-                else {
-                    f.forget();
-                    ok = fetch_gzip_ordinary(name, fetch_bytes, device, f, text_bytes) && records_on_device(e, stream, format, text_bytes, f);
-                }
-            } else ok = fetch_plain(name, fetch_bytes, device, f, text_bytes) && records_on_device(e, stream, format, text_bytes, f);
+            Fetched got;
+            fetch_file(name, fetch_bytes, device, f, got);
+            ok = got.way != Fetched::None && cut_records(e, stream, format, got, f);
         } catch (const DeviceOutOfMemory&) { throw; }
         catch (const std::exception&) { ok = false; }
         if (ok) return;
         f.forget();
     }
-    hipStream_t up = nullptr;
-    HIP_OK(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
-    struct Guard { hipStream_t s; ~Guard() { (void)hipStreamDestroy(s); } } g{up};
-    Pinned<uint64_t> h_start, h_seq; Pinned<uint32_t> h_idl, h_sql, h_size;
-    Side side;
-    side.open_file(name, format, false, block_bytes);
-    side.prime(3, device);
-    while (side.available() > 0) {
-        PooledBlock* b = side.cur;
-        const size_t from = side.pos, nb = b->recs.size() - from;
-        const RecordRef* r = &b->recs[from];
-        const uint64_t text_lo = r[0].start, bytes = r[nb - 1].start + r[nb - 1].size - text_lo;
-        f.text.room_for(bytes + 64, up);
-        HIP_OK(hipMemcpyAsync(f.text.p + f.text.used, b->text.p + text_lo, bytes, hipMemcpyHostToDevice, up));
-        h_start.reserve(nb); h_seq.reserve(nb); h_idl.reserve(nb); h_sql.reserve(nb); h_size.reserve(nb);
-        for (size_t k = 0; k < nb; ++k) {
-            h_start.p[k] = f.text.used + (r[k].start - text_lo); h_seq.p[k] = h_start.p[k] + r[k].id_len;
-            h_idl.p[k] = r[k].id_len; h_sql.p[k] = r[k].seq_len; h_size.p[k] = r[k].size;
-        }
-        f.start.room_for(nb, up); f.seq_off.room_for(nb, up); f.id_len.room_for(nb, up); f.seq_len.room_for(nb, up); f.size.room_for(nb, up);
-        HIP_OK(hipMemcpyAsync(f.start.p + f.n, h_start.p, nb * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(f.seq_off.p + f.n, h_seq.p, nb * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(f.id_len.p + f.n, h_idl.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(f.seq_len.p + f.n, h_sql.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(f.size.p + f.n, h_size.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipStreamSynchronize(up));                    // the block and the staging arrays are reused
-        f.text.used += bytes;
-        f.start.used = f.seq_off.used = f.id_len.used = f.seq_len.used = f.size.used = f.n + nb;
-        f.n += nb;
-        side.pos += nb;
-    }
-    if (side.failed) { std::cerr << side.failure.diag; throw std::runtime_error(side.failure.what); }
+    StreamGuard up;
+    throw_if_set(append_file(name, format, false, device, block_bytes, f, up));
 }
 
 // ---- the ranged run ---------------------------------------------------------------------------------------------------
@@ -114,49 +78,22 @@ void load_file(fqd_engine* e, hipStream_t stream, const std::string& name, Forma
 // A block of the host reader in HBM: its text and, per record, the offsets (from the block's first record) and lengths.
 struct BlockOnDevice {
     Device<char> text; Device<uint64_t> start, seq_off; Device<uint32_t> id_len, seq_len, size;
-    Pinned<uint64_t> h_start, h_seq; Pinned<uint32_t> h_idl, h_sql, h_size;
+    RecordStaging staging;
     uint64_t bytes = 0;
     void upload(const PooledBlock* b, size_t from, size_t nb, bool with_text, hipStream_t up)
     {
         const RecordRef* r = &b->recs[from];
         const uint64_t text_lo = r[0].start;
         bytes = r[nb - 1].start + r[nb - 1].size - text_lo;
-        h_start.reserve(nb); h_seq.reserve(nb); h_idl.reserve(nb); h_sql.reserve(nb); h_size.reserve(nb);
-        for (size_t k = 0; k < nb; ++k) {
-            h_start.p[k] = r[k].start - text_lo; h_seq.p[k] = h_start.p[k] + r[k].id_len;
-            h_idl.p[k] = r[k].id_len; h_sql.p[k] = r[k].seq_len; h_size.p[k] = r[k].size;
-        }
+        staging.fill(r, nb, 0);
         start.reserve(nb); seq_off.reserve(nb); id_len.reserve(nb); seq_len.reserve(nb); size.reserve(nb);
         if (with_text) {
             text.reserve(bytes + 64);
             HIP_OK(hipMemcpyAsync(text.p, b->text.p + text_lo, bytes, hipMemcpyHostToDevice, up));
         }
-        HIP_OK(hipMemcpyAsync(start.p, h_start.p, nb * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(seq_off.p, h_seq.p, nb * sizeof(uint64_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(id_len.p, h_idl.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(seq_len.p, h_sql.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up));
-        HIP_OK(hipMemcpyAsync(size.p, h_size.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, up));
+        staging.copy_to(start.p, seq_off.p, id_len.p, seq_len.p, size.p, nb, up);
     }
 };
-
-// Every block of a file through the host reader, which reports what is wrong in the reference's words (load_file's second half).
-// body(block, first unread record, records, index of that record in the file) must be done with the block when it returns.
-template <class Body>
-uint64_t stream_blocks(const std::string& name, Format format, int device, size_t block_bytes, Body&& body)
-{
-    Side side;
-    side.open_file(name, format, false, block_bytes);
-    side.prime(3, device);
-    uint64_t base = 0;
-    while (side.available() > 0) {
-        const size_t from = side.pos, nb = side.cur->recs.size() - from;
-        body(side.cur, from, nb, base);
-        base += nb;
-        side.pos += nb;
-    }
-    if (side.failed) { std::cerr << side.failure.diag; throw std::runtime_error(side.failure.what); }
-    return base;
-}
 
 // What a range of `pairs` pairs and `bytes` bytes of record text (both files' together: each store is sized for its own
 // file's share, store_bytes below) needs in HBM while it is sorted, compared and written (DESIGN §9a has the derivation):
@@ -240,9 +177,7 @@ void SeqDupRemover::run(int S, const std::string* in, const std::string* out)
         throw std::runtime_error("--compare-seq runs on one GPU: FQD_DEVICES may name one device only");
     const int device = tuning_.devices.size() == 1 ? tuning_.devices[0] : tuning_.device;
     HIP_OK(hipSetDevice(device));
-    hipStream_t stream = nullptr;
-    HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{stream};
+    StreamGuard stream;
 
     // In core unless FQD_SEQ_RANGE_KB asks for ranges, plain inputs are plainly too large for the free HBM (their text and
     // two fifths of it again for the working set: what range_need comes to for records of 300 bytes), or the in-core
@@ -268,9 +203,7 @@ bool SeqDupRemover::run_in_core(int S, const std::string* in, const std::string*
     bool outputs_exist = false;
     try {
     EngineHandle eng(S, device, stream);
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(eng.e)); };
-    const size_t block_bytes = std::max<size_t>(1u << 20, tuning_.block_bytes);
-    const size_t fetch_bytes = std::max<size_t>(block_bytes, 64u << 20);
+    const size_t block_bytes = block_bytes_for(tuning_, 0), fetch_bytes = fetch_bytes_for(block_bytes, 0);   // (no --mem-limit term here)
 
     FileOnDevice dev[2];
     {
@@ -292,8 +225,8 @@ bool SeqDupRemover::run_in_core(int S, const std::string* in, const std::string*
     uint64_t heads = 0;
     {
         StageClock::Scope t("sequence: sort + compare on the GPU");
-        engine_ok(fqd_sort_seqs(eng.e, &mates[0], mate2, perm.p));
-        engine_ok(fqd_seq_heads(eng.e, &mates[0], mate2, perm.p, static_cast<int>(mode_), distance_, head.p, &heads));
+        engine_ok(eng.e, fqd_sort_seqs(eng.e, &mates[0], mate2, perm.p));
+        engine_ok(eng.e, fqd_seq_heads(eng.e, &mates[0], mate2, perm.p, static_cast<int>(mode_), distance_, head.p, &heads));
     }
     const uint64_t dups = n - heads;
     FileOnDevice* files[2] = {&dev[0], &dev[1]};
@@ -322,10 +255,7 @@ bool SeqDupRemover::run_in_core(int S, const std::string* in, const std::string*
     if (tuning_.leave_memory_to_exit) g_leave_memory_to_exit = true;
     StageClock::report();
     summary_.total = n; summary_.duplicates = dups; summary_.unmatched = 0;
-    if (verbose_) {                                                      // seq_dup_remover.hpp:107-108,216-217
-        if (S == 1) std::cout << n << " reads processed, out of which " << dups << " duplicates were removed.\n";
-        else        std::cout << n << " read pairs processed, out of which " << dups << " duplicates were removed.\n";
-    }
+    if (verbose_) print_summary(S, n, dups);
     return true;
     } catch (const DeviceOutOfMemory&) {
         if (outputs_exist) throw;
@@ -347,7 +277,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
     if (keep_best_ && mode_ != CompareSeq::Tight)
         throw std::runtime_error("FQD_SEQ_KEEP=best with --compare-seq loose or tail-hamming needs the whole input in GPU memory at once; "
                                  "this run goes through it in ranges of the sort order (FQD_SEQ_RANGE_KB is set, or the input does not fit)");
-    const size_t block_bytes = std::max<size_t>(1u << 20, tuning_.block_bytes);
+    const size_t block_bytes = block_bytes_for(tuning_, 0);
     BlockOnDevice blk;
     Device<uint32_t> range_of;
     std::vector<fqd_seq_range> table;
@@ -356,12 +286,12 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
     {   // ---- pass A: a key and a size per pair; everything that can refuse the run, before any output exists ----
         StageClock::Scope t("sequence: pass A, keys and sizes of every pair");
         EngineHandle eng(S, device, stream);
-        auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(eng.e)); };
         GrowDevice<uint64_t> key; GrowDevice<uint32_t> bytes, bytes0;     // bytes0: the first file's part of a pair's bytes
         uint64_t count[2] = {0, 0}, first_with[10], record_bytes = 0;
         for (uint64_t& f : first_with) f = ~0ull;
         for (int s = 0; s < S; ++s) {
-            count[s] = stream_blocks(in[s], format_, device, block_bytes, [&](const PooledBlock* b, size_t from, size_t nb, uint64_t base) {
+            throw_if_set(stream_blocks(in[s], format_, false, device, block_bytes, [&](const PooledBlock* b, size_t from, size_t nb, uint64_t base) {
+                count[s] = base + nb;
                 // the second file's records beyond the first file's have no partner: they are counted, nothing else
                 const uint64_t take = s == 0 ? nb : (base < count[0] ? std::min<uint64_t>(nb, count[0] - base) : 0);
                 if (take == 0) return;
@@ -372,7 +302,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
                 }
                 const fqd_tags tags{reinterpret_cast<const uint8_t*>(blk.text.p), blk.seq_off.p, blk.seq_len.p, take};
                 fqd_seq_block_info info;
-                engine_ok(fqd_seq_prefix_keys(eng.e, &tags, nullptr, blk.size.p, nullptr, s == 1, s == 0 ? key.p + base : nullptr,
+                engine_ok(eng.e, fqd_seq_prefix_keys(eng.e, &tags, nullptr, blk.size.p, nullptr, s == 1, s == 0 ? key.p + base : nullptr,
                                               bytes.p + base, &info));                          // waits for the stream: the block is free again
                 if (s == 0) {
                     if (S == 2) {
@@ -384,7 +314,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
                 }
                 for (int c = 0; c < 10; ++c) if (info.first_with[c] != ~0ull) first_with[c] = std::min(first_with[c], base + info.first_with[c]);
                 record_bytes += info.record_bytes;
-            });
+            }));
             if (count[s] == 0) throw std::runtime_error("Not enough memory to read a single object!");   // bufferedinput.hpp:81-84
         }
         n = S == 2 ? std::min(count[0], count[1]) : count[0];              // pairs end with the shorter file (sort_buckets)
@@ -415,7 +345,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
         uint32_t R = 0, room = 4096;
         for (;;) {
             table.resize(room);
-            engine_ok(fqd_seq_plan_ranges(eng.e, key.p, bytes.p, S == 2 ? bytes0.p : nullptr, n, target, range_of.p, table.data(), room, &R));
+            engine_ok(eng.e, fqd_seq_plan_ranges(eng.e, key.p, bytes.p, S == 2 ? bytes0.p : nullptr, n, target, range_of.p, table.data(), room, &R));
             if (R <= room) break;
             room = R;
         }
@@ -444,7 +374,6 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
 
     // ---- pass B: range after range ----
     EngineHandle eng(S, device, stream);
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(eng.e)); };
     const bool carries = mode_ != CompareSeq::Tight;          // tight: nothing crosses a cut (fqd_seq_range_core.hpp)
     Carry carry;
     FileOnDevice store[2];
@@ -503,19 +432,19 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
                     HIP_OK(hipStreamSynchronize(stream));
                     f.text.used = carry.size[s]; f.n = 1;
                 }
-                stream_blocks(in[s], format_, device, block_bytes, [&](const PooledBlock* b, size_t from, size_t nb, uint64_t base) {
+                throw_if_set(stream_blocks(in[s], format_, false, device, block_bytes, [&](const PooledBlock* b, size_t from, size_t nb, uint64_t base) {
                     if (base >= n) return;                       // behind the last pair
                     const uint64_t take = std::min<uint64_t>(nb, n - base);
                     keep.reserve(take);
                     uint64_t kept = 0, moved = 0;
-                    engine_ok(fqd_range_keep(eng.e, range_of.p + base, take, r, keep.p, &kept));
+                    engine_ok(eng.e, fqd_range_keep(eng.e, range_of.p + base, take, r, keep.p, &kept));
                     if (kept == 0) return;
                     if (f.n + kept > want) throw std::runtime_error("--compare-seq: an input changed between the passes of the ranged run");
                     blk.upload(b, from, take, true, stream);
                     src_off.reserve(take); dst_off.reserve(take + 1); len.reserve(take);
-                    engine_ok(fqd_output_plan(eng.e, keep.p, nullptr, take, blk.start.p, blk.size.p, src_off.p, len.p, dst_off.p, &moved));
+                    engine_ok(eng.e, fqd_output_plan(eng.e, keep.p, nullptr, take, blk.start.p, blk.size.p, src_off.p, len.p, dst_off.p, &moved));
                     if (f.text.used + moved + 64 > f.text.cap) throw std::runtime_error("--compare-seq: an input changed between the passes of the ranged run");
-                    engine_ok(fqd_copy_spans(eng.e, reinterpret_cast<const uint8_t*>(blk.text.p), src_off.p, len.p, take,
+                    engine_ok(eng.e, fqd_copy_spans(eng.e, reinterpret_cast<const uint8_t*>(blk.text.p), src_off.p, len.p, take,
                                              reinterpret_cast<uint8_t*>(f.text.p) + f.text.used, dst_off.p));
                     // the kept records' places in the store, in input order (what fqd_output_plan's dst_off says, re-based)
                     h_keep.reserve(take);
@@ -537,7 +466,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
                     HIP_OK(hipMemcpyAsync(f.size.p + f.n, c_size.p, kept * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
                     HIP_OK(hipStreamSynchronize(stream));        // the block and the staging arrays are reused
                     f.text.used = at; f.n += kept;
-                });
+                }));
                 f.start.used = f.seq_off.used = f.id_len.used = f.seq_len.used = f.size.used = f.n;
                 if (f.n != want) throw std::runtime_error("--compare-seq: an input changed between the passes of the ranged run");
             }
@@ -551,9 +480,9 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
         uint64_t heads = 0;
         {
             StageClock::Scope t("sequence: sort + compare on the GPU");
-            engine_ok(fqd_sort_seqs(eng.e, &mates[0], mate2, perm.p));
+            engine_ok(eng.e, fqd_sort_seqs(eng.e, &mates[0], mate2, perm.p));
             if (phantom && peek_u32(perm.p, 0, stream) != 0) throw std::runtime_error("--compare-seq: internal error (the carried record is not the first of its range)");
-            engine_ok(fqd_seq_heads(eng.e, &mates[0], mate2, perm.p, static_cast<int>(mode_), distance_, head.p, &heads));
+            engine_ok(eng.e, fqd_seq_heads(eng.e, &mates[0], mate2, perm.p, static_cast<int>(mode_), distance_, head.p, &heads));
             if (phantom) {                                       // written, listed and counted in its own range
                 HIP_OK(hipMemsetAsync(head.p, 0, 1, stream));
                 HIP_OK(hipStreamSynchronize(stream));
@@ -619,10 +548,7 @@ void SeqDupRemover::run_ranged(int S, const std::string* in, const std::string* 
         std::cerr << "sequence: best-quality pick, " << moved_clusters << " of " << all_clusters << " clusters changed\n";
     StageClock::report();
     summary_.total = total; summary_.duplicates = total_dups; summary_.unmatched = 0;
-    if (verbose_) {                                                      // seq_dup_remover.hpp:107-108,216-217
-        if (S == 1) std::cout << total << " reads processed, out of which " << total_dups << " duplicates were removed.\n";
-        else        std::cout << total << " read pairs processed, out of which " << total_dups << " duplicates were removed.\n";
-    }
+    if (verbose_) print_summary(S, total, total_dups);
 }
 
 } // namespace fqdhost

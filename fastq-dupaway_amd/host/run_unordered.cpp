@@ -18,7 +18,6 @@ uint32_t peek_u32(const uint32_t* d, uint64_t k, hipStream_t s)
 
 void join_and_dedup(fqd_engine* e, hipStream_t stream, const DeviceSide (&side)[2], bool tail_rule, JoinedPairs& jp)
 {
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(e)); };
     if (side[0].n >= 0x80000000ull || side[1].n >= 0x80000000ull)
         throw std::runtime_error("--unordered: more than 2^31-1 records in one file");
     const uint64_t max_pairs = std::min(side[0].n, side[1].n);
@@ -30,7 +29,7 @@ void join_and_dedup(fqd_engine* e, hipStream_t stream, const DeviceSide (&side)[
         StageClock::Scope t("unordered: tag join on the GPU");
         for (int s = 0; s < 2; ++s) { jp.perm[s].reserve(side[s].n); jp.match[s].reserve(side[s].n); jp.pair[s].reserve(max_pairs); }
         const fqd_join jo{jp.perm[0].p, jp.perm[1].p, jp.match[0].p, jp.match[1].p, jp.pair[0].p, jp.pair[1].p, &n_pairs};
-        engine_ok(fqd_join_tags(e, &tags[0], &tags[1], &jo));
+        engine_ok(e, fqd_join_tags(e, &tags[0], &tags[1], &jo));
         JoinLookup look;
         look.n = side[0].n; look.m = side[1].n; look.n_pairs = n_pairs;
         look.match_a = [&](uint64_t k) { return peek_u32(jp.match[0].p, k, stream); };
@@ -39,7 +38,7 @@ void join_and_dedup(fqd_engine* e, hipStream_t stream, const DeviceSide (&side)[
         auto count_le = [&](int of, uint64_t pos_other) {
             const int other = 1 - of;
             uint64_t c = 0;
-            engine_ok(fqd_count_tags_le(e, &tags[of], &tags[other], peek_u32(jp.perm[other].p, pos_other, stream), &c));
+            engine_ok(e, fqd_count_tags_le(e, &tags[of], &tags[other], peek_u32(jp.perm[other].p, pos_other, stream), &c));
             return c;
         };
         look.count_b_le_a = [&](uint64_t i) { return count_le(1, i); };
@@ -54,7 +53,7 @@ void join_and_dedup(fqd_engine* e, hipStream_t stream, const DeviceSide (&side)[
     Device<uint64_t>* d_off = jp.seq_off; Device<uint32_t>* d_len = jp.seq_len;
     for (int s = 0; s < 2; ++s) {
         d_off[s].reserve(n_proc); d_len[s].reserve(n_proc);
-        engine_ok(fqd_gather_seqs(e, jp.pair[s].p, n_proc, side[s].seq_off, side[s].seq_len, d_off[s].p, d_len[s].p));
+        engine_ok(e, fqd_gather_seqs(e, jp.pair[s].p, n_proc, side[s].seq_off, side[s].seq_len, d_off[s].p, d_len[s].p));
     }
     jp.keep.reserve(n_proc);
     const size_t kBatch = 16u << 20;
@@ -71,7 +70,7 @@ void join_and_dedup(fqd_engine* e, hipStream_t stream, const DeviceSide (&side)[
         uint64_t rec; uint32_t sg2, pos;
         fqd_bad_base(e, &rec, &sg2, &pos, &jp.bad_byte);
         jp.bad = true; jp.written_below = std::min<uint64_t>(rec, n_proc);
-    } else engine_ok(rc);
+    } else engine_ok(e, rc);
 }
 
 bool is_regular_file(const std::string& name, uint64_t& size)
@@ -141,18 +140,15 @@ void HashDupRemover::run_unordered_in_memory(const std::string* in, const std::s
         second.join();
         for (int s = 0; s < 2; ++s) {
             if (err[s]) std::rethrow_exception(err[s]);
-            if (file[s].failure.set) { std::cerr << file[s].failure.diag; throw std::runtime_error(file[s].failure.what); }
+            throw_if_set(file[s].failure);
         }
     }
 
     // 2. outputs are opened after the sort phase (hpp:265-266)
     OutputFile sink0(out[0]), sink1(out[1]);
 
-    hipStream_t stream = nullptr;
-    HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{stream};
+    StreamGuard stream;
     EngineHandle eng(2, tuning_.device, stream);
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(eng.e)); };
 
     const uint64_t n_rec[2] = {file[0].recs.size(), file[1].recs.size()};
 
@@ -170,7 +166,7 @@ void HashDupRemover::run_unordered_in_memory(const std::string* in, const std::s
         if (need > free_b)
             throw std::runtime_error("--unordered: the two inputs (" + std::to_string((text_bytes[0] + text_bytes[1]) >> 20) +
                                      " MiB of text) do not fit in GPU memory beside the join and the set");
-        Pinned<uint64_t> h_off, h_ids; Pinned<uint32_t> h_idl, h_sql;
+        Pinned<uint64_t> h_off, h_ids; Pinned<uint32_t> h_id_len, h_seq_len;
         for (int s = 0; s < 2; ++s) {
             d_text[s].reserve(text_bytes[s] + 64);
             std::vector<uint64_t> chunk_base;
@@ -181,23 +177,23 @@ void HashDupRemover::run_unordered_in_memory(const std::string* in, const std::s
                 at += file[s].chunk_used[c];
             }
             const size_t n = n_rec[s];
-            h_off.reserve(n); h_ids.reserve(n); h_idl.reserve(n); h_sql.reserve(n);
+            h_off.reserve(n); h_ids.reserve(n); h_id_len.reserve(n); h_seq_len.reserve(n);
             const unsigned parts = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(host_threads(), n >> 16)));
             run_parts(parts, [&](unsigned p) {
                 for (size_t k = n / parts * p, e = p + 1 == parts ? n : n / parts * (p + 1); k < e; ++k) {
                     const FileRecord& r = file[s].recs[k];
                     h_ids.p[k] = chunk_base[r.chunk] + static_cast<uint64_t>(r.text - file[s].chunks[r.chunk]->p);
                     h_off.p[k] = h_ids.p[k] + r.id_len;
-                    h_idl.p[k] = r.id_len; h_sql.p[k] = r.seq_len;
+                    h_id_len.p[k] = r.id_len; h_seq_len.p[k] = r.seq_len;
                 }
             });
             d_seq_off[s].reserve(n); d_id_len[s].reserve(n); d_seq_len[s].reserve(n);
             d_id_start[s].reserve(n); d_tag_off[s].reserve(n); d_tag_len[s].reserve(n);
             HIP_OK(hipMemcpyAsync(d_seq_off[s].p, h_off.p, n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            HIP_OK(hipMemcpyAsync(d_id_len[s].p, h_idl.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            HIP_OK(hipMemcpyAsync(d_seq_len[s].p, h_sql.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIP_OK(hipMemcpyAsync(d_id_len[s].p, h_id_len.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIP_OK(hipMemcpyAsync(d_seq_len[s].p, h_seq_len.p, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
             HIP_OK(hipMemcpyAsync(d_id_start[s].p, h_ids.p, n * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-            engine_ok(fqd_extract_tags(eng.e, reinterpret_cast<const uint8_t*>(d_text[s].p), d_id_start[s].p, d_id_len[s].p, n,
+            engine_ok(eng.e, fqd_extract_tags(eng.e, reinterpret_cast<const uint8_t*>(d_text[s].p), d_id_start[s].p, d_id_len[s].p, n,
                                        d_tag_off[s].p, d_tag_len[s].p));
             HIP_OK(hipStreamSynchronize(stream));                // the pinned staging arrays are reused by file 2
         }
@@ -245,23 +241,17 @@ void HashDupRemover::run_unordered_in_memory(const std::string* in, const std::s
     StageClock::report();
     if (jp.bad) throw_unknown_base(jp.bad_byte);
     summary_.total = n_proc; summary_.duplicates = dups; summary_.unmatched = jp.unmatched;
-    if (verbose_) {
-        std::cout << summary_.total << " valid read pairs processed, out of which " << summary_.duplicates << " duplicates were removed.\n";
-        std::cout << summary_.unmatched << " Non-matching entries from both files were skipped.\n";
-    }
+    if (verbose_) print_unordered_summary(summary_);
 }
 
 // The bounded-memory way (see run_unordered).
 void HashDupRemover::run_unordered_streaming(const std::string* in, const std::string* out)
 {
     HIP_OK(hipSetDevice(tuning_.device));
-    hipStream_t stream = nullptr;
-    HIP_OK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{stream};
+    StreamGuard stream;
     EngineHandle eng(2, tuning_.device, stream);
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(eng.e)); };
     // pinned blocks in flight: three per file at most, sized so that they stay well inside the limit
-    const size_t block_bytes = std::max<size_t>(1u << 20, std::min<size_t>(tuning_.block_bytes, static_cast<size_t>(memlimit_ > 0 ? memlimit_ / 16 : tuning_.block_bytes)));
+    const size_t block_bytes = block_bytes_for(tuning_, memlimit_);
 
     struct FileOnDevice {
         GrowDevice<char> tags, seqs;
@@ -305,9 +295,9 @@ void HashDupRemover::run_unordered_streaming(const std::string* in, const std::s
                 HIP_OK(hipMemcpyAsync(f.seq_len.p + f.n, h_seq_len.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
                 HIP_OK(hipMemcpyAsync(f.tag_len.p + f.n, h_tag_len.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
                 HIP_OK(hipMemcpyAsync(f.size.p + f.n, h_size.p, nb * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                engine_ok(fqd_copy_spans(eng.e, reinterpret_cast<const uint8_t*>(d_block.p), d_src_seq.p, f.seq_len.p + f.n, nb,
+                engine_ok(eng.e, fqd_copy_spans(eng.e, reinterpret_cast<const uint8_t*>(d_block.p), d_src_seq.p, f.seq_len.p + f.n, nb,
                                          reinterpret_cast<uint8_t*>(f.seqs.p), f.seq_off.p + f.n));
-                engine_ok(fqd_copy_spans(eng.e, reinterpret_cast<const uint8_t*>(d_block.p), d_src_tag.p, f.tag_len.p + f.n, nb,
+                engine_ok(eng.e, fqd_copy_spans(eng.e, reinterpret_cast<const uint8_t*>(d_block.p), d_src_tag.p, f.tag_len.p + f.n, nb,
                                          reinterpret_cast<uint8_t*>(f.tags.p), f.tag_off.p + f.n));
                 HIP_OK(hipStreamSynchronize(stream));            // the block and the staging arrays are reused
                 f.seqs.used = seq_at; f.tags.used = tag_at;
@@ -315,7 +305,7 @@ void HashDupRemover::run_unordered_streaming(const std::string* in, const std::s
                 f.n += nb;
                 side.pos += nb;
             }
-            if (side.failed) { std::cerr << side.failure.diag; throw std::runtime_error(side.failure.what); }
+            throw_if_set(side.failure);
         }
     }
 
@@ -345,7 +335,7 @@ void HashDupRemover::run_unordered_streaming(const std::string* in, const std::s
     for (int s = 0; s < 2; ++s) {
         d_dest[s].reserve(dev[s].n);
         if (dev[s].n) HIP_OK(hipMemsetAsync(d_dest[s].p, 0xFF, dev[s].n * sizeof(uint64_t), stream));
-        engine_ok(fqd_output_offsets(eng.e, jp.keep.p, jp.pair[s].p, upto, dev[s].size.p, d_dest[s].p, &out_bytes[s]));
+        engine_ok(eng.e, fqd_output_offsets(eng.e, jp.keep.p, jp.pair[s].p, upto, dev[s].size.p, d_dest[s].p, &out_bytes[s]));
     }
 
     // ---- pass 2: every surviving record to its place ------------------------------------------------
@@ -356,9 +346,7 @@ void HashDupRemover::run_unordered_streaming(const std::string* in, const std::s
         const std::string tmp = out_bytes[0] > window || out_bytes[1] > window ? std::string(tempdir_->name()) : std::string();
         run_parts(2, [&](unsigned s) {
             (void)hipSetDevice(tuning_.device);
-            hipStream_t st2 = nullptr;
-            HIP_OK(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-            struct Guard { hipStream_t s; ~Guard() { (void)hipStreamDestroy(s); } } g{st2};
+            StreamGuard st2;
             const uint64_t total = out_bytes[s];
             const size_t n_win = static_cast<size_t>((total + window - 1) / window);
             // windows of the output: window w holds the records that START in [w*window, (w+1)*window); the
@@ -420,10 +408,7 @@ void HashDupRemover::run_unordered_streaming(const std::string* in, const std::s
     StageClock::report();
     if (jp.bad) throw_unknown_base(jp.bad_byte);
     summary_.total = n_proc; summary_.duplicates = dups; summary_.unmatched = jp.unmatched;
-    if (verbose_) {
-        std::cout << summary_.total << " valid read pairs processed, out of which " << summary_.duplicates << " duplicates were removed.\n";
-        std::cout << summary_.unmatched << " Non-matching entries from both files were skipped.\n";
-    }
+    if (verbose_) print_unordered_summary(summary_);
 }
 
 } // namespace fqdhost

@@ -73,14 +73,13 @@ uint32_t device_deflate_effort()
 void plan_survivors(fqd_engine* e, int S, FileOnDevice* const* file, const uint32_t* const* idx, const uint8_t* keep, uint64_t upto,
                            const bool* gz_out, long long memlimit, SurvivorBuffers& b)
 {
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(e)); };
     b.window = std::max<uint64_t>(4u << 20, static_cast<uint64_t>(memlimit > 0 ? memlimit : (2ll << 30)) / 16);   // bytes per buffer, two per file
     if (const char* v = std::getenv("FQD_STREAM_WINDOW_KB")) { const long kb = std::atol(v); if (kb > 0) b.window = static_cast<uint64_t>(kb) << 10; }
     b.roomy = b.window + b.window / 4;                      // the most a window may hold
     for (int s = 0; s < S; ++s) {
         SurvivorBuffers::PerFile& o = b.f[s];
         o.src_off.reserve(upto); o.dst_off.reserve(upto + 1); o.len.reserve(upto);
-        engine_ok(fqd_output_plan(e, keep, idx[s], upto, file[s]->start.p, file[s]->size.p, o.src_off.p, o.len.p, o.dst_off.p, &o.total));
+        engine_ok<DeviceError>(e, fqd_output_plan(e, keep, idx[s], upto, file[s]->start.p, file[s]->size.p, o.src_off.p, o.len.p, o.dst_off.p, &o.total));
         o.on_device = gz_out[s] && deflate_on_device();
         // every buffer is sized once, for the largest window the writer lets through (a single record larger than that is the
         // one case that grows them later): a window a little larger than all before it must not cost a new pinned allocation
@@ -98,7 +97,6 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
                             const uint8_t* keep, uint64_t upto, uint64_t dups, OutputFile* const* sinks, Format format, long long memlimit,
                             bool close_sinks, SurvivorBuffers* planned)
 {
-    auto engine_ok = [&](int rc) { if (rc != FQD_OK) throw std::runtime_error(std::string("GPU engine: ") + fqd_last_error(e)); };
     SurvivorBuffers own;
     if (!planned || !planned->planned) {
         bool gz_out[2] = {false, false};
@@ -193,7 +191,7 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
                     d_win.reserve(room + 64);
                     o[s].buf[*id].reserve((o[s].on_device ? std::max<uint64_t>(room / 2, 1u << 20) : room) + 64);
                     // dst_off is absolute in the output: the window's buffer starts `lo` bytes in
-                    engine_ok(fqd_copy_spans(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), o[s].src_off.p + at[s], o[s].len.p + at[s], take,
+                    engine_ok(e, fqd_copy_spans(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), o[s].src_off.p + at[s], o[s].len.p + at[s], take,
                                              reinterpret_cast<uint8_t*>(d_win.p) - lo, o[s].dst_off.p + at[s]));
                     uint64_t out_bytes = bytes;
                     const char* from = d_win.p;
@@ -201,7 +199,7 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
                         Device<char>& d_members = o[s].d_members[*id];
                         const uint64_t cap = fqd_bgzf_bound(room);
                         d_members.reserve(cap);
-                        engine_ok(fqd_bgzf_deflate_ex(e, reinterpret_cast<const uint8_t*>(d_win.p), bytes, lines_per_record, effort,
+                        engine_ok(e, fqd_bgzf_deflate_ex(e, reinterpret_cast<const uint8_t*>(d_win.p), bytes, lines_per_record, effort,
                                                       reinterpret_cast<uint8_t*>(d_members.p), cap, &out_bytes));
                         from = d_members.p;
                         o[s].buf[*id].reserve(out_bytes + 64);           // (text that does not shrink to half)

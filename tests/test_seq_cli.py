@@ -224,6 +224,52 @@ def test_cli_fuzz_against_restatement(exe, tmp_path, case):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("case", ["flipped_bit", "bad_record", "good"])
+def test_bgzf_input_falls_back_to_the_host_reader(exe, tmp_path, case):
+    """A BGZF input of the sequence run goes to HBM as it lies on disk and is inflated and cut there; a damaged member
+    or a malformed record sends the file to the host reader, which says what is wrong before any output exists.
+    Either way: exactly what the run with FQD_GUNZIP_DEVICE=0 says and leaves behind."""
+    from inflate_cases import bgzf
+    rng = random.Random(5)
+    pool = ["".join(rng.choice("ACGT") for _ in range(rng.randrange(40, 91))) for _ in range(150)]
+    recs = []
+    for k in range(600):
+        s = list(rng.choice(pool))
+        if rng.random() < 0.3:                              # a substitution or two near the end (tail-hamming)
+            for _ in range(rng.randrange(1, 3)):
+                s[rng.randrange(len(s) // 2, len(s))] = rng.choice("ACGT")
+        recs.append(f"@r{k} x\n{''.join(s)}\n+\n{chr(33 + k % 90) * len(s)}\n".encode())
+    text = b"".join(recs)
+    if case == "bad_record":
+        cut = text.index(b"\n@", len(text) // 2) + 1
+        text = text[:cut] + b"x" + text[cut + 1:]           # a record that does not start with '@'
+    z = bgzf(text, level=1)
+    if case == "flipped_bit":
+        z = bytearray(z); z[len(z) // 2] ^= 0x10; z = bytes(z)
+    src = tmp_path / "in.fq.gz"
+    src.write_bytes(z)
+    runs = {}
+    for gunzip in ("1", "0"):
+        out = tmp_path / f"out_{gunzip}.fq"
+        r = run(exe, "-i", src, "-o", out, "--compare-seq", "tail-hamming", "--distance", 2, "-v",
+                env={"FQD_HOST_TIMING": "1", "FQD_GUNZIP_DEVICE": gunzip, "FQD_PGZIP_MIN_MB": "0" if gunzip == "1" else "8"})
+        said = "\n".join(l for l in r.stderr.splitlines() if "[host timing]" not in l)
+        runs[gunzip] = (r.returncode, r.stdout, said, out.read_bytes() if out.exists() else None)
+    assert runs["1"] == runs["0"]
+    rc, stdout, said, got = runs["1"]
+    if case == "good":
+        assert rc == 0, said
+        exp_out, _, total, dups = ref.dedup([text], fasta=False, mode=ref.MODES["tail-hamming"], distance=2)
+        assert dups > 0
+        assert stdout == ref.verbose_line(total, dups, False)
+        check_same(got, exp_out[0], False)
+    else:
+        assert rc != 0
+        assert ("corrupt or truncated" if case == "flipped_bit" else "Invalid record start character: x") in said
+        assert got is None                                  # the reference sorts before it opens an output
+
+
+@pytest.mark.gpu
 def test_empty_input_is_refused(exe, tmp_path):
     src = tmp_path / "in.fq"; src.write_bytes(b"")
     out = tmp_path / "o.fq"
