@@ -385,6 +385,32 @@ class Engine:
         self._check(self._L.fqd_count_tags_le(self._h, C.byref(tt), C.byref(to), other_index, C.byref(count)))
         return int(count.value)
 
+    # -- `--unordered` over several GPUs: records dealt by tag range (splitters) ------------------
+    def sample_tags(self, t, n_samples: int, stride: int, out_bytes, out_len):
+        """Sample k = the tag of record k * n / n_samples of t = (bytes, offsets, lengths, n), cut to `stride` bytes, at
+        out_bytes + k * stride; out_len[k] (uint32) = its length.  Only launches."""
+        tt = self._tags(*t)
+        self._check(self._L.fqd_sample_tags(self._h, C.byref(tt), n_samples, stride, self._p(out_bytes), self._p(out_len)))
+
+    def classify_tags(self, t, split_bytes, split_stride: int, split_len, n_split: int, range_out):
+        """range_out[i] (uint32) = number of the n_split ascending splitters (split_bytes + k * split_stride, split_len[k])
+        that are < tag i of t = (bytes, offsets, lengths, n).  Only launches."""
+        tt = self._tags(*t)
+        self._check(self._L.fqd_classify_tags(self._h, C.byref(tt), self._p(split_bytes), split_stride, self._p(split_len), n_split,
+                                              self._p(range_out)))
+
+    def range_keep(self, range_, n: int, which: int, keep) -> int:
+        """keep[i] = (range_[i] == which) as 0 / 1 bytes; returns how many are set (the call drains the stream)."""
+        count = C.c_uint64(0)
+        self._check(self._L.fqd_range_keep(self._h, self._p(range_), n, which, self._p(keep), C.byref(count)))
+        return int(count.value)
+
+    def max_u32(self, values, n: int) -> int:
+        """The largest of n uint32 values, 0 for none (the call drains the stream)."""
+        m = C.c_uint32(0)
+        self._check(self._L.fqd_max_u32(self._h, self._p(values), n, C.byref(m)))
+        return int(m.value)
+
     def output_offsets(self, keep, idx, n: int, sizes, dest) -> int:
         total = C.c_uint64(0)
         self._check(self._L.fqd_output_offsets(self._h, self._p(keep), self._p(idx), n, self._p(sizes), self._p(dest), C.byref(total)))
