@@ -10,6 +10,7 @@ import pytest
 
 from bgzf_cases import fasta_text, fastq_text
 from inflate_cases import bgzf, cases
+from record_reference import numpy_records
 
 pytestmark = pytest.mark.gpu
 
@@ -130,14 +131,6 @@ def test_deflate_then_inflate_600_mb_on_the_device(eng):
     want = torch.arange(n, device=dev, dtype=torch.int64) * R
     assert ok and torch.equal(start, want) and torch.equal(seq_off, want + 18)
     assert bool((id_len == 18).all()) and bool((seq_len == L).all()) and bool((sz == R).all())
-
-
-def numpy_records(data: bytes, k: int):
-    nl = np.flatnonzero(np.frombuffer(data, dtype=np.uint8) == 10)
-    n = len(nl) // k
-    ends = nl[: n * k].reshape(n, k)
-    start = np.concatenate([[0], ends[:-1, -1] + 1]) if n else np.zeros(0, np.int64)
-    return start, ends[:, 0] + 1, ends[:, 0] - start + 1, ends[:, 1] - ends[:, 0] - 1, ends[:, -1] - start + 1
 
 
 @pytest.mark.parametrize("kind", ["fastq", "fastq_ragged", "fasta", "one_record"])
