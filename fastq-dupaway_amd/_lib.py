@@ -143,6 +143,7 @@ def load_library():
     L.fqd_owners.argtypes = [vp, vp, vp, u64, vp]
     L.fqd_group_owners.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
     L.fqd_heads_to_keep.argtypes = [vp, vp, vp, u64, vp]
+    L.fqd_canonical_reads.argtypes = [vp, C.POINTER(ReadsDesc), u64, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

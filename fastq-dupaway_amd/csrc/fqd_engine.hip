@@ -606,6 +606,7 @@ bool seg_is_uniform(const fqd_reads& r) { return r.offsets == nullptr && r.lengt
 // ---- what fqd_join.hip needs from an engine (same library, not exported) -----------------
 FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e) { return e->stream; }
 FQD_HIDDEN int fqd_internal_device(fqd_engine* e) { return e->device; }
+FQD_HIDDEN int fqd_internal_segments(fqd_engine* e) { return e->S; }
 FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg) { return e->fail(code, msg); }
 FQD_HIDDEN uint64_t* fqd_internal_state(fqd_engine* e) { return e->d_state; }
 FQD_HIDDEN int fqd_internal_scratch(fqd_engine* e, int which, size_t bytes, void** out)

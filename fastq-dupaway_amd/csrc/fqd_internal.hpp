@@ -14,6 +14,7 @@
 #define FQD_HIDDEN __attribute__((visibility("hidden")))
 FQD_HIDDEN hipStream_t fqd_internal_stream(fqd_engine* e);
 FQD_HIDDEN int fqd_internal_device(fqd_engine* e);
+FQD_HIDDEN int fqd_internal_segments(fqd_engine* e);      // fqd_config.segments: 1 or 2
 FQD_HIDDEN int fqd_internal_fail(fqd_engine* e, int code, const char* msg);
 FQD_HIDDEN uint64_t* fqd_internal_state(fqd_engine* e);
 FQD_HIDDEN int fqd_internal_scratch(fqd_engine* e, int which, size_t bytes, void** out);

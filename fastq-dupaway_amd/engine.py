@@ -314,6 +314,20 @@ class Engine:
         """keep[perm[k]] = head[k]."""
         self._check(self._L.fqd_heads_to_keep(self._h, self._p(perm), self._p(head), n, self._p(keep)))
 
+    # -- FQD_FAST_STRAND=both (csrc/fqd_strand.hip) ------------------------------------------------
+    def canonical_reads(self, segs: Sequence[Reads], n: int, out, out_off0, out_len0, flipped, out_off1=None, out_len1=None,
+                        out_capacity: Optional[int] = None, count: bool = False) -> Optional[int]:
+        """The n records of segs (device memory) in the orientation they are keyed in, packed back to back into out (device
+        bytes; out_capacity defaults to out.numel()): Reads(out, out_off0, out_len0) and, for pairs, Reads(out, out_off1,
+        out_len1) go into submit; flipped[i] = 1 where record i was turned.  count: wait and return how many were."""
+        if len(segs) != self.segments:
+            raise ValueError(f"engine has {self.segments} mate(s) per record, got {len(segs)}")
+        turned = C.c_uint64(0)
+        cap = out.numel() if out_capacity is None else out_capacity
+        self._check(self._L.fqd_canonical_reads(self._h, self._desc(segs), n, self._p(out), cap, self._p(out_off0), self._p(out_len0),
+                                                self._p(out_off1), self._p(out_len1), self._p(flipped), C.byref(turned) if count else None))
+        return int(turned.value) if count else None
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

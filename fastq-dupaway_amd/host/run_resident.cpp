@@ -25,28 +25,44 @@ bool fast_clusters()
     return v && std::atoi(v) != 0;
 }
 
+// FQD_FAST_STRAND=given|both: whether `--fast` tells the two strands of a fragment apart.  given (and unset): a read is
+// what its bytes are, as in the reference; both: a read and its reverse complement — a pair and the pair with its mates
+// exchanged — are one key (csrc/fqd_strand_core.hpp).  Read here and nowhere else.
+bool fast_both_strands()
+{
+    const char* v = std::getenv("FQD_FAST_STRAND");
+    if (!v || std::strcmp(v, "given") == 0) return false;
+    if (std::strcmp(v, "both") == 0) return true;
+    throw std::runtime_error(std::string("FQD_FAST_STRAND must be 'given' or 'both', not '") + v + "'");
+}
+
 } // namespace detail
 
 namespace {
 
 // Why a run with FQD_FAST_KEEP=best or FQD_FAST_CLUSTERS=1 ends: these modes need every record's flag to stay open until
 // the last record is in, which only the GPU-resident run offers (the streaming run's flags are final batch by batch).
+// FQD_FAST_STRAND=both ends the same way: it turns the reads where they lie in HBM, in front of the engine.
 struct FastModeRefusal : std::runtime_error { using std::runtime_error::runtime_error; };
 
-std::string fast_switches(bool best, bool clusters)
+std::string fast_switches(bool best, bool clusters, bool both)
 {
-    return best && clusters ? "FQD_FAST_KEEP=best and FQD_FAST_CLUSTERS=1" : best ? "FQD_FAST_KEEP=best" : "FQD_FAST_CLUSTERS=1";
+    std::string s;
+    for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr})
+        if (name) s += (s.empty() ? "" : " and ") + std::string(name);
+    return s;
 }
 
 } // namespace
 
-// Everything about the two switches that their values and the command line decide, before any GPU call.
+// Everything about the three switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     keep_best_ = fast_keep_best();
     write_clusters_ = fast_clusters();
-    if (!keep_best_ && !write_clusters_) return;
-    const std::string which = fast_switches(keep_best_, write_clusters_);
+    both_strands_ = fast_both_strands();
+    if (!keep_best_ && !write_clusters_ && !both_strands_) return;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_);
     if (unordered)
         throw FastModeRefusal(which + " with --unordered: these modes run on ordered inputs only");
     if (tuning_.devices.size() > 1)
@@ -69,11 +85,16 @@ void HashDupRemover::read_fast_modes(bool unordered)
 // records by it (fqd_group_owners) and, for `best`, moves the keep flag of every cluster to its best member
 // (pick_best_members, fqd_heads_to_keep).  There is no hand-over then: whatever would have sent the input to the
 // streaming run ends the run with a message that names the switch and the reason, still before any output exists.
+//
+// With FQD_FAST_STRAND=both (also `modes`) one fqd_canonical_reads over all n records stands between the record scan and
+// the submit loop, which then submits the canonical descriptors; whatever comes after the loop sees flags and links as
+// before, and the writers take the records' ORIGINAL text.
 bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
 {
-    const bool modes = keep_best_ || write_clusters_;
+    const bool linked = keep_best_ || write_clusters_, modes = linked || both_strands_;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_);
     auto give_up = [&](const std::string& why) -> bool {
-        if (modes) throw FastModeRefusal(fast_switches(keep_best_, write_clusters_) + ": the GPU-resident run cannot take this input (" + why +
+        if (modes) throw FastModeRefusal(which + ": the GPU-resident run cannot take this input (" + why +
                                          "), and the streaming run cannot serve these modes");
         return false;
     };
@@ -107,6 +128,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     FileOnDevice dev[2];
     Device<uint8_t> keep;
     Device<uint32_t> link, owner, perm; Device<uint8_t> head;     // FQD_FAST_KEEP / FQD_FAST_CLUSTERS
+    Device<uint8_t> canon, turned; Device<uint64_t> canon_off[2]; Device<uint32_t> canon_len[2];   // FQD_FAST_STRAND=both
     std::string clusters[2];
     uint64_t n = 0, dups = 0;
     std::unique_ptr<EngineHandle> eng;
@@ -149,31 +171,57 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         }
         if (S == 2 && dev[0].n != dev[1].n) return give_up("the two files hold different numbers of records");
         n = dev[0].n;
-        if (modes && n >= 0x80000000ull)
-            throw FastModeRefusal(fast_switches(keep_best_, write_clusters_) + ": at most 2^31-1 records (pairs) per run, the input holds " + std::to_string(n));
+        if (linked && n >= 0x80000000ull)
+            throw FastModeRefusal(which + ": at most 2^31-1 records (pairs) per run, the input holds " + std::to_string(n));
+        if (both_strands_ && n > 0xFFFFFFFEull)
+            throw FastModeRefusal(which + ": at most 2^32-2 records (pairs) per run, the input holds " + std::to_string(n));
         StageClock::Scope t("ordered/resident: dedup on the GPU");
         keep.reserve(n);
-        if (modes) { link.reserve(n); owner.reserve(n); perm.reserve(n); head.reserve(n); }
+        if (linked) { link.reserve(n); owner.reserve(n); perm.reserve(n); head.reserve(n); }
+        if (both_strands_) {
+            // the canonical sequences and their descriptors: no more than the sequence bytes — a FASTQ record is its
+            // sequence twice (bases, qualities) and at least six more bytes, a FASTA record its sequence and at least three
+            uint64_t bound = 0;
+            for (int s = 0; s < S; ++s)
+                bound += format_ == Format::Fasta ? dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 3 * n)
+                                                  : (dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 6 * n)) / 2 + 1;
+            canon.reserve(bound + 64); turned.reserve(n);
+            for (int s = 0; s < S; ++s) { canon_off[s].reserve(n); canon_len[s].reserve(n); }
+            StageClock::Scope t2("fast: both strands, canonical reads on the GPU");
+            fqd_reads given[2] = {};
+            for (int s = 0; s < S; ++s) {
+                given[s].bases = reinterpret_cast<const uint8_t*>(dev[s].text.p);
+                given[s].offsets = dev[s].seq_off.p; given[s].lengths = dev[s].seq_len.p;
+            }
+            uint64_t n_turned = 0;
+            engine_ok<DeviceError>(eng->e, fqd_canonical_reads(eng->e, given, n, canon.p, bound, canon_off[0].p, canon_len[0].p,
+                                                               S == 2 ? canon_off[1].p : nullptr, S == 2 ? canon_len[1].p : nullptr, turned.p,
+                                                               StageClock::on() ? &n_turned : nullptr));
+            if (StageClock::on()) std::cerr << "fast: both strands, " << n_turned << " of " << n << " records turned\n";
+        }
         const size_t kBatch = 16u << 20;
         int rc = FQD_OK;
         for (size_t a = 0; a < n && rc == FQD_OK; a += kBatch) {
             fqd_reads seg[2] = {};
             for (int s = 0; s < S; ++s) {
-                seg[s].bases = reinterpret_cast<const uint8_t*>(dev[s].text.p);
-                seg[s].offsets = dev[s].seq_off.p + a; seg[s].lengths = dev[s].seq_len.p + a;
+                seg[s].bases = both_strands_ ? canon.p : reinterpret_cast<const uint8_t*>(dev[s].text.p);
+                seg[s].offsets = (both_strands_ ? canon_off[s].p : dev[s].seq_off.p) + a;
+                seg[s].lengths = (both_strands_ ? canon_len[s].p : dev[s].seq_len.p) + a;
             }
-            if (modes) rc = fqd_submit_linked(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, link.p + a, a + kBatch < n ? 0 : 1);
+            if (linked) rc = fqd_submit_linked(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, link.p + a, a + kBatch < n ? 0 : 1);
             else rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
         }
         if (rc == FQD_OK) rc = fqd_engine_sync(eng->e);
         if (rc == FQD_ERR_BAD_BASE) return give_up(std::string(fqd_last_error(eng->e)));   // the streaming run cuts the output where the reference does
         if (rc != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e));
+        canon.release(); turned.release();                       // the last submit is through: nothing below reads a turned byte
+        for (int s = 0; s < 2; ++s) { canon_off[s].release(); canon_len[s].release(); }
         if (std::getenv("FQD_TEST_FAIL_RESIDENT")) throw DeviceError("GPU engine: forced by FQD_TEST_FAIL_RESIDENT");      // tests: the hand-over is announced
         fqd_stats st{};
         fqd_get_stats(eng->e, &st);
         dups = st.duplicates;
         FileOnDevice* all_files[2] = {&dev[0], &dev[1]};
-        if (modes) {
+        if (linked) {
             uint64_t n_clusters = 0;
             {
                 StageClock::Scope t2("fast: owners and clusters on the GPU");
@@ -202,7 +250,8 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     } catch (const FastModeRefusal&) {
         throw;                                                    // nothing has been written
     } catch (const DeviceOutOfMemory&) {
-        return give_up("the text, the record arrays and up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory");   // the streaming run needs a few blocks of HBM only
+        return give_up(both_strands_ ? "the text, the record arrays, the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record) and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory"
+                                     : "the text, the record arrays and up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory");   // the streaming run needs a few blocks of HBM only
     } catch (const DeviceError& e) {
         if (modes) return give_up(e.what());
         announce_handover("the GPU-resident ordered run", e);     // nothing has been written yet

@@ -589,6 +589,26 @@ int  fqd_owners(fqd_engine* e, const uint8_t* keep, const uint32_t* link, uint64
 int  fqd_group_owners(fqd_engine* e, const uint32_t* owner, uint64_t n, uint32_t* perm, uint8_t* head, uint64_t* n_clusters);
 int  fqd_heads_to_keep(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint64_t n, uint8_t* keep);
 
+/* ---- FQD_FAST_STRAND=both: the orientation a read (pair) is keyed in (added within ABI version 5: purely additive; no
+ * existing entry launches anything new).  Rule and proofs: csrc/fqd_strand_core.hpp.  Single-end: the canonical form of a
+ * read s is the bytewise smaller of s and its reverse complement (A<->T, C<->G, every other byte as it is); flipped = the
+ * reverse complement is strictly smaller.  Pairs: the canonical form of (mate 1, mate 2) has the smaller mate first — bytewise
+ * over the shorter length, the shorter first on a tie; nothing is complemented; flipped = mate 2 is strictly smaller.  Two
+ * records are copies of one fragment, whichever strand each came from, exactly when their canonical forms are identical.
+ *
+ * fqd_canonical_reads: device memory only.  seg = the engine's `segments` descriptors, ragged or uniform as in fqd_submit.
+ * The canonical sequences of the n records are packed back to back, in input order, into out: record i's first canonical
+ * mate at out_off0[i] with out_len0[i] bytes, then (paired engines) its second at out_off1[i] = out_off0[i] + out_len0[i]
+ * with out_len1[i] bytes; the offsets are exclusive prefix sums in 64 bits, the total is exactly the input's sequence bytes.
+ * out_capacity below that total: FQD_ERR_ARG, and none of the output arrays is written.  flipped[i] (n bytes) = 1 where
+ * record i was turned; *n_flipped (host, may be NULL) = how many.  {out, out_off0, out_len0} and {out, out_off1, out_len1}
+ * are fqd_reads that fqd_submit* take.  out_off1 and out_len1 are NULL for a single-end engine (anything else: FQD_ERR_ARG).
+ * Queued on the engine's stream and not waited for, except: with n_flipped the call returns after the stream has drained,
+ * and with ragged descriptors it waits for its size scan (8 bytes come back) before it queues the rest. */
+int  fqd_canonical_reads(fqd_engine* e, const fqd_reads* seg, uint64_t n, uint8_t* out, uint64_t out_capacity,
+                         uint64_t* out_off0, uint32_t* out_len0, uint64_t* out_off1, uint32_t* out_len1,
+                         uint8_t* flipped, uint64_t* n_flipped);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
