@@ -49,6 +49,15 @@ class SeqRange(C.Structure):                                 # fqd_seq_range
                 ("bytes_mate1", C.c_uint64)]
 
 
+class UmiInfo(C.Structure):                                  # fqd_umi_info
+    _fields_ = [("n_bases", C.c_uint32), ("umi_len", C.c_uint32), ("joiners", C.c_uint64), ("bad_record", C.c_uint64),
+                ("bad_reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
+UMI_OK, UMI_NO_SEPARATOR, UMI_EMPTY, UMI_TOO_LONG, UMI_BAD_BYTE, UMI_NO_BASE, UMI_SHAPE_DIFFERS = range(7)
+
+
 class JoinDesc(C.Structure):
     _fields_ = [("perm_a", C.c_void_p), ("perm_b", C.c_void_p), ("match_a", C.c_void_p), ("match_b", C.c_void_p),
                 ("pair_a", C.c_void_p), ("pair_b", C.c_void_p), ("n_pairs", C.POINTER(C.c_uint64))]
@@ -144,6 +153,8 @@ def load_library():
     L.fqd_group_owners.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
     L.fqd_heads_to_keep.argtypes = [vp, vp, vp, u64, vp]
     L.fqd_canonical_reads.argtypes = [vp, C.POINTER(ReadsDesc), u64, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
+    L.fqd_umi_find.argtypes = [vp, vp, vp, vp, u64, i32, vp, C.POINTER(UmiInfo)]
+    L.fqd_umi_reads.argtypes = [vp, vp, vp, vp, C.POINTER(UmiInfo), C.POINTER(ReadsDesc), u64, vp, u64, vp, vp]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

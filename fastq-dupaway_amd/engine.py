@@ -328,6 +328,25 @@ class Engine:
                                                 self._p(out_off1), self._p(out_len1), self._p(flipped), C.byref(turned) if count else None))
         return int(turned.value) if count else None
 
+    # -- FQD_FAST_UMI (csrc/fqd_umi.hip) ----------------------------------------------------------------
+    def umi_find(self, text, id_start, id_len, n: int, sep: str, umi_off, info=True):
+        """umi_off[i] (n uint32, device) = where the UMI field starts inside ID line i (id_len[i] bytes at text +
+        id_start[i]): behind the last `sep` (':' or '_') of the line's first word.  Returns the call's fqd_umi_info
+        (_lib.UmiInfo): record 0's shape, and the lowest refused record with its reason.  info=None hands the library a null
+        pointer, which it refuses."""
+        got = _lib.UmiInfo() if info else None
+        self._check(self._L.fqd_umi_find(self._h, self._p(text), self._p(id_start), self._p(id_len), n, ord(sep), self._p(umi_off),
+                                         C.byref(got) if info else None))
+        return got
+
+    def umi_reads(self, text, id_start, umi_off, info, mate0: Reads, n: int, out, out_off, out_len, out_capacity: Optional[int] = None):
+        """Record i's key bytes — the bases of its UMI field, then mate 1's sequence (mate0, device memory) — packed back to
+        back into out (device bytes; out_capacity defaults to out.numel()): Reads(out, out_off, out_len) goes into submit as
+        mate 1.  info: what umi_find returned."""
+        cap = out.numel() if out_capacity is None else out_capacity
+        self._check(self._L.fqd_umi_reads(self._h, self._p(text), self._p(id_start), self._p(umi_off), C.byref(info) if info is not None else None,
+                                          self._desc([mate0]), n, self._p(out), cap, self._p(out_off), self._p(out_len)))
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

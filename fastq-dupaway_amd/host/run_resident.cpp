@@ -36,6 +36,19 @@ bool fast_both_strands()
     throw std::runtime_error(std::string("FQD_FAST_STRAND must be 'given' or 'both', not '") + v + "'");
 }
 
+// FQD_FAST_UMI=off|colon|underscore: whether `--fast` keys a read (pair) by the unique molecular identifier in file 1's ID
+// lines as well.  off (and unset): by its sequence(s) alone; colon / underscore: by the UMI bases behind the last ':' / '_'
+// of the ID line's first word, then the sequence(s) (csrc/fqd_umi_core.hpp).  Returns 0, ':' or '_'.  Read here and
+// nowhere else.
+int fast_umi()
+{
+    const char* v = std::getenv("FQD_FAST_UMI");
+    if (!v || std::strcmp(v, "off") == 0) return 0;
+    if (std::strcmp(v, "colon") == 0) return ':';
+    if (std::strcmp(v, "underscore") == 0) return '_';
+    throw std::runtime_error(std::string("FQD_FAST_UMI must be 'off', 'colon' or 'underscore', not '") + v + "'");
+}
+
 } // namespace detail
 
 namespace {
@@ -45,24 +58,42 @@ namespace {
 // FQD_FAST_STRAND=both ends the same way: it turns the reads where they lie in HBM, in front of the engine.
 struct FastModeRefusal : std::runtime_error { using std::runtime_error::runtime_error; };
 
-std::string fast_switches(bool best, bool clusters, bool both)
+const char* umi_switch(int umi) { return umi == ':' ? "FQD_FAST_UMI=colon" : umi == '_' ? "FQD_FAST_UMI=underscore" : nullptr; }
+
+std::string fast_switches(bool best, bool clusters, bool both, int umi)
 {
     std::string s;
-    for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr})
+    for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr, umi_switch(umi)})
         if (name) s += (s.empty() ? "" : " and ") + std::string(name);
     return s;
 }
 
+// Why fqd_umi_find refuses a record (enum fqd_umi_reason), in the words of csrc/fqd_umi_core.hpp.
+std::string umi_reason(uint32_t reason, int sep)
+{
+    const std::string c(1, char(sep));
+    switch (reason) {
+    case FQD_UMI_NO_SEPARATOR: return "the first word of its ID line holds no '" + c + "'";
+    case FQD_UMI_EMPTY: return "its UMI is empty: the last '" + c + "' is the last byte of the ID line's first word";
+    case FQD_UMI_TOO_LONG: return "its UMI is longer than 64 bytes";
+    case FQD_UMI_BAD_BYTE: return "its UMI holds a byte outside ACGTN+-_";
+    case FQD_UMI_NO_BASE: return "its UMI has no base";
+    case FQD_UMI_SHAPE_DIFFERS: return "the shape of its UMI (its length and the places of '+', '-', '_') differs from record 0's: UMIs of varying length are not supported";
+    }
+    return "its UMI was refused";
+}
+
 } // namespace
 
-// Everything about the three switches that their values and the command line decide, before any GPU call.
+// Everything about the four switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     keep_best_ = fast_keep_best();
     write_clusters_ = fast_clusters();
     both_strands_ = fast_both_strands();
-    if (!keep_best_ && !write_clusters_ && !both_strands_) return;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_);
+    umi_sep_ = fast_umi();
+    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_) return;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_);
     if (unordered)
         throw FastModeRefusal(which + " with --unordered: these modes run on ordered inputs only");
     if (tuning_.devices.size() > 1)
@@ -89,10 +120,15 @@ void HashDupRemover::read_fast_modes(bool unordered)
 // With FQD_FAST_STRAND=both (also `modes`) one fqd_canonical_reads over all n records stands between the record scan and
 // the submit loop, which then submits the canonical descriptors; whatever comes after the loop sees flags and links as
 // before, and the writers take the records' ORIGINAL text.
+//
+// With FQD_FAST_UMI=colon|underscore (also `modes`) one more rewrite stands at that place, behind the strand block:
+// fqd_umi_find over file 1's ID lines — a record it refuses ends the run — then fqd_umi_reads, which packs `UMI bases ‖
+// sequence` of mate 1 (the canonical mate 1 with FQD_FAST_STRAND=both) for the submit loop's segment 0.  Mate 2 goes to the
+// submit as it is.
 bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
 {
-    const bool linked = keep_best_ || write_clusters_, modes = linked || both_strands_;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_);
+    const bool linked = keep_best_ || write_clusters_, modes = linked || both_strands_ || umi_sep_;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_);
     auto give_up = [&](const std::string& why) -> bool {
         if (modes) throw FastModeRefusal(which + ": the GPU-resident run cannot take this input (" + why +
                                          "), and the streaming run cannot serve these modes");
@@ -129,6 +165,8 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     Device<uint8_t> keep;
     Device<uint32_t> link, owner, perm; Device<uint8_t> head;     // FQD_FAST_KEEP / FQD_FAST_CLUSTERS
     Device<uint8_t> canon, turned; Device<uint64_t> canon_off[2]; Device<uint32_t> canon_len[2];   // FQD_FAST_STRAND=both
+    Device<uint8_t> umi_text; Device<uint64_t> umi_off64; Device<uint32_t> umi_len, umi_off;        // FQD_FAST_UMI
+    uint32_t umi_bases = 0;
     std::string clusters[2];
     uint64_t n = 0, dups = 0;
     std::unique_ptr<EngineHandle> eng;
@@ -173,31 +211,52 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         n = dev[0].n;
         if (linked && n >= 0x80000000ull)
             throw FastModeRefusal(which + ": at most 2^31-1 records (pairs) per run, the input holds " + std::to_string(n));
-        if (both_strands_ && n > 0xFFFFFFFEull)
+        if ((both_strands_ || umi_sep_) && n > 0xFFFFFFFEull)
             throw FastModeRefusal(which + ": at most 2^32-2 records (pairs) per run, the input holds " + std::to_string(n));
         StageClock::Scope t("ordered/resident: dedup on the GPU");
         keep.reserve(n);
         if (linked) { link.reserve(n); owner.reserve(n); perm.reserve(n); head.reserve(n); }
+        // no more than a file's sequence bytes — a FASTQ record is its sequence twice (bases, qualities) and at least six
+        // more bytes, a FASTA record its sequence and at least three
+        auto seq_bound = [&](int s) -> uint64_t {
+            return format_ == Format::Fasta ? dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 3 * n)
+                                            : (dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 6 * n)) / 2 + 1;
+        };
+        fqd_reads given[2] = {};
+        for (int s = 0; s < S; ++s) {
+            given[s].bases = reinterpret_cast<const uint8_t*>(dev[s].text.p);
+            given[s].offsets = dev[s].seq_off.p; given[s].lengths = dev[s].seq_len.p;
+        }
         if (both_strands_) {
-            // the canonical sequences and their descriptors: no more than the sequence bytes — a FASTQ record is its
-            // sequence twice (bases, qualities) and at least six more bytes, a FASTA record its sequence and at least three
+            // the canonical sequences and their descriptors
             uint64_t bound = 0;
-            for (int s = 0; s < S; ++s)
-                bound += format_ == Format::Fasta ? dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 3 * n)
-                                                  : (dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 6 * n)) / 2 + 1;
+            for (int s = 0; s < S; ++s) bound += seq_bound(s);
             canon.reserve(bound + 64); turned.reserve(n);
             for (int s = 0; s < S; ++s) { canon_off[s].reserve(n); canon_len[s].reserve(n); }
             StageClock::Scope t2("fast: both strands, canonical reads on the GPU");
-            fqd_reads given[2] = {};
-            for (int s = 0; s < S; ++s) {
-                given[s].bases = reinterpret_cast<const uint8_t*>(dev[s].text.p);
-                given[s].offsets = dev[s].seq_off.p; given[s].lengths = dev[s].seq_len.p;
-            }
             uint64_t n_turned = 0;
             engine_ok<DeviceError>(eng->e, fqd_canonical_reads(eng->e, given, n, canon.p, bound, canon_off[0].p, canon_len[0].p,
                                                                S == 2 ? canon_off[1].p : nullptr, S == 2 ? canon_len[1].p : nullptr, turned.p,
                                                                StageClock::on() ? &n_turned : nullptr));
             if (StageClock::on()) std::cerr << "fast: both strands, " << n_turned << " of " << n << " records turned\n";
+        }
+        if (umi_sep_) {
+            StageClock::Scope t2("fast: UMI, find and pack on the GPU");
+            const uint8_t* text0 = reinterpret_cast<const uint8_t*>(dev[0].text.p);
+            umi_off.reserve(n);
+            fqd_umi_info info{};
+            engine_ok<DeviceError>(eng->e, fqd_umi_find(eng->e, text0, dev[0].start.p, dev[0].id_len.p, n, umi_sep_, umi_off.p, &info));
+            if (info.bad_record != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal(std::string(umi_switch(umi_sep_)) + ": record " + std::to_string(info.bad_record) + " (counted from 0) of " + in[0] +
+                                      ": " + umi_reason(info.bad_reason, umi_sep_));
+            umi_bases = info.n_bases;
+            // mate 1's sequence bytes (with both strands the canonical mate 1 of a pair may be either file's read), the UMI
+            // bases of every record, and the descriptors
+            const uint64_t bound = seq_bound(0) + (both_strands_ && S == 2 ? seq_bound(1) : 0) + uint64_t(umi_bases) * n;
+            umi_text.reserve(bound + 64); umi_off64.reserve(n); umi_len.reserve(n);
+            const fqd_reads mate0 = both_strands_ ? fqd_reads{canon.p, canon_off[0].p, canon_len[0].p, 0, 0} : given[0];
+            engine_ok<DeviceError>(eng->e, fqd_umi_reads(eng->e, text0, dev[0].start.p, umi_off.p, &info, &mate0, n, umi_text.p, bound, umi_off64.p, umi_len.p));
+            if (StageClock::on()) std::cerr << "fast: UMI, " << umi_bases << " bases behind the last '" << char(umi_sep_) << "' of the first word\n";
         }
         const size_t kBatch = 16u << 20;
         int rc = FQD_OK;
@@ -208,14 +267,17 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
                 seg[s].offsets = (both_strands_ ? canon_off[s].p : dev[s].seq_off.p) + a;
                 seg[s].lengths = (both_strands_ ? canon_len[s].p : dev[s].seq_len.p) + a;
             }
+            if (umi_sep_) seg[0] = fqd_reads{umi_text.p, umi_off64.p + a, umi_len.p + a, 0, 0};
             if (linked) rc = fqd_submit_linked(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, link.p + a, a + kBatch < n ? 0 : 1);
             else rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
         }
         if (rc == FQD_OK) rc = fqd_engine_sync(eng->e);
-        if (rc == FQD_ERR_BAD_BASE) return give_up(std::string(fqd_last_error(eng->e)));   // the streaming run cuts the output where the reference does
+        if (rc == FQD_ERR_BAD_BASE)                              // the streaming run cuts the output where the reference does
+            return give_up(std::string(fqd_last_error(eng->e)) + (umi_sep_ ? "; a position in mate 1 counts the " + std::to_string(umi_bases) + " UMI bases in front of the sequence" : std::string()));
         if (rc != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e));
         canon.release(); turned.release();                       // the last submit is through: nothing below reads a turned byte
         for (int s = 0; s < 2; ++s) { canon_off[s].release(); canon_len[s].release(); }
+        umi_text.release(); umi_off64.release(); umi_len.release(); umi_off.release();
         if (std::getenv("FQD_TEST_FAIL_RESIDENT")) throw DeviceError("GPU engine: forced by FQD_TEST_FAIL_RESIDENT");      // tests: the hand-over is announced
         fqd_stats st{};
         fqd_get_stats(eng->e, &st);
@@ -250,6 +312,10 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     } catch (const FastModeRefusal&) {
         throw;                                                    // nothing has been written
     } catch (const DeviceOutOfMemory&) {
+        if (umi_sep_)
+            return give_up(std::string("the text, the record arrays, the keyed bytes of FQD_FAST_UMI (mate 1's sequence bytes once more and the UMI bases of every record, 16 bytes a record)") +
+                           (both_strands_ ? ", the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record)" : "") +
+                           " and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory");
         return give_up(both_strands_ ? "the text, the record arrays, the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record) and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory"
                                      : "the text, the record arrays and up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory");   // the streaming run needs a few blocks of HBM only
     } catch (const DeviceError& e) {

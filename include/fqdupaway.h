@@ -609,6 +609,51 @@ int  fqd_canonical_reads(fqd_engine* e, const fqd_reads* seg, uint64_t n, uint8_
                          uint64_t* out_off0, uint32_t* out_len0, uint64_t* out_off1, uint32_t* out_len1,
                          uint8_t* flipped, uint64_t* n_flipped);
 
+/* ---- FQD_FAST_UMI=colon|underscore: the unique molecular identifier in a record's ID line as part of its key (added
+ * within ABI version 5: purely additive; no existing entry launches anything new).  Rule and proofs:
+ * csrc/fqd_umi_core.hpp.  The first word W of an ID line is what stands behind its leading '@' / '>' up to the first of
+ * ' ', '\t', '\r', '\n'; the UMI field U is what stands in W behind its LAST separator byte (sep: ':' or '_'); '+', '-'
+ * and '_' inside U join the halves of a dual UMI, every other byte of U is one of A C G T N; U's shape is its length and
+ * the set of its places that hold a joiner, and it is the same for every record of a run.  The key of a record is U's bases
+ * in front of mate 1's sequence.
+ *
+ * fqd_umi_find: device memory only (info: host).  Line i is the id_len[i] bytes at text + id_start[i].  umi_off[i] (n
+ * uint32) = U's offset inside line i: the last separator's position + 1, 0 where W holds none.  *info: umi_len, joiners
+ * (bit p = U[p] is a joiner) and n_bases = umi_len - popcount(joiners) are record 0's shape (all 0 when record 0 is
+ * refused or n = 0); bad_record = the LOWEST record that is refused (FQD_UMI_NO_RECORD: none) and bad_reason why — the
+ * first of FQD_UMI_NO_SEPARATOR .. FQD_UMI_SHAPE_DIFFERS that holds for it, in that order.  Nothing else is written.
+ * Returns after the stream has drained (once).
+ *
+ * fqd_umi_reads: device memory only (info: host, as fqd_umi_find left it with no record refused — anything else is
+ * FQD_ERR_ARG).  mate0 = ONE descriptor, ragged or uniform as in fqd_submit: mate 1's sequences.  Record i's key bytes — the
+ * n_bases bases of its U, then its sequence — are packed back to back, in input order, into out at out_off[i] with
+ * out_len[i] = n_bases + its length; the offsets are exclusive prefix sums in 64 bits.  out_capacity below their total:
+ * FQD_ERR_ARG, and none of the output arrays is written.  {out, out_off, out_len} is an fqd_reads that fqd_submit* take
+ * for mate 1.  Queued on the engine's stream and not waited for, except that with ragged descriptors it waits for its size
+ * scan (8 bytes come back) before it queues the rest. */
+#define FQD_UMI_NO_RECORD 0xFFFFFFFFFFFFFFFFull
+enum fqd_umi_reason {
+    FQD_UMI_OK = 0,
+    FQD_UMI_NO_SEPARATOR = 1,   /* W holds no separator */
+    FQD_UMI_EMPTY = 2,          /* U is empty: the separator is W's last byte */
+    FQD_UMI_TOO_LONG = 3,       /* U is longer than 64 bytes */
+    FQD_UMI_BAD_BYTE = 4,       /* U holds a byte outside ACGTN+-_ */
+    FQD_UMI_NO_BASE = 5,        /* U holds joiners only */
+    FQD_UMI_SHAPE_DIFFERS = 6   /* U's length or joiner places differ from record 0's */
+};
+typedef struct fqd_umi_info {
+    uint32_t n_bases;           /* Lb */
+    uint32_t umi_len;
+    uint64_t joiners;
+    uint64_t bad_record;
+    uint32_t bad_reason;        /* enum fqd_umi_reason */
+    uint32_t reserved;
+} fqd_umi_info;
+int  fqd_umi_find(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, const uint32_t* id_len, uint64_t n, int sep,
+                  uint32_t* umi_off, fqd_umi_info* info);
+int  fqd_umi_reads(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, const uint32_t* umi_off, const fqd_umi_info* info,
+                   const fqd_reads* mate0, uint64_t n, uint8_t* out, uint64_t out_capacity, uint64_t* out_off, uint32_t* out_len);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
