@@ -18,6 +18,7 @@
 
 #include "fqd_internal.hpp"
 #include "fqd_kernels.hpp"
+#include "fqd_table_geometry.hpp"
 
 using namespace fqd;
 
@@ -100,7 +101,6 @@ struct fqd_engine {
 
 namespace {
 
-inline uint64_t pow2_at_least(uint64_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
 inline uint32_t grid_for(const fqd_engine* e, uint64_t n, uint32_t per_block = kBlock)
 {
     const uint64_t want = (n + per_block - 1) / per_block;
@@ -223,33 +223,11 @@ KeyStore key_store(const fqd_engine* e)
     return KeyStore{e->keys.as<uint64_t>(), e->ragged ? e->koff.as<uint64_t>() : nullptr, e->W0, e->W0, 0};
 }
 
-// Probing segments: 4096..16384 slots so that (slots / segment) <= 131072 buckets, or the whole
-// table when it is smaller than one segment.
-uint32_t seg_bits_for(uint64_t slots)
+// Table geometry (csrc/fqd_table_geometry.hpp) with this process's wishes: FQD_SEG_BITS is read per table.
+uint32_t wanted_seg_bits()
 {
-    uint32_t t = 0; while ((1ull << t) < slots) ++t;
-    if (t <= 12) return t;
-    uint32_t want = 13u;                                 // 64 KiB of LDS per segment: best of the 12/13/14 sweep
-    if (const char* v = std::getenv("FQD_SEG_BITS")) want = uint32_t(std::min(14, std::max(12, std::atoi(v))));
-    return std::min<uint32_t>(14u, std::max<uint32_t>(want, t >= 17 ? t - 17 : 12u));
-}
-
-// How a table of 2^t slots with 2^seg_bits-slot segments is split into partition digits, and
-// how wide its slot tags can be so that a partition record fits 8 bytes (fqd_kernels.hpp,
-// BulkGeom): seg_bits + bits2 + tag bits = 32.
-void table_digits(uint32_t t, uint32_t seg_bits, uint32_t& bits1, uint32_t& bits2)
-{
-    const uint32_t nb_bits = t > seg_bits ? t - seg_bits : 0;
-    bits1 = nb_bits <= 8 ? nb_bits : std::min<uint32_t>(8u, (nb_bits + 1) / 2);   // level 1: 256 ways at most
-    bits2 = nb_bits - bits1;                                                      // level 2: 512 ways at most (bulk_plan checks)
-}
-uint32_t tag_mask_for(uint64_t slots, uint32_t seg_bits)
-{
-    uint32_t t = 0; while ((1ull << t) < slots) ++t;
-    uint32_t bits1, bits2;
-    table_digits(t, seg_bits, bits1, bits2);
-    const uint32_t tag_bits = 32u - std::min(seg_bits, 14u) - std::min(bits2, 9u);
-    return tag_bits >= 32 ? 0xFFFFFFFFu : (1u << tag_bits) - 1u;
+    if (const char* v = std::getenv("FQD_SEG_BITS")) return fqdgeom::clamp_seg_bits(std::atoi(v));
+    return fqdgeom::kDefaultSegBits;
 }
 
 // Keeps the table at <= 50 % load.  `exact`: size for a known total (capacity hint);
@@ -260,15 +238,15 @@ int ensure_table(fqd_engine* e, uint64_t records_after, bool exact = false)
     // (capacity hint) may run denser, FQD_TABLE_PCT slots per 100 records: segments are probed in
     // LDS by the bulk path, where longer probe runs cost little and every slot not allocated is 8
     // bytes of table the dedup kernel does not write back.
-    static const uint64_t exact_pct = [] { const char* v = std::getenv("FQD_TABLE_PCT"); const long x = v ? std::atol(v) : 200; return uint64_t(x < 115 ? 115 : (x > 400 ? 400 : x)); }();
-    const uint64_t min_slots = e->table_exact ? (records_after * exact_pct + 99) / 100 : 2 * records_after;
+    static const uint64_t exact_pct = [] { const char* v = std::getenv("FQD_TABLE_PCT"); return v ? fqdgeom::clamp_table_pct(std::atol(v)) : fqdgeom::kDefaultTablePct; }();
+    const uint64_t min_slots = fqdgeom::min_slots_for(records_after, e->table_exact, exact_pct);
     if (e->slots >= min_slots && e->slots) return FQD_OK;
     e->table_exact = exact;
-    const uint64_t want = std::max<uint64_t>(pow2_at_least(exact ? (records_after * exact_pct + 99) / 100 : 4 * records_after), 1ull << 16);
+    const uint64_t want = fqdgeom::slots_for(records_after, exact, exact_pct);
     void* nt = nullptr;
     HIP_TRY(e, hipMalloc(&nt, want * sizeof(uint64_t)));
-    const uint32_t new_seg_bits = seg_bits_for(want);
-    const uint32_t new_tag_mask = tag_mask_for(want, new_seg_bits);
+    const uint32_t new_seg_bits = fqdgeom::seg_bits_for(want, wanted_seg_bits());
+    const uint32_t new_tag_mask = fqdgeom::tag_mask_for(want, new_seg_bits);
     if (e->slots && e->n_records) {
         Bracket br(e, K_OTHER, 0);
         HIP_TRY(e, hipMemsetAsync(nt, 0xFF, want * sizeof(uint64_t), e->stream));
@@ -463,7 +441,7 @@ int bulk_plan(fqd_engine* e, uint64_t n, BulkPlan& p)
     p.ok = false;
     if (nb_bits > 17 || nb_bits == 0) return FQD_OK;
     p.g.slot_mask = e->slots - 1; p.g.seg_bits = e->seg_bits; p.g.tag_mask = e->tag_mask;
-    table_digits(t, e->seg_bits, p.g.bits1, p.g.bits2);
+    fqdgeom::table_digits(t, e->seg_bits, p.g.bits1, p.g.bits2);
     p.nd1 = 1u << p.g.bits1; p.n_buckets = 1u << nb_bits;
     int rc;
     const size_t rec_bytes = ((n * sizeof(uint64_t)) + 255) & ~size_t(255);
