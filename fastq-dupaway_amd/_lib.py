@@ -54,6 +54,10 @@ class UmiInfo(C.Structure):                                  # fqd_umi_info
                 ("bad_reason", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SizeLevels(C.Structure):                               # fqd_size_levels
+    _fields_ = [("clusters", C.c_uint64 * 16), ("records", C.c_uint64 * 16), ("largest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
 UMI_OK, UMI_NO_SEPARATOR, UMI_EMPTY, UMI_TOO_LONG, UMI_BAD_BYTE, UMI_NO_BASE, UMI_SHAPE_DIFFERS = range(7)
 
@@ -155,6 +159,9 @@ def load_library():
     L.fqd_canonical_reads.argtypes = [vp, C.POINTER(ReadsDesc), u64, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.fqd_umi_find.argtypes = [vp, vp, vp, vp, u64, i32, vp, C.POINTER(UmiInfo)]
     L.fqd_umi_reads.argtypes = [vp, vp, vp, vp, C.POINTER(UmiInfo), C.POINTER(ReadsDesc), u64, vp, u64, vp, vp]
+    L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
+    L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
+    L.fqd_copy_labelled.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

@@ -347,6 +347,27 @@ class Engine:
         self._check(self._L.fqd_umi_reads(self._h, self._p(text), self._p(id_start), self._p(umi_off), C.byref(info) if info is not None else None,
                                           self._desc([mate0]), n, self._p(out), cap, self._p(out_off), self._p(out_len)))
 
+    # -- FQD_FAST_SIZEOUT / FQD_FAST_LEVELS (csrc/fqd_size.hip) --------------------------------------------
+    def cluster_sizes(self, perm, head, n: int, size, levels: bool = True):
+        """size[perm[k]] (n uint32, device) = the length of the run of (perm, head) that starts at place k where head[k], 0 at
+        every other place.  Returns the call's fqd_size_levels (_lib.SizeLevels): runs and records per duplication level and
+        the longest run; levels=False hands the library a null pointer and returns None."""
+        got = _lib.SizeLevels() if levels else None
+        self._check(self._L.fqd_cluster_sizes(self._h, self._p(perm), self._p(head), n, self._p(size), C.byref(got) if levels else None))
+        return got
+
+    def size_labels(self, text, start, id_len, rec_size, keep, size, n: int, label_at, out_size):
+        """Per record of one file: label_at = the length of '@' and the first word of its ID line (where `;size=N` goes),
+        out_size = its size with the label where keep is set: output_plan's `sizes`."""
+        self._check(self._L.fqd_size_labels(self._h, self._p(text), self._p(start), self._p(id_len), self._p(rec_size), self._p(keep),
+                                            self._p(size), n, self._p(label_at), self._p(out_size)))
+
+    def copy_labelled(self, src, src_off, lens, label_at, size, n: int, dst, dst_off):
+        """copy_spans with `;size=<size[i]>` put in at label_at[i]; lens are the grown lengths of output_plan.  dst may be an
+        address (int): a window's buffer moved back by the window's first offset."""
+        self._check(self._L.fqd_copy_labelled(self._h, self._p(src), self._p(src_off), self._p(lens), self._p(label_at), self._p(size), n,
+                                              self._p(dst), self._p(dst_off)))
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

@@ -68,5 +68,21 @@ uint64_t pick_best_members(fqd_engine* e, int S, FileOnDevice* const* files, uin
     return moved;
 }
 
+// `<output 1>.duplevels`: a header, the sixteen levels of csrc/fqd_size_core.hpp (all always there), the totals and the
+// largest cluster, tab-separated.
+std::string duplevels_text(const fqd_size_levels& lv)
+{
+    static const char* const kRows[16] = {"1", "2", "3", "4", "5", "6", "7", "8", "9", "10-49", "50-99", "100-499", "500-999", "1000-4999", "5000-9999", "10000+"};
+    std::string text = "#level\tclusters\trecords\n";
+    uint64_t clusters = 0, records = 0;
+    for (int k = 0; k < 16; ++k) {
+        text += std::string(kRows[k]) + "\t" + std::to_string(lv.clusters[k]) + "\t" + std::to_string(lv.records[k]) + "\n";
+        clusters += lv.clusters[k]; records += lv.records[k];
+    }
+    text += "#total\t" + std::to_string(clusters) + "\t" + std::to_string(records) + "\n";
+    text += "#largest\t" + std::to_string(lv.largest) + "\n";
+    return text;
+}
+
 } // namespace detail
 } // namespace fqdhost

@@ -434,13 +434,18 @@ ParseFailure append_file(const std::string& name, Format format, bool want_tag, 
 // Everything write_survivors allocates — the output plan of each file, the window and member buffers on the device,
 // the pinned buffers the windows come back in — so that a run can have it all BEFORE it creates an output (ADVICE r2:
 // an allocation that fails after the sinks exist leaves truncated files and no way back to the streaming run).
+// With FQD_FAST_SIZEOUT the caller sets cluster_size (device, per record: fqd_cluster_sizes) before plan_survivors: every
+// file then gets label_at and out_size (fqd_size_labels, 8 bytes a record and file), the plan is made from out_size, and the
+// windows are copied by fqd_copy_labelled.  Only for runs whose pair k is record k (idx[s] == nullptr).
 struct SurvivorBuffers {
     struct PerFile {
         Device<uint64_t> src_off, dst_off; Device<uint32_t> len; uint64_t total = 0;
+        Device<uint32_t> label_at, out_size;          // FQD_FAST_SIZEOUT only
         Pinned<char> buf[2]; Device<char> d_win[2], d_members[2];      // a slot = pinned buffer k + the device buffers k
         bool on_device = false;                       // .gz: windows leave the device as finished BGZF members
     } f[2];
     uint64_t window = 0, roomy = 0;
+    const uint32_t* cluster_size = nullptr;           // FQD_FAST_SIZEOUT: the label of record r says cluster_size[r]
     bool planned = false;
 };
 
@@ -458,6 +463,9 @@ void write_clusters(fqd_engine* e, hipStream_t stream, FileOnDevice& f, const ui
                     const std::string& name, bool append = false);
 uint64_t pick_best_members(fqd_engine* e, int S, FileOnDevice* const* files, uint64_t n, const uint8_t* head, uint32_t* perm,
                            const char* stage = "sequence: best-quality pick on the GPU");
+
+// ---- FQD_FAST_LEVELS (cluster_output.cpp): the text of `<output 1>.duplevels` ----
+std::string duplevels_text(const fqd_size_levels& lv);
 
 } // namespace detail
 } // namespace fqdhost

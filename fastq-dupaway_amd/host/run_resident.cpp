@@ -49,6 +49,22 @@ int fast_umi()
     throw std::runtime_error(std::string("FQD_FAST_UMI must be 'off', 'colon' or 'underscore', not '") + v + "'");
 }
 
+// FQD_FAST_SIZEOUT=1: every record `--fast` writes carries `;size=N`, its cluster's member count, behind the first word of
+// its ID line (csrc/fqd_size_core.hpp).  Read here and nowhere else.
+bool fast_sizeout()
+{
+    const char* v = std::getenv("FQD_FAST_SIZEOUT");
+    return v && std::atoi(v) != 0;
+}
+
+// FQD_FAST_LEVELS=1: `--fast` writes `<output 1>.duplevels`, the clusters and records per duplication level.  Read here and
+// nowhere else.
+bool fast_levels()
+{
+    const char* v = std::getenv("FQD_FAST_LEVELS");
+    return v && std::atoi(v) != 0;
+}
+
 } // namespace detail
 
 namespace {
@@ -60,10 +76,11 @@ struct FastModeRefusal : std::runtime_error { using std::runtime_error::runtime_
 
 const char* umi_switch(int umi) { return umi == ':' ? "FQD_FAST_UMI=colon" : umi == '_' ? "FQD_FAST_UMI=underscore" : nullptr; }
 
-std::string fast_switches(bool best, bool clusters, bool both, int umi)
+std::string fast_switches(bool best, bool clusters, bool both, int umi, bool sizeout, bool levels)
 {
     std::string s;
-    for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr, umi_switch(umi)})
+    for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr, umi_switch(umi),
+                             sizeout ? "FQD_FAST_SIZEOUT=1" : nullptr, levels ? "FQD_FAST_LEVELS=1" : nullptr})
         if (name) s += (s.empty() ? "" : " and ") + std::string(name);
     return s;
 }
@@ -85,15 +102,17 @@ std::string umi_reason(uint32_t reason, int sep)
 
 } // namespace
 
-// Everything about the four switches that their values and the command line decide, before any GPU call.
+// Everything about the six switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     keep_best_ = fast_keep_best();
     write_clusters_ = fast_clusters();
     both_strands_ = fast_both_strands();
     umi_sep_ = fast_umi();
-    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_) return;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_);
+    size_out_ = fast_sizeout();
+    write_levels_ = fast_levels();
+    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_ && !size_out_ && !write_levels_) return;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, size_out_, write_levels_);
     if (unordered)
         throw FastModeRefusal(which + " with --unordered: these modes run on ordered inputs only");
     if (tuning_.devices.size() > 1)
@@ -125,10 +144,16 @@ void HashDupRemover::read_fast_modes(bool unordered)
 // fqd_umi_find over file 1's ID lines — a record it refuses ends the run — then fqd_umi_reads, which packs `UMI bases ‖
 // sequence` of mate 1 (the canonical mate 1 with FQD_FAST_STRAND=both) for the submit loop's segment 0.  Mate 2 goes to the
 // submit as it is.
+//
+// With FQD_FAST_SIZEOUT=1 or FQD_FAST_LEVELS=1 (both `linked`) one fqd_cluster_sizes follows the grouping and the pick: the
+// member count of every cluster at the record that is written, 4 bytes a record, and the level table.  The table becomes
+// `<output 1>.duplevels`; the sizes stay for the writer when FQD_FAST_SIZEOUT is set, which then plans the outputs from the
+// records' sizes with their labels and copies the windows with fqd_copy_labelled (survivor_writer.cpp), and are released
+// at once otherwise.
 bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
 {
-    const bool linked = keep_best_ || write_clusters_, modes = linked || both_strands_ || umi_sep_;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_);
+    const bool linked = keep_best_ || write_clusters_ || size_out_ || write_levels_, modes = linked || both_strands_ || umi_sep_;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, size_out_, write_levels_);
     auto give_up = [&](const std::string& why) -> bool {
         if (modes) throw FastModeRefusal(which + ": the GPU-resident run cannot take this input (" + why +
                                          "), and the streaming run cannot serve these modes");
@@ -154,6 +179,9 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     if (!modes && !any_gz_in && !(any_gz_out && deflate_on_device())) return false;
     if (modes && all_empty) {
         // no record, no cluster, nothing to choose: what the default run makes of empty files, and empty cluster files
+        // (the table of zeros is written whatever the default run makes of an empty file, behind its outputs)
+        struct LevelsOfNothing { bool on; const std::string& name; ~LevelsOfNothing() { if (on) write_cluster_lines(duplevels_text(fqd_size_levels{}), name + ".duplevels"); } }
+            levels_of_nothing{write_levels_, out[0]};
         run_ordered(S, in, out);
         if (write_clusters_) for (int s = 0; s < S; ++s) write_cluster_lines(std::string(), out[s] + ".clusters");
         return true;
@@ -163,7 +191,8 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     const size_t fetch_bytes = fetch_bytes_for(block_bytes_for(tuning_, memlimit_), memlimit_);
     FileOnDevice dev[2];
     Device<uint8_t> keep;
-    Device<uint32_t> link, owner, perm; Device<uint8_t> head;     // FQD_FAST_KEEP / FQD_FAST_CLUSTERS
+    Device<uint32_t> link, owner, perm; Device<uint8_t> head;     // FQD_FAST_KEEP / FQD_FAST_CLUSTERS / FQD_FAST_SIZEOUT / FQD_FAST_LEVELS
+    Device<uint32_t> cluster_size; fqd_size_levels levels{};      // FQD_FAST_SIZEOUT / FQD_FAST_LEVELS
     Device<uint8_t> canon, turned; Device<uint64_t> canon_off[2]; Device<uint32_t> canon_len[2];   // FQD_FAST_STRAND=both
     Device<uint8_t> umi_text; Device<uint64_t> umi_off64; Device<uint32_t> umi_len, umi_off;        // FQD_FAST_UMI
     uint32_t umi_bases = 0;
@@ -301,6 +330,13 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
                 StageClock::Scope t2("fast: ID lines of the clusters out of HBM");
                 for (int s = 0; s < S; ++s) clusters[s] = cluster_lines(eng->e, stream, dev[s], perm.p, head.p, n);
             }
+            if (size_out_ || write_levels_) {
+                StageClock::Scope t2("fast: cluster sizes on the GPU");
+                cluster_size.reserve(n);
+                engine_ok<DeviceError>(eng->e, fqd_cluster_sizes(eng->e, perm.p, head.p, n, cluster_size.p, &levels));
+                if (StageClock::on()) std::cerr << "fast: cluster sizes, " << n_clusters << " clusters, largest " << levels.largest << "\n";
+                if (!size_out_) cluster_size.release();
+            }
             perm.release(); head.release();
         }
         // everything the writer needs is reserved HERE, while the run can still hand over: once an output exists it cannot
@@ -308,16 +344,21 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         for (int s = 0; s < S; ++s) gz_out[s] = has_gz_extension(out[s]);
         FileOnDevice* files[2] = {&dev[0], &dev[1]};
         const uint32_t* idx[2] = {nullptr, nullptr};
+        if (size_out_) buffers.cluster_size = cluster_size.p;
         plan_survivors(eng->e, S, files, idx, keep.p, n, gz_out, memlimit_, buffers);
     } catch (const FastModeRefusal&) {
         throw;                                                    // nothing has been written
     } catch (const DeviceOutOfMemory&) {
+        // (what the two size switches add, named only when one of them is set)
+        const std::string sizes = !(size_out_ || write_levels_) ? std::string() :
+            std::string("; the cluster sizes of ") + (size_out_ ? "FQD_FAST_SIZEOUT" : "FQD_FAST_LEVELS") + " take 4 bytes a record more" +
+            (size_out_ ? " and the labels' places and grown sizes 8 bytes a record and file" : "");
         if (umi_sep_)
             return give_up(std::string("the text, the record arrays, the keyed bytes of FQD_FAST_UMI (mate 1's sequence bytes once more and the UMI bases of every record, 16 bytes a record)") +
                            (both_strands_ ? ", the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record)" : "") +
-                           " and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory");
-        return give_up(both_strands_ ? "the text, the record arrays, the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record) and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory"
-                                     : "the text, the record arrays and up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory");   // the streaming run needs a few blocks of HBM only
+                           " and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory" + sizes);
+        return give_up((both_strands_ ? "the text, the record arrays, the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record) and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory"
+                                     : "the text, the record arrays and up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory") + sizes);   // the streaming run needs a few blocks of HBM only
     } catch (const DeviceError& e) {
         if (modes) return give_up(e.what());
         announce_handover("the GPU-resident ordered run", e);     // nothing has been written yet
@@ -333,6 +374,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     OutputFile* sinks[2] = {&sink0, sink1.get()};
     if (write_clusters_)
         for (int s = 0; s < S; ++s) { write_cluster_lines(clusters[s], out[s] + ".clusters"); std::string().swap(clusters[s]); }
+    if (write_levels_) write_cluster_lines(duplevels_text(levels), out[0] + ".duplevels");
     {
         StageClock::Scope t("ordered/resident: survivors out of HBM");
         FileOnDevice* files[2] = {&dev[0], &dev[1]};

@@ -79,7 +79,16 @@ void plan_survivors(fqd_engine* e, int S, FileOnDevice* const* file, const uint3
     for (int s = 0; s < S; ++s) {
         SurvivorBuffers::PerFile& o = b.f[s];
         o.src_off.reserve(upto); o.dst_off.reserve(upto + 1); o.len.reserve(upto);
-        engine_ok<DeviceError>(e, fqd_output_plan(e, keep, idx[s], upto, file[s]->start.p, file[s]->size.p, o.src_off.p, o.len.p, o.dst_off.p, &o.total));
+        const uint32_t* sizes = file[s]->size.p;
+        if (b.cluster_size) {
+            // FQD_FAST_SIZEOUT: the plan from the records' sizes WITH their labels, so that len and dst_off leave the labels' room
+            if (idx[s]) throw std::logic_error("plan_survivors: labels need pair k to be record k");
+            o.label_at.reserve(upto); o.out_size.reserve(upto);
+            engine_ok<DeviceError>(e, fqd_size_labels(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), file[s]->start.p, file[s]->id_len.p, file[s]->size.p,
+                                                      keep, b.cluster_size, upto, o.label_at.p, o.out_size.p));
+            sizes = o.out_size.p;
+        }
+        engine_ok<DeviceError>(e, fqd_output_plan(e, keep, idx[s], upto, file[s]->start.p, sizes, o.src_off.p, o.len.p, o.dst_off.p, &o.total));
         o.on_device = gz_out[s] && deflate_on_device();
         // every buffer is sized once, for the largest window the writer lets through (a single record larger than that is the
         // one case that grows them later): a window a little larger than all before it must not cost a new pinned allocation
@@ -109,12 +118,13 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
     const uint32_t effort = device_deflate_effort();
     struct Out {
         Device<uint64_t>& src_off; Device<uint64_t>& dst_off; Device<uint32_t>& len; uint64_t total;
+        const uint32_t* label_at;                         // FQD_FAST_SIZEOUT: not null
         Pinned<char>* buf; Device<char>* d_win; Device<char>* d_members;
         Channel<int> free_bufs, full_bufs; int slot_id[2] = {0, 1}; size_t bytes[2] = {0, 0};
         hipEvent_t copied[2] = {nullptr, nullptr};        // the slot's window has reached its pinned buffer
         bool on_device = false;
         std::thread writer; std::exception_ptr error;
-        explicit Out(SurvivorBuffers::PerFile& p) : src_off(p.src_off), dst_off(p.dst_off), len(p.len), total(p.total), buf(p.buf), d_win(p.d_win), d_members(p.d_members), on_device(p.on_device) {}
+        explicit Out(SurvivorBuffers::PerFile& p) : src_off(p.src_off), dst_off(p.dst_off), len(p.len), total(p.total), label_at(p.label_at.p), buf(p.buf), d_win(p.d_win), d_members(p.d_members), on_device(p.on_device) {}
     };
     Out o[2] = {Out(planned->f[0]), Out(planned->f[1])};
     static int kStop = -1;
@@ -191,8 +201,13 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
                     d_win.reserve(room + 64);
                     o[s].buf[*id].reserve((o[s].on_device ? std::max<uint64_t>(room / 2, 1u << 20) : room) + 64);
                     // dst_off is absolute in the output: the window's buffer starts `lo` bytes in
-                    engine_ok(e, fqd_copy_spans(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), o[s].src_off.p + at[s], o[s].len.p + at[s], take,
-                                             reinterpret_cast<uint8_t*>(d_win.p) - lo, o[s].dst_off.p + at[s]));
+                    const uint8_t* text = reinterpret_cast<const uint8_t*>(file[s]->text.p);
+                    uint8_t* win = reinterpret_cast<uint8_t*>(d_win.p) - lo;
+                    if (planned->cluster_size)
+                        engine_ok(e, fqd_copy_labelled(e, text, o[s].src_off.p + at[s], o[s].len.p + at[s], o[s].label_at + at[s], planned->cluster_size + at[s], take,
+                                                       win, o[s].dst_off.p + at[s]));
+                    else
+                        engine_ok(e, fqd_copy_spans(e, text, o[s].src_off.p + at[s], o[s].len.p + at[s], take, win, o[s].dst_off.p + at[s]));
                     uint64_t out_bytes = bytes;
                     const char* from = d_win.p;
                     if (o[s].on_device) {

@@ -654,6 +654,44 @@ int  fqd_umi_find(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, 
 int  fqd_umi_reads(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, const uint32_t* umi_off, const fqd_umi_info* info,
                    const fqd_reads* mate0, uint64_t n, uint8_t* out, uint64_t out_capacity, uint64_t* out_off, uint32_t* out_len);
 
+/* ---- FQD_FAST_SIZEOUT / FQD_FAST_LEVELS: every cluster's member count, as a `;size=N` label on the written record and as
+ * a table of duplication levels (added within ABI version 5: purely additive; no existing entry launches anything new).
+ * Rules and proofs: csrc/fqd_size_core.hpp.  (perm, head) is an order of the n records and a flag at the first place of
+ * every cluster — fqd_group_owners', after fqd_seq_pick_best where a member was picked, so that the record at a head's
+ * place is the written one; any other (perm, head) of that shape, fqd_sort_seqs / fqd_seq_heads' among them, serves as well.
+ *
+ * fqd_cluster_sizes: device memory only (levels: host, may be NULL).  A run is a head place and the places behind it up
+ * to the next head; size[perm[k]] (n uint32) = the run's length where head[k], 0 at every other place: every entry of size
+ * is written exactly once.  levels: row L counts the runs whose length falls in level L — 1 .. 9 one row each, then 10-49,
+ * 50-99, 100-499, 500-999, 1000-4999, 5000-9999, 10000+ — and sums their lengths; largest = the longest run (all 0 for
+ * n = 0).  n < 2^31.  head[0] == 0 with n > 0 is FQD_ERR_ARG and nothing is written to size.  A max-scan in three launches
+ * (tile values, one block over them, the places), no block waiting for another; 4 bytes of scratch per 2048 records.
+ * Returns after the stream has drained.
+ *
+ * fqd_size_labels: device memory only; all arrays per record r < n of ONE file (called once per file).  The ID line of
+ * record r is the id_len[r] bytes at text + start[r], its '\n' included.  label_at[r] (n uint32) = the length of '@' / '>'
+ * and the line's first word: the position of the first ' ', '\t', '\r' or '\n' behind position 0, id_len[r] where there is
+ * none.  An ID line that already holds `;size=` is not looked at.  out_size[r] (n uint32) = rec_size[r] + 6 + the decimal
+ * digits of size[r] where keep[r], rec_size[r] elsewhere: what fqd_output_plan takes for `sizes`, so that its len and dst_off
+ * leave room for the labels.  A kept record whose size is 0 is FQD_ERR_ARG (counted on the device, reported once).  Returns
+ * after the stream has drained.
+ *
+ * fqd_copy_labelled: fqd_copy_spans with a label, all arrays per span i < n (a window passes every array advanced by its
+ * first span, as with fqd_copy_spans).  len[i] is the GROWN length that fqd_output_plan produced from out_size, 0 for a span
+ * that is not written.  dst + dst_off[i] receives the first label_at[i] bytes at src + src_off[i], then `;size=<size[i]>`,
+ * then the remaining len[i] - label_at[i] - label bytes of the source.  Only launches. */
+typedef struct fqd_size_levels {
+    uint64_t clusters[16];      /* runs per level */
+    uint64_t records[16];       /* the sum of their lengths */
+    uint32_t largest;
+    uint32_t reserved;
+} fqd_size_levels;
+int  fqd_cluster_sizes(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint64_t n, uint32_t* size, fqd_size_levels* levels);
+int  fqd_size_labels(fqd_engine* e, const uint8_t* text, const uint64_t* start, const uint32_t* id_len, const uint32_t* rec_size,
+                     const uint8_t* keep, const uint32_t* size, uint64_t n, uint32_t* label_at, uint32_t* out_size);
+int  fqd_copy_labelled(fqd_engine* e, const uint8_t* src, const uint64_t* src_off, const uint32_t* len, const uint32_t* label_at,
+                       const uint32_t* size, uint64_t n, uint8_t* dst, const uint64_t* dst_off);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
