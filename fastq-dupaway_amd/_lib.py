@@ -54,6 +54,11 @@ class UmiInfo(C.Structure):                                  # fqd_umi_info
                 ("bad_reason", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class UmiMergeInfo(C.Structure):                             # fqd_umi_merge_info
+    _fields_ = [("nodes", C.c_uint64), ("groups", C.c_uint64), ("merged", C.c_uint64), ("largest", C.c_uint32), ("sweeps", C.c_uint32),
+                ("max_group", C.c_uint32), ("over_limit_nodes", C.c_uint32), ("over_limit_first", C.c_uint64), ("stage_ms", C.c_float * 4)]
+
+
 class SizeLevels(C.Structure):                               # fqd_size_levels
     _fields_ = [("clusters", C.c_uint64 * 16), ("records", C.c_uint64 * 16), ("largest", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -159,6 +164,8 @@ def load_library():
     L.fqd_canonical_reads.argtypes = [vp, C.POINTER(ReadsDesc), u64, vp, u64, vp, vp, vp, vp, vp, C.POINTER(u64)]
     L.fqd_umi_find.argtypes = [vp, vp, vp, vp, u64, i32, vp, C.POINTER(UmiInfo)]
     L.fqd_umi_reads.argtypes = [vp, vp, vp, vp, C.POINTER(UmiInfo), C.POINTER(ReadsDesc), u64, vp, u64, vp, vp]
+    L.fqd_umi_merge.argtypes = [vp, vp, vp, vp, C.POINTER(UmiInfo), vp, vp, vp, u64, u32, vp, C.POINTER(UmiMergeInfo)]
+    L.fqd_owners_to_keep.argtypes = [vp, vp, u64, vp]
     L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
     L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_copy_labelled.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]

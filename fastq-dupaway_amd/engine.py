@@ -347,6 +347,23 @@ class Engine:
         self._check(self._L.fqd_umi_reads(self._h, self._p(text), self._p(id_start), self._p(umi_off), C.byref(info) if info is not None else None,
                                           self._desc([mate0]), n, self._p(out), cap, self._p(out_off), self._p(out_len)))
 
+    # -- FQD_FAST_UMI_MISMATCH (csrc/fqd_umi_merge.hip) ------------------------------------------------
+    def umi_merge(self, text, id_start, umi_off, info, owner_exact, owner_seq, size, n: int, distance: int, owner_out, out=True):
+        """owner_out[i] (n uint32, device) = the first record of record i's cluster after the exact UMI clusters of one
+        sequence within `distance` mismatches were merged by the directional rule.  info: what umi_find returned;
+        owner_exact / owner_seq: owners of the runs keyed UMI ‖ sequence and sequence alone; size: cluster_sizes over the
+        exact grouping.  Returns the call's fqd_umi_merge_info (_lib.UmiMergeInfo); out=None hands the library a null
+        pointer, which it refuses."""
+        got = _lib.UmiMergeInfo() if out else None
+        self._check(self._L.fqd_umi_merge(self._h, self._p(text), self._p(id_start), self._p(umi_off), C.byref(info) if info is not None else None,
+                                          self._p(owner_exact), self._p(owner_seq), self._p(size), n, distance, self._p(owner_out),
+                                          C.byref(got) if out else None))
+        return got
+
+    def owners_to_keep(self, owner, n: int, keep):
+        """keep[i] = (owner[i] == i)."""
+        self._check(self._L.fqd_owners_to_keep(self._h, self._p(owner), n, self._p(keep)))
+
     # -- FQD_FAST_SIZEOUT / FQD_FAST_LEVELS (csrc/fqd_size.hip) --------------------------------------------
     def cluster_sizes(self, perm, head, n: int, size, levels: bool = True):
         """size[perm[k]] (n uint32, device) = the length of the run of (perm, head) that starts at place k where head[k], 0 at

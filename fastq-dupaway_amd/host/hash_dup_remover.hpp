@@ -60,7 +60,7 @@ public:
                   const std::string& outfile1, const std::string& outfile2, bool unordered);
     const Summary& summary() const { return summary_; }
 private:
-    void read_fast_modes(bool unordered);             // FQD_FAST_KEEP / _CLUSTERS / _STRAND / _UMI / _SIZEOUT / _LEVELS: read and checked before any GPU call
+    void read_fast_modes(bool unordered);             // FQD_FAST_KEEP / _CLUSTERS / _STRAND / _UMI / _UMI_MISMATCH / _SIZEOUT / _LEVELS: read and checked before any GPU call
     void run_ordered(int n_files, const std::string* in, const std::string* out);
     bool run_ordered_resident(int n_files, const std::string* in, const std::string* out);   // false: not taken, nothing touched
     void run_ordered_multi(int n_files, const std::string* in, const std::string* out);
@@ -79,6 +79,7 @@ private:
     bool                write_clusters_ = false; // FQD_FAST_CLUSTERS=1
     bool                both_strands_ = false;   // FQD_FAST_STRAND=both
     int                 umi_sep_ = 0;            // FQD_FAST_UMI=colon|underscore: ':' or '_', 0 for off
+    int                 umi_mismatch_ = 0;       // FQD_FAST_UMI_MISMATCH=1|2: UMI clusters of one sequence this many bases apart merge; 0 for off
     bool                size_out_ = false;       // FQD_FAST_SIZEOUT=1
     bool                write_levels_ = false;   // FQD_FAST_LEVELS=1
 };
@@ -90,8 +91,9 @@ namespace detail { uint32_t device_deflate_effort(); uint64_t seq_range_target_b
 // FQD_FAST_KEEP=first|best and FQD_FAST_CLUSTERS=1 of the `--fast` mode (run_resident.cpp, the one place each is read):
 // throw on any other value of FQD_FAST_KEEP.  main() asks before a run starts, HashDupRemover before any GPU call.
 // FQD_FAST_STRAND=given|both (same place): throws on any other value; asked by HashDupRemover::read_fast_modes only, which
-// runs before any GPU call.  FQD_FAST_UMI=off|colon|underscore likewise: 0, ':' or '_'.  FQD_FAST_SIZEOUT=1 and
+// runs before any GPU call.  FQD_FAST_UMI=off|colon|underscore likewise: 0, ':' or '_', and
+// FQD_FAST_UMI_MISMATCH=0|1|2: its value.  FQD_FAST_SIZEOUT=1 and
 // FQD_FAST_LEVELS=1 are parsed as FQD_FAST_CLUSTERS is.
-namespace detail { bool fast_keep_best(); bool fast_clusters(); bool fast_both_strands(); int fast_umi(); bool fast_sizeout(); bool fast_levels(); }
+namespace detail { bool fast_keep_best(); bool fast_clusters(); bool fast_both_strands(); int fast_umi(); int fast_umi_mismatch(); bool fast_sizeout(); bool fast_levels(); }
 
 } // namespace fqdhost

@@ -49,6 +49,18 @@ int fast_umi()
     throw std::runtime_error(std::string("FQD_FAST_UMI must be 'off', 'colon' or 'underscore', not '") + v + "'");
 }
 
+// FQD_FAST_UMI_MISMATCH=0|1|2: with FQD_FAST_UMI, whether the exact UMI clusters of one sequence (pair of sequences) whose UMIs
+// differ in at most that many bases are merged by UMI-tools' directional rule (csrc/fqd_umi_merge_core.hpp).  0 (and unset):
+// a UMI is told apart by every base.  Read here and nowhere else.
+int fast_umi_mismatch()
+{
+    const char* v = std::getenv("FQD_FAST_UMI_MISMATCH");
+    if (!v || std::strcmp(v, "0") == 0) return 0;
+    if (std::strcmp(v, "1") == 0) return 1;
+    if (std::strcmp(v, "2") == 0) return 2;
+    throw std::runtime_error(std::string("FQD_FAST_UMI_MISMATCH must be 0, 1 or 2, not '") + v + "'");
+}
+
 // FQD_FAST_SIZEOUT=1: every record `--fast` writes carries `;size=N`, its cluster's member count, behind the first word of
 // its ID line (csrc/fqd_size_core.hpp).  Read here and nowhere else.
 bool fast_sizeout()
@@ -76,11 +88,13 @@ struct FastModeRefusal : std::runtime_error { using std::runtime_error::runtime_
 
 const char* umi_switch(int umi) { return umi == ':' ? "FQD_FAST_UMI=colon" : umi == '_' ? "FQD_FAST_UMI=underscore" : nullptr; }
 
-std::string fast_switches(bool best, bool clusters, bool both, int umi, bool sizeout, bool levels)
+const char* mismatch_switch(int mismatch) { return mismatch == 1 ? "FQD_FAST_UMI_MISMATCH=1" : mismatch == 2 ? "FQD_FAST_UMI_MISMATCH=2" : nullptr; }
+
+std::string fast_switches(bool best, bool clusters, bool both, int umi, int mismatch, bool sizeout, bool levels)
 {
     std::string s;
     for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr, umi_switch(umi),
-                             sizeout ? "FQD_FAST_SIZEOUT=1" : nullptr, levels ? "FQD_FAST_LEVELS=1" : nullptr})
+                             mismatch_switch(mismatch), sizeout ? "FQD_FAST_SIZEOUT=1" : nullptr, levels ? "FQD_FAST_LEVELS=1" : nullptr})
         if (name) s += (s.empty() ? "" : " and ") + std::string(name);
     return s;
 }
@@ -102,17 +116,20 @@ std::string umi_reason(uint32_t reason, int sep)
 
 } // namespace
 
-// Everything about the six switches that their values and the command line decide, before any GPU call.
+// Everything about the seven switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     keep_best_ = fast_keep_best();
     write_clusters_ = fast_clusters();
     both_strands_ = fast_both_strands();
     umi_sep_ = fast_umi();
+    umi_mismatch_ = fast_umi_mismatch();
     size_out_ = fast_sizeout();
     write_levels_ = fast_levels();
-    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_ && !size_out_ && !write_levels_) return;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, size_out_, write_levels_);
+    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_ && !umi_mismatch_ && !size_out_ && !write_levels_) return;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_);
+    if (umi_mismatch_ && !umi_sep_)
+        throw FastModeRefusal(std::string(mismatch_switch(umi_mismatch_)) + " merges the UMIs that FQD_FAST_UMI finds: set FQD_FAST_UMI=colon or FQD_FAST_UMI=underscore as well");
     if (unordered)
         throw FastModeRefusal(which + " with --unordered: these modes run on ordered inputs only");
     if (tuning_.devices.size() > 1)
@@ -150,10 +167,18 @@ void HashDupRemover::read_fast_modes(bool unordered)
 // `<output 1>.duplevels`; the sizes stay for the writer when FQD_FAST_SIZEOUT is set, which then plans the outputs from the
 // records' sizes with their labels and copies the windows with fqd_copy_labelled (survivor_writer.cpp), and are released
 // at once otherwise.
+//
+// With FQD_FAST_UMI_MISMATCH=1|2 (also `linked`; FQD_FAST_UMI is set) the engine is used TWICE: the submit loop as above
+// keyed `UMI bases ‖ sequence` gives the exact owners and, through fqd_group_owners and fqd_cluster_sizes, every exact
+// cluster's count; after fqd_engine_reset the same batches go in again keyed by the sequences alone (the given or the
+// canonical descriptors), into the same flags and links, which gives every record's sequence group.  fqd_umi_merge makes
+// the merged owners of the three, fqd_owners_to_keep the flags, and the grouping, the pick, the cluster files, the sizes
+// and the writers follow as they do for any other owners.  The canonical and keyed buffers stay until the second pass is
+// through, the UMI offsets until the merge is.
 bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
 {
-    const bool linked = keep_best_ || write_clusters_ || size_out_ || write_levels_, modes = linked || both_strands_ || umi_sep_;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, size_out_, write_levels_);
+    const bool linked = keep_best_ || write_clusters_ || size_out_ || write_levels_ || umi_mismatch_, modes = linked || both_strands_ || umi_sep_;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_);
     auto give_up = [&](const std::string& why) -> bool {
         if (modes) throw FastModeRefusal(which + ": the GPU-resident run cannot take this input (" + why +
                                          "), and the streaming run cannot serve these modes");
@@ -195,6 +220,8 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     Device<uint32_t> cluster_size; fqd_size_levels levels{};      // FQD_FAST_SIZEOUT / FQD_FAST_LEVELS
     Device<uint8_t> canon, turned; Device<uint64_t> canon_off[2]; Device<uint32_t> canon_len[2];   // FQD_FAST_STRAND=both
     Device<uint8_t> umi_text; Device<uint64_t> umi_off64; Device<uint32_t> umi_len, umi_off;        // FQD_FAST_UMI
+    Device<uint32_t> owner_seq, exact_size, merged_owner;        // FQD_FAST_UMI_MISMATCH
+    fqd_umi_info umi_info{};
     uint32_t umi_bases = 0;
     std::string clusters[2];
     uint64_t n = 0, dups = 0;
@@ -245,6 +272,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         StageClock::Scope t("ordered/resident: dedup on the GPU");
         keep.reserve(n);
         if (linked) { link.reserve(n); owner.reserve(n); perm.reserve(n); head.reserve(n); }
+        if (umi_mismatch_) { owner_seq.reserve(n); exact_size.reserve(n); merged_owner.reserve(n); }
         // no more than a file's sequence bytes — a FASTQ record is its sequence twice (bases, qualities) and at least six
         // more bytes, a FASTA record its sequence and at least three
         auto seq_bound = [&](int s) -> uint64_t {
@@ -273,7 +301,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
             StageClock::Scope t2("fast: UMI, find and pack on the GPU");
             const uint8_t* text0 = reinterpret_cast<const uint8_t*>(dev[0].text.p);
             umi_off.reserve(n);
-            fqd_umi_info info{};
+            fqd_umi_info& info = umi_info;
             engine_ok<DeviceError>(eng->e, fqd_umi_find(eng->e, text0, dev[0].start.p, dev[0].id_len.p, n, umi_sep_, umi_off.p, &info));
             if (info.bad_record != FQD_UMI_NO_RECORD)
                 throw FastModeRefusal(std::string(umi_switch(umi_sep_)) + ": record " + std::to_string(info.bad_record) + " (counted from 0) of " + in[0] +
@@ -287,40 +315,76 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
             engine_ok<DeviceError>(eng->e, fqd_umi_reads(eng->e, text0, dev[0].start.p, umi_off.p, &info, &mate0, n, umi_text.p, bound, umi_off64.p, umi_len.p));
             if (StageClock::on()) std::cerr << "fast: UMI, " << umi_bases << " bases behind the last '" << char(umi_sep_) << "' of the first word\n";
         }
-        const size_t kBatch = 16u << 20;
-        int rc = FQD_OK;
-        for (size_t a = 0; a < n && rc == FQD_OK; a += kBatch) {
-            fqd_reads seg[2] = {};
-            for (int s = 0; s < S; ++s) {
-                seg[s].bases = both_strands_ ? canon.p : reinterpret_cast<const uint8_t*>(dev[s].text.p);
-                seg[s].offsets = (both_strands_ ? canon_off[s].p : dev[s].seq_off.p) + a;
-                seg[s].lengths = (both_strands_ ? canon_len[s].p : dev[s].seq_len.p) + a;
+        // all n records through the engine, batch by batch; with_umi: mate 1 as `UMI bases ‖ sequence`
+        auto submit_all = [&](bool with_umi) -> int {
+            const size_t kBatch = 16u << 20;
+            int rc = FQD_OK;
+            for (size_t a = 0; a < n && rc == FQD_OK; a += kBatch) {
+                fqd_reads seg[2] = {};
+                for (int s = 0; s < S; ++s) {
+                    seg[s].bases = both_strands_ ? canon.p : reinterpret_cast<const uint8_t*>(dev[s].text.p);
+                    seg[s].offsets = (both_strands_ ? canon_off[s].p : dev[s].seq_off.p) + a;
+                    seg[s].lengths = (both_strands_ ? canon_len[s].p : dev[s].seq_len.p) + a;
+                }
+                if (with_umi) seg[0] = fqd_reads{umi_text.p, umi_off64.p + a, umi_len.p + a, 0, 0};
+                if (linked) rc = fqd_submit_linked(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, link.p + a, a + kBatch < n ? 0 : 1);
+                else rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
             }
-            if (umi_sep_) seg[0] = fqd_reads{umi_text.p, umi_off64.p + a, umi_len.p + a, 0, 0};
-            if (linked) rc = fqd_submit_linked(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, link.p + a, a + kBatch < n ? 0 : 1);
-            else rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
-        }
-        if (rc == FQD_OK) rc = fqd_engine_sync(eng->e);
+            if (rc == FQD_OK) rc = fqd_engine_sync(eng->e);
+            return rc;
+        };
+        int rc = submit_all(umi_sep_ != 0);
         if (rc == FQD_ERR_BAD_BASE)                              // the streaming run cuts the output where the reference does
             return give_up(std::string(fqd_last_error(eng->e)) + (umi_sep_ ? "; a position in mate 1 counts the " + std::to_string(umi_bases) + " UMI bases in front of the sequence" : std::string()));
         if (rc != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e));
+        fqd_umi_merge_info merged{};
+        if (umi_mismatch_) {
+            // the exact owners and counts, then the same records once more without their UMIs: the flags and links of the
+            // first pass are used up by fqd_owners and taken again
+            uint64_t exact_clusters = 0;
+            {
+                StageClock::Scope t2("fast: UMI mismatches, exact owners and counts on the GPU");
+                engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner.p));
+                engine_ok<DeviceError>(eng->e, fqd_group_owners(eng->e, owner.p, n, perm.p, head.p, &exact_clusters));
+                engine_ok<DeviceError>(eng->e, fqd_cluster_sizes(eng->e, perm.p, head.p, n, exact_size.p, nullptr));
+            }
+            {
+                StageClock::Scope t2("fast: UMI mismatches, second pass by sequence on the GPU");
+                engine_ok<DeviceError>(eng->e, fqd_engine_reset(eng->e));
+                if (submit_all(false) != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e));
+                engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner_seq.p));
+            }
+            StageClock::Scope t2("fast: UMI mismatches, networks on the GPU");
+            engine_ok<DeviceError>(eng->e, fqd_umi_merge(eng->e, reinterpret_cast<const uint8_t*>(dev[0].text.p), dev[0].start.p, umi_off.p, &umi_info, owner.p,
+                                                         owner_seq.p, exact_size.p, n, uint32_t(umi_mismatch_), merged_owner.p, &merged));
+            if (merged.over_limit_first != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal(std::string(mismatch_switch(umi_mismatch_)) + ": the sequence of record " + std::to_string(merged.over_limit_first) + " (counted from 0) of " + in[0] +
+                                      " stands under " + std::to_string(merged.over_limit_nodes) + " different UMIs, a network of at most " + std::to_string(merged.max_group) +
+                                      " is merged (amplicon-style data: deduplicate it by exact UMI, without the switch)");
+            if (merged.nodes != exact_clusters) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
+            engine_ok<DeviceError>(eng->e, fqd_owners_to_keep(eng->e, merged_owner.p, n, keep.p));
+            if (StageClock::on())
+                std::cerr << "fast: UMI mismatches <= " << umi_mismatch_ << ", " << merged.merged << " of " << merged.nodes << " exact clusters merged into others, largest network "
+                          << merged.largest << ", " << merged.sweeps << " sweeps\n";
+            owner_seq.release(); exact_size.release();
+        }
         canon.release(); turned.release();                       // the last submit is through: nothing below reads a turned byte
         for (int s = 0; s < 2; ++s) { canon_off[s].release(); canon_len[s].release(); }
         umi_text.release(); umi_off64.release(); umi_len.release(); umi_off.release();
         if (std::getenv("FQD_TEST_FAIL_RESIDENT")) throw DeviceError("GPU engine: forced by FQD_TEST_FAIL_RESIDENT");      // tests: the hand-over is announced
         fqd_stats st{};
         fqd_get_stats(eng->e, &st);
-        dups = st.duplicates;
+        dups = umi_mismatch_ ? n - (merged.nodes - merged.merged) : st.duplicates;
         FileOnDevice* all_files[2] = {&dev[0], &dev[1]};
         if (linked) {
             uint64_t n_clusters = 0;
             {
                 StageClock::Scope t2("fast: owners and clusters on the GPU");
-                engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner.p));
-                engine_ok<DeviceError>(eng->e, fqd_group_owners(eng->e, owner.p, n, perm.p, head.p, &n_clusters));
+                if (!umi_mismatch_) engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner.p));
+                engine_ok<DeviceError>(eng->e, fqd_group_owners(eng->e, umi_mismatch_ ? merged_owner.p : owner.p, n, perm.p, head.p, &n_clusters));
             }
             if (n_clusters + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
-            link.release(); owner.release();
+            link.release(); owner.release(); merged_owner.release();
             if (keep_best_) {
                 const uint64_t moved = pick_best_members(eng->e, S, all_files, n, head.p, perm.p, "fast: best-quality pick on the GPU");
                 engine_ok<DeviceError>(eng->e, fqd_heads_to_keep(eng->e, perm.p, head.p, n, keep.p));
@@ -349,10 +413,12 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     } catch (const FastModeRefusal&) {
         throw;                                                    // nothing has been written
     } catch (const DeviceOutOfMemory&) {
-        // (what the two size switches add, named only when one of them is set)
-        const std::string sizes = !(size_out_ || write_levels_) ? std::string() :
+        // (what the two size switches and the mismatch switch add, named only when one of them is set)
+        const std::string sizes = (!(size_out_ || write_levels_) ? std::string() :
             std::string("; the cluster sizes of ") + (size_out_ ? "FQD_FAST_SIZEOUT" : "FQD_FAST_LEVELS") + " take 4 bytes a record more" +
-            (size_out_ ? " and the labels' places and grown sizes 8 bytes a record and file" : "");
+            (size_out_ ? " and the labels' places and grown sizes 8 bytes a record and file" : "")) +
+            (!umi_mismatch_ ? std::string() : std::string("; FQD_FAST_UMI_MISMATCH takes 12 bytes a record more (the owners by sequence, the exact counts, the merged owners) "
+                                                          "and, while it merges, 4 bytes a record and up to 66 bytes an exact cluster"));
         if (umi_sep_)
             return give_up(std::string("the text, the record arrays, the keyed bytes of FQD_FAST_UMI (mate 1's sequence bytes once more and the UMI bases of every record, 16 bytes a record)") +
                            (both_strands_ ? ", the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record)" : "") +

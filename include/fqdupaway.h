@@ -692,6 +692,49 @@ int  fqd_size_labels(fqd_engine* e, const uint8_t* text, const uint64_t* start, 
 int  fqd_copy_labelled(fqd_engine* e, const uint8_t* src, const uint64_t* src_off, const uint32_t* len, const uint32_t* label_at,
                        const uint32_t* size, uint64_t n, uint8_t* dst, const uint64_t* dst_off);
 
+/* ---- FQD_FAST_UMI_MISMATCH=1|2: exact UMI clusters of one sequence that differ in a base or two are one molecule (added
+ * within ABI version 5: purely additive; no existing entry launches anything new).  Rule and proofs:
+ * csrc/fqd_umi_merge_core.hpp.  A sequence group is the records with identical sequences (UMI left out); a node is one
+ * distinct B(U) in it — an exact cluster — with count = its members and first = its first record; dist = the places at which
+ * two nodes' B(U) differ; a -> b where dist(a, b) <= distance and count(a) >= 2 count(b) - 1 (UMI-tools' directional rule);
+ * root(v) = the node of highest count, on equal counts of lowest first record, among v and the nodes with a directed path
+ * to v; the records of all nodes with one root are one merged cluster.
+ *
+ * fqd_umi_merge: device memory only (info, out: host).  text, id_start, umi_off and info are fqd_umi_find's over the same n
+ * records (an info that names a refused record: FQD_ERR_ARG).  owner_exact = fqd_owners of the run keyed B(U) ‖ sequence,
+ * owner_seq = fqd_owners of a second run over the same records keyed by the sequences alone, size = fqd_cluster_sizes over
+ * the exact grouping (the count at every cluster's first record).  distance is 1 or 2 (anything else: FQD_ERR_ARG).
+ * owner_out[i] (n uint32) = the first record, in input order, of record i's merged cluster; fqd_group_owners takes it.
+ * owner_out must not overlap the inputs.  *out: nodes; groups = the sequence groups of more than one node; merged = the
+ * nodes whose root is another node (the merged clusters number nodes - merged); largest = the nodes of the largest group;
+ * sweeps = the most label sweeps that changed something in any group (the longest shortest path from a root to a node of
+ * its cluster); max_group = FQD_UMI_MERGE_MAX_GROUP.  A group of more nodes than that is refused: over_limit_first = the
+ * lowest first record of such a group (FQD_UMI_NO_RECORD: there is none), over_limit_nodes = that group's nodes; the call
+ * returns FQD_OK, owner_out is NOT written, merged and sweeps are 0.  An owner behind its record, or size 0 at a record that
+ * owns itself, is FQD_ERR_ARG (counted on the device, nothing written).  n < 2^31.  Scratch during the call: 4 bytes a record
+ * and (34 + 8 * ceil(n_bases / 16)) bytes a node.  Two 64-bit results come back in between (the nodes, the groups per size
+ * class); returns after the stream has drained.  stage_ms is a diagnostic (tools/umi_merge_probe.py): the wall time of the
+ * three parts the call's own waits cut it into, launches and waits included. */
+#define FQD_UMI_MERGE_MAX_GROUP 4096u
+typedef struct fqd_umi_merge_info {
+    uint64_t nodes;
+    uint64_t groups;
+    uint64_t merged;
+    uint32_t largest;
+    uint32_t sweeps;
+    uint32_t max_group;
+    uint32_t over_limit_nodes;
+    uint64_t over_limit_first;
+    float    stage_ms[4];       /* host wall time between the call's own synchronisations: nodes, group + classes, merge + spread; 0 */
+} fqd_umi_merge_info;
+int  fqd_umi_merge(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, const uint32_t* umi_off, const fqd_umi_info* info,
+                   const uint32_t* owner_exact, const uint32_t* owner_seq, const uint32_t* size, uint64_t n, uint32_t distance,
+                   uint32_t* owner_out, fqd_umi_merge_info* out);
+
+/* keep[i] = (owner[i] == i) for i < n (all device): the flags of a grouping given by its owners — what fqd_umi_merge leaves.
+ * Only launches. */
+int  fqd_owners_to_keep(fqd_engine* e, const uint32_t* owner, uint64_t n, uint8_t* keep);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
