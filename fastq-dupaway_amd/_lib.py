@@ -63,6 +63,10 @@ class SizeLevels(C.Structure):                               # fqd_size_levels
     _fields_ = [("clusters", C.c_uint64 * 16), ("records", C.c_uint64 * 16), ("largest", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SizeOrderInfo(C.Structure):                            # fqd_size_order_info
+    _fields_ = [("written", C.c_uint64), ("large", C.c_uint64), ("largest", C.c_uint32), ("tier2_passes", C.c_uint32)]
+
+
 UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
 UMI_OK, UMI_NO_SEPARATOR, UMI_EMPTY, UMI_TOO_LONG, UMI_BAD_BYTE, UMI_NO_BASE, UMI_SHAPE_DIFFERS = range(7)
 
@@ -169,6 +173,10 @@ def load_library():
     L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
     L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_copy_labelled.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]
+    L.fqd_size_filter.argtypes = [vp, vp, u64, u32, u32, vp, C.POINTER(u64), C.POINTER(u64)]
+    L.fqd_size_order.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
+    L.fqd_size_order_ex.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(SizeOrderInfo)]
+    L.fqd_take_u32.argtypes = [vp, vp, vp, u64, vp]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

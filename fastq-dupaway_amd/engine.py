@@ -385,6 +385,33 @@ class Engine:
         self._check(self._L.fqd_copy_labelled(self._h, self._p(src), self._p(src_off), self._p(lens), self._p(label_at), self._p(size), n,
                                               self._p(dst), self._p(dst_off)))
 
+    # -- FQD_FAST_SORT / FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE (csrc/fqd_size_order.hip) ----------------------
+    def size_filter(self, size, n: int, min_size: int, max_size: int, keep):
+        """Clears keep[r] of every kept record whose cluster size lies outside min_size .. max_size (max_size 0: no upper
+        bound).  Returns (clusters taken out, their records)."""
+        clusters, records = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.fqd_size_filter(self._h, self._p(size), n, min_size, max_size, self._p(keep), C.byref(clusters), C.byref(records)))
+        return int(clusters.value), int(records.value)
+
+    def size_order(self, perm, head, size, keep, n: int, order) -> int:
+        """order[k] (uint32, device) = the record written k-th: the kept head places of (perm, head) sorted stably by cluster
+        size descending.  Returns W, the number of entries written; order[W:] is not touched."""
+        written = C.c_uint64(0)
+        self._check(self._L.fqd_size_order(self._h, self._p(perm), self._p(head), self._p(size), self._p(keep), n, self._p(order), C.byref(written)))
+        return int(written.value)
+
+    def size_order_info(self, perm, head, size, keep, n: int, order):
+        """size_order through fqd_size_order_ex: returns (W, the call's fqd_size_order_info (_lib.SizeOrderInfo): W, the
+        clusters above 255 members that tier 2 sorted apart, the largest size and tier 2's passes)."""
+        written, info = C.c_uint64(0), _lib.SizeOrderInfo()
+        self._check(self._L.fqd_size_order_ex(self._h, self._p(perm), self._p(head), self._p(size), self._p(keep), n, self._p(order),
+                                              C.byref(written), C.byref(info)))
+        return int(written.value), info
+
+    def take_u32(self, values, idx, n: int, out):
+        """out[k] = values[idx[k]] for k < n (uint32, device)."""
+        self._check(self._L.fqd_take_u32(self._h, self._p(values), self._p(idx), n, self._p(out)))
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

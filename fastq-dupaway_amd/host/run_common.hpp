@@ -143,6 +143,7 @@ struct Device {
         p = static_cast<T*>(np); cap = std::max<size_t>(n, 1024);
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void swap(Device& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
 };
 
 // Thread-safe pool / queue of raw pointers.
@@ -436,7 +437,10 @@ ParseFailure append_file(const std::string& name, Format format, bool want_tag, 
 // an allocation that fails after the sinks exist leaves truncated files and no way back to the streaming run).
 // With FQD_FAST_SIZEOUT the caller sets cluster_size (device, per record: fqd_cluster_sizes) before plan_survivors: every
 // file then gets label_at and out_size (fqd_size_labels, 8 bytes a record and file), the plan is made from out_size, and the
-// windows are copied by fqd_copy_labelled.  Only for runs whose pair k is record k (idx[s] == nullptr).
+// windows are copied by fqd_copy_labelled.  Where pair k is record idx[s][k] (FQD_FAST_SORT=size: both files take the written
+// order) the caller also sets record_keep and records, the flags and the number of the RECORDS: fqd_size_labels runs per
+// record, the plan takes out_size through the index, and label_at and the sizes are gathered into arrays per pair
+// (fqd_take_u32: 4 bytes a pair and file, 4 bytes a pair), which label_at and cluster_size name from then on.
 struct SurvivorBuffers {
     struct PerFile {
         Device<uint64_t> src_off, dst_off; Device<uint32_t> len; uint64_t total = 0;
@@ -446,6 +450,8 @@ struct SurvivorBuffers {
     } f[2];
     uint64_t window = 0, roomy = 0;
     const uint32_t* cluster_size = nullptr;           // FQD_FAST_SIZEOUT: the label of record r says cluster_size[r]
+    const uint8_t* record_keep = nullptr; uint64_t records = 0;      // FQD_FAST_SIZEOUT through an index: the flags per record
+    Device<uint32_t> taken_size;                      // ... and the sizes per pair: cluster_size names it once the plan is made
     bool planned = false;
 };
 

@@ -77,6 +77,34 @@ bool fast_levels()
     return v && std::atoi(v) != 0;
 }
 
+// FQD_FAST_SORT=input|size: the order of the records `--fast` writes.  input (and unset): the input's; size: by decreasing
+// cluster size, clusters of one size in the order of their first member (csrc/fqd_size_order_core.hpp).  Read here and
+// nowhere else.
+bool fast_sort_by_size()
+{
+    const char* v = std::getenv("FQD_FAST_SORT");
+    if (!v || std::strcmp(v, "input") == 0) return false;
+    if (std::strcmp(v, "size") == 0) return true;
+    throw std::runtime_error(std::string("FQD_FAST_SORT must be 'input' or 'size', not '") + v + "'");
+}
+
+// FQD_FAST_MINSIZE=N / FQD_FAST_MAXSIZE=N: a cluster of fewer / more members than N is not written.  `unset` where the
+// variable is not set (1 and 0, "no bound").  Read here and nowhere else.
+uint32_t fast_size_bound(const char* name, uint32_t unset)
+{
+    const char* v = std::getenv(name);
+    if (!v) return unset;
+    uint64_t x = 0;
+    size_t digits = 0;
+    for (const char* p = v; *p; ++p, ++digits) {
+        if (*p < '0' || *p > '9' || digits >= 10) { digits = 0; break; }
+        x = x * 10 + uint64_t(*p - '0');
+    }
+    if (!digits || x < 1 || x > 0x7FFFFFFFull)
+        throw std::runtime_error(std::string(name) + " must be a decimal integer in 1 .. 2147483647, not '" + v + "'");
+    return uint32_t(x);
+}
+
 } // namespace detail
 
 namespace {
@@ -90,12 +118,16 @@ const char* umi_switch(int umi) { return umi == ':' ? "FQD_FAST_UMI=colon" : umi
 
 const char* mismatch_switch(int mismatch) { return mismatch == 1 ? "FQD_FAST_UMI_MISMATCH=1" : mismatch == 2 ? "FQD_FAST_UMI_MISMATCH=2" : nullptr; }
 
-std::string fast_switches(bool best, bool clusters, bool both, int umi, int mismatch, bool sizeout, bool levels)
+// (min_size 1 and max_size 0 are the two bounds that take nothing out: not named)
+std::string fast_switches(bool best, bool clusters, bool both, int umi, int mismatch, bool sizeout, bool levels, bool by_size, uint32_t min_size, uint32_t max_size)
 {
     std::string s;
     for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr, umi_switch(umi),
-                             mismatch_switch(mismatch), sizeout ? "FQD_FAST_SIZEOUT=1" : nullptr, levels ? "FQD_FAST_LEVELS=1" : nullptr})
+                             mismatch_switch(mismatch), sizeout ? "FQD_FAST_SIZEOUT=1" : nullptr, levels ? "FQD_FAST_LEVELS=1" : nullptr,
+                             by_size ? "FQD_FAST_SORT=size" : nullptr})
         if (name) s += (s.empty() ? "" : " and ") + std::string(name);
+    if (min_size > 1) s += (s.empty() ? "" : " and ") + ("FQD_FAST_MINSIZE=" + std::to_string(min_size));
+    if (max_size) s += (s.empty() ? "" : " and ") + ("FQD_FAST_MAXSIZE=" + std::to_string(max_size));
     return s;
 }
 
@@ -116,9 +148,15 @@ std::string umi_reason(uint32_t reason, int sep)
 
 } // namespace
 
-// Everything about the seven switches that their values and the command line decide, before any GPU call.
+// Everything about the ten switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
+    sort_by_size_ = fast_sort_by_size();
+    min_size_ = fast_size_bound("FQD_FAST_MINSIZE", 1);
+    max_size_ = fast_size_bound("FQD_FAST_MAXSIZE", 0);
+    if (max_size_ && max_size_ < min_size_)
+        throw FastModeRefusal("FQD_FAST_MAXSIZE=" + std::to_string(max_size_) + " is below FQD_FAST_MINSIZE=" + std::to_string(min_size_) + ": no cluster could be written");
+    size_filter_ = min_size_ > 1 || max_size_ != 0;
     keep_best_ = fast_keep_best();
     write_clusters_ = fast_clusters();
     both_strands_ = fast_both_strands();
@@ -126,8 +164,8 @@ void HashDupRemover::read_fast_modes(bool unordered)
     umi_mismatch_ = fast_umi_mismatch();
     size_out_ = fast_sizeout();
     write_levels_ = fast_levels();
-    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_ && !umi_mismatch_ && !size_out_ && !write_levels_) return;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_);
+    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_ && !umi_mismatch_ && !size_out_ && !write_levels_ && !sort_by_size_ && !size_filter_) return;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_);
     if (umi_mismatch_ && !umi_sep_)
         throw FastModeRefusal(std::string(mismatch_switch(umi_mismatch_)) + " merges the UMIs that FQD_FAST_UMI finds: set FQD_FAST_UMI=colon or FQD_FAST_UMI=underscore as well");
     if (unordered)
@@ -168,6 +206,13 @@ void HashDupRemover::read_fast_modes(bool unordered)
 // records' sizes with their labels and copies the windows with fqd_copy_labelled (survivor_writer.cpp), and are released
 // at once otherwise.
 //
+// With FQD_FAST_SORT=size, FQD_FAST_MINSIZE or FQD_FAST_MAXSIZE (all `linked`) the sizes are computed as well, while perm and
+// head still exist: fqd_size_filter clears the flags of the clusters outside the bounds — behind the cluster files and the
+// level table, which hold all clusters — and fqd_size_order writes the records that stay in order of decreasing cluster
+// size.  The writer then takes that order as its index for both files, a set flag for each of its entries, and as many
+// pairs as it has entries; with FQD_FAST_SIZEOUT the labels are still found per record and brought into the order by
+// fqd_take_u32 (survivor_writer.cpp).  A filter without the order needs no index: the cleared flags go through the plan.
+//
 // With FQD_FAST_UMI_MISMATCH=1|2 (also `linked`; FQD_FAST_UMI is set) the engine is used TWICE: the submit loop as above
 // keyed `UMI bases ‖ sequence` gives the exact owners and, through fqd_group_owners and fqd_cluster_sizes, every exact
 // cluster's count; after fqd_engine_reset the same batches go in again keyed by the sequences alone (the given or the
@@ -177,8 +222,14 @@ void HashDupRemover::read_fast_modes(bool unordered)
 // through, the UMI offsets until the merge is.
 bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
 {
-    const bool linked = keep_best_ || write_clusters_ || size_out_ || write_levels_ || umi_mismatch_, modes = linked || both_strands_ || umi_sep_;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_);
+    const bool linked = keep_best_ || write_clusters_ || size_out_ || write_levels_ || umi_mismatch_ || sort_by_size_ || size_filter_, modes = linked || both_strands_ || umi_sep_;
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_);
+    // FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE: what `-v` says behind its first line
+    auto print_not_written = [&](uint64_t clusters, uint64_t records) {
+        if (verbose_ && size_filter_)
+            std::cout << clusters << " clusters holding " << records << (S == 1 ? " reads" : " read pairs") << " were not written (FQD_FAST_MINSIZE=" << min_size_
+                      << ", FQD_FAST_MAXSIZE=" << (max_size_ ? std::to_string(max_size_) : std::string("none")) << ").\n";
+    };
     auto give_up = [&](const std::string& why) -> bool {
         if (modes) throw FastModeRefusal(which + ": the GPU-resident run cannot take this input (" + why +
                                          "), and the streaming run cannot serve these modes");
@@ -207,7 +258,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         // (the table of zeros is written whatever the default run makes of an empty file, behind its outputs)
         struct LevelsOfNothing { bool on; const std::string& name; ~LevelsOfNothing() { if (on) write_cluster_lines(duplevels_text(fqd_size_levels{}), name + ".duplevels"); } }
             levels_of_nothing{write_levels_, out[0]};
-        run_ordered(S, in, out);
+        run_ordered(S, in, out);                                  // (no cluster, no filter: the second `-v` line is not said either)
         if (write_clusters_) for (int s = 0; s < S; ++s) write_cluster_lines(std::string(), out[s] + ".clusters");
         return true;
     }
@@ -217,7 +268,9 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     FileOnDevice dev[2];
     Device<uint8_t> keep;
     Device<uint32_t> link, owner, perm; Device<uint8_t> head;     // FQD_FAST_KEEP / FQD_FAST_CLUSTERS / FQD_FAST_SIZEOUT / FQD_FAST_LEVELS
-    Device<uint32_t> cluster_size; fqd_size_levels levels{};      // FQD_FAST_SIZEOUT / FQD_FAST_LEVELS
+    Device<uint32_t> cluster_size; fqd_size_levels levels{};      // FQD_FAST_SIZEOUT / FQD_FAST_LEVELS / FQD_FAST_SORT / FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE
+    Device<uint32_t> order; Device<uint8_t> all_kept;             // FQD_FAST_SORT=size: the written order and a set flag for each of its entries
+    uint64_t n_written = 0, dropped_clusters = 0, dropped_records = 0;
     Device<uint8_t> canon, turned; Device<uint64_t> canon_off[2]; Device<uint32_t> canon_len[2];   // FQD_FAST_STRAND=both
     Device<uint8_t> umi_text; Device<uint64_t> umi_off64; Device<uint32_t> umi_len, umi_off;        // FQD_FAST_UMI
     Device<uint32_t> owner_seq, exact_size, merged_owner;        // FQD_FAST_UMI_MISMATCH
@@ -394,29 +447,64 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
                 StageClock::Scope t2("fast: ID lines of the clusters out of HBM");
                 for (int s = 0; s < S; ++s) clusters[s] = cluster_lines(eng->e, stream, dev[s], perm.p, head.p, n);
             }
-            if (size_out_ || write_levels_) {
+            if (size_out_ || write_levels_ || sort_by_size_ || size_filter_) {
                 StageClock::Scope t2("fast: cluster sizes on the GPU");
                 cluster_size.reserve(n);
                 engine_ok<DeviceError>(eng->e, fqd_cluster_sizes(eng->e, perm.p, head.p, n, cluster_size.p, &levels));
                 if (StageClock::on()) std::cerr << "fast: cluster sizes, " << n_clusters << " clusters, largest " << levels.largest << "\n";
-                if (!size_out_) cluster_size.release();
             }
+            if (size_filter_) {
+                // the clusters outside the bounds leave the flags; the cluster files and the level table have been made of all
+                StageClock::Scope t2("fast: size filter on the GPU");
+                engine_ok<DeviceError>(eng->e, fqd_size_filter(eng->e, cluster_size.p, n, min_size_, max_size_, keep.p, &dropped_clusters, &dropped_records));
+                if (StageClock::on()) std::cerr << "fast: size filter, " << dropped_clusters << " clusters of " << dropped_records << " records not written\n";
+            }
+            n_written = n_clusters - dropped_clusters;
+            if (sort_by_size_) {
+                order.reserve(std::max<uint64_t>(n_written, 1)); all_kept.reserve(std::max<uint64_t>(n_written, 1));    // (a filter may leave nothing)
+                uint64_t w = 0;
+                fqd_size_order_info sorted{};
+                {
+                    StageClock::Scope t2("fast: abundance order on the GPU");
+                    engine_ok<DeviceError>(eng->e, fqd_size_order_ex(eng->e, perm.p, head.p, cluster_size.p, keep.p, n, order.p, &w, &sorted));
+                    if (w != n_written) throw DeviceError("GPU engine: internal error (the written order and the kept clusters differ in number)");
+                    if (w) HIP_OK(hipMemsetAsync(all_kept.p, 1, w, stream));
+                    HIP_OK(hipStreamSynchronize(stream));
+                }
+                // (what the call counted: the pairs of tier 1's bucket 0, which alone went through tier 2's passes)
+                if (StageClock::on())
+                    std::cerr << "fast: abundance order, " << w << " clusters written, " << sorted.large << " of them above 255 members sorted apart\n";
+            }
+            if (!size_out_) cluster_size.release();
             perm.release(); head.release();
         }
         // everything the writer needs is reserved HERE, while the run can still hand over: once an output exists it cannot
         bool gz_out[2] = {false, false};
         for (int s = 0; s < S; ++s) gz_out[s] = has_gz_extension(out[s]);
         FileOnDevice* files[2] = {&dev[0], &dev[1]};
-        const uint32_t* idx[2] = {nullptr, nullptr};
         if (size_out_) buffers.cluster_size = cluster_size.p;
-        plan_survivors(eng->e, S, files, idx, keep.p, n, gz_out, memlimit_, buffers);
+        if (sort_by_size_) {
+            // pair k is record order[k], of both files; every pair is written
+            const uint32_t* idx[2] = {order.p, order.p};
+            buffers.record_keep = keep.p; buffers.records = n;
+            plan_survivors(eng->e, S, files, idx, all_kept.p, n_written, gz_out, memlimit_, buffers);
+            cluster_size.release();                               // (the writer has the sizes in written order)
+        } else {
+            const uint32_t* idx[2] = {nullptr, nullptr};
+            plan_survivors(eng->e, S, files, idx, keep.p, n, gz_out, memlimit_, buffers);
+        }
     } catch (const FastModeRefusal&) {
         throw;                                                    // nothing has been written
     } catch (const DeviceOutOfMemory&) {
         // (what the two size switches and the mismatch switch add, named only when one of them is set)
-        const std::string sizes = (!(size_out_ || write_levels_) ? std::string() :
-            std::string("; the cluster sizes of ") + (size_out_ ? "FQD_FAST_SIZEOUT" : "FQD_FAST_LEVELS") + " take 4 bytes a record more" +
+        const bool sized = size_out_ || write_levels_ || sort_by_size_ || size_filter_;
+        const std::string sizes = (!sized ? std::string() :
+            std::string("; the cluster sizes of ") + (size_out_ ? "FQD_FAST_SIZEOUT" : write_levels_ ? "FQD_FAST_LEVELS" : sort_by_size_ ? "FQD_FAST_SORT" : "FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE") +
+            " take 4 bytes a record more" +
             (size_out_ ? " and the labels' places and grown sizes 8 bytes a record and file" : "")) +
+            (!sort_by_size_ ? std::string() : std::string("; FQD_FAST_SORT=size takes 4 bytes a cluster for the written order, 1 byte a cluster for its flags and, while it sorts, "
+                                                          "24 bytes a cluster of scratch (the scratch of the grouping serves where it is as large)") +
+                                              (size_out_ ? ", and the labels' places and the sizes in written order 4 bytes a cluster and file and 4 bytes a cluster" : "")) +
             (!umi_mismatch_ ? std::string() : std::string("; FQD_FAST_UMI_MISMATCH takes 12 bytes a record more (the owners by sequence, the exact counts, the merged owners) "
                                                           "and, while it merges, 4 bytes a record and up to 66 bytes an exact cluster"));
         if (umi_sep_)
@@ -444,13 +532,17 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     {
         StageClock::Scope t("ordered/resident: survivors out of HBM");
         FileOnDevice* files[2] = {&dev[0], &dev[1]};
+        const uint32_t* by_order[2] = {order.p, order.p};
         const uint32_t* idx[2] = {nullptr, nullptr};
-        write_survivors(eng->e, stream, S, files, idx, keep.p, n, dups, sinks, format_, memlimit_, true, &buffers);
+        // (the count of pairs that are not written only sizes the windows)
+        if (sort_by_size_) write_survivors(eng->e, stream, S, files, by_order, all_kept.p, n_written, 0, sinks, format_, memlimit_, true, &buffers);
+        else write_survivors(eng->e, stream, S, files, idx, keep.p, n, dups + dropped_clusters, sinks, format_, memlimit_, true, &buffers);
     }
     if (tuning_.leave_memory_to_exit) g_leave_memory_to_exit = true;
     StageClock::report();
     summary_.total = n; summary_.duplicates = dups; summary_.unmatched = 0;
     if (verbose_) print_summary(S, summary_.total, summary_.duplicates);
+    print_not_written(dropped_clusters, dropped_records);
     return true;
 }
 

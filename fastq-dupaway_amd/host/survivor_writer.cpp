@@ -80,15 +80,26 @@ void plan_survivors(fqd_engine* e, int S, FileOnDevice* const* file, const uint3
         SurvivorBuffers::PerFile& o = b.f[s];
         o.src_off.reserve(upto); o.dst_off.reserve(upto + 1); o.len.reserve(upto);
         const uint32_t* sizes = file[s]->size.p;
+        Device<uint32_t> taken_at;                            // FQD_FAST_SIZEOUT through an index: label_at per pair, while it is gathered
         if (b.cluster_size) {
             // FQD_FAST_SIZEOUT: the plan from the records' sizes WITH their labels, so that len and dst_off leave the labels' room
-            if (idx[s]) throw std::logic_error("plan_survivors: labels need pair k to be record k");
-            o.label_at.reserve(upto); o.out_size.reserve(upto);
+            // (through an index the labels are still found per RECORD: the plan below takes out_size at idx[s][k])
+            if (idx[s] && !b.record_keep) throw std::logic_error("plan_survivors: labels through an index need the records' own flags");
+            const uint64_t records = idx[s] ? b.records : upto;
+            o.label_at.reserve(records); o.out_size.reserve(records);
+            if (idx[s]) taken_at.reserve(upto);
             engine_ok<DeviceError>(e, fqd_size_labels(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), file[s]->start.p, file[s]->id_len.p, file[s]->size.p,
-                                                      keep, b.cluster_size, upto, o.label_at.p, o.out_size.p));
+                                                      idx[s] ? b.record_keep : keep, b.cluster_size, records, o.label_at.p, o.out_size.p));
             sizes = o.out_size.p;
         }
         engine_ok<DeviceError>(e, fqd_output_plan(e, keep, idx[s], upto, file[s]->start.p, sizes, o.src_off.p, o.len.p, o.dst_off.p, &o.total));
+        if (b.cluster_size && idx[s]) {
+            // label_at per pair from here on: the window loop advances it by pairs
+            engine_ok<DeviceError>(e, fqd_take_u32(e, o.label_at.p, idx[s], upto, taken_at.p));
+            engine_ok<DeviceError>(e, fqd_engine_sync(e));
+            o.label_at.swap(taken_at);                       // (the per-record array leaves with this scope)
+            o.out_size.release();
+        }
         o.on_device = gz_out[s] && deflate_on_device();
         // every buffer is sized once, for the largest window the writer lets through (a single record larger than that is the
         // one case that grows them later): a window a little larger than all before it must not cost a new pinned allocation
@@ -98,6 +109,13 @@ void plan_survivors(fqd_engine* e, int S, FileOnDevice* const* file, const uint3
             o.buf[k].reserve((o.on_device ? std::max<uint64_t>(room / 2, 1u << 20) : room) + 64);
             if (o.on_device) o.d_members[k].reserve(fqd_bgzf_bound(room));
         }
+    }
+    if (b.cluster_size && idx[0]) {
+        // every file's labels are found: the sizes per pair as well (one index serves all files of such a run)
+        b.taken_size.reserve(upto);
+        engine_ok<DeviceError>(e, fqd_take_u32(e, b.cluster_size, idx[0], upto, b.taken_size.p));
+        engine_ok<DeviceError>(e, fqd_engine_sync(e));
+        b.cluster_size = b.taken_size.p;
     }
     b.planned = true;
 }

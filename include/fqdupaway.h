@@ -692,6 +692,54 @@ int  fqd_size_labels(fqd_engine* e, const uint8_t* text, const uint64_t* start, 
 int  fqd_copy_labelled(fqd_engine* e, const uint8_t* src, const uint64_t* src_off, const uint32_t* len, const uint32_t* label_at,
                        const uint32_t* size, uint64_t n, uint8_t* dst, const uint64_t* dst_off);
 
+/* ---- FQD_FAST_SORT=size / FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE: the written records in order of decreasing cluster size,
+ * and clusters outside size bounds not written at all (added within ABI version 5: purely additive; no existing entry
+ * launches anything new).  Rules and proofs: csrc/fqd_size_order_core.hpp.  (perm, head), size and keep are those of
+ * fqd_cluster_sizes and fqd_size_labels above: size[r] = the member count at every written record r, 0 elsewhere, and
+ * keep[r] set at the written records.
+ *
+ * fqd_size_filter: device memory only (the two counts: host, each may be NULL).  For every record r < n with keep[r] set
+ * and size[r] < min_size, or max_size != 0 and size[r] > max_size: keep[r] is cleared, *clusters_dropped counts it and
+ * *records_dropped adds size[r].  No other flag is written.  1 <= min_size <= 2^31-1; max_size = 0 (no upper bound) or
+ * min_size <= max_size <= 2^31-1; n < 2^31; anything else is FQD_ERR_ARG and nothing is launched.  A kept record whose size
+ * is 0 — flags and sizes that do not belong together — is FQD_ERR_ARG (counted on the device, reported once): nothing is
+ * promised about keep then, and the counts stay 0.  One streaming pass, the counters summed wave by wave and block by block
+ * (three atomics a block, none per record).  Returns after the stream has drained.
+ *
+ * fqd_size_order: device memory only (n_written: host, not NULL).  A kept place is a place s with head[s] set and
+ * keep[perm[s]] set.  Take the kept places in ascending order and sort them STABLY by size[perm[s]] descending:
+ * order[k] = perm[s] of the k-th, for k < W = *n_written, their number.  Among clusters of one size the one whose first
+ * member stands earlier in the input comes first (the order of `<output>.clusters`).  Entries of order at W and beyond are
+ * not touched; W = 0 leaves order as it is.  n < 2^31.  head[0] == 0 with n > 0 is FQD_ERR_ARG, and so is a kept place of size
+ * 0: in both cases nothing is written to order.  An order that is no permutation of 0 .. n-1 never makes the call read
+ * outside keep[0 .. n) and size[0 .. n) or write outside order[0 .. n): W <= the number of head places <= n.  The kept places
+ * are compacted by an exclusive count in three launches (tile counts, one block over them, the places; no block waits for
+ * another), then sorted in two tiers: ONE 8-bit pass over all W entries tells the sizes 1 .. 255 apart and collects the L
+ * clusters above 255 members, and only those L <= n / 256 entries go through the passes that the largest size needs.
+ * Scratch during the call: 8 bytes per 2048 records and 24 bytes per kept place, plus 1 KiB per 4096 kept places.  Two counts
+ * come back in between (W; L and the largest size); returns after the stream has drained.
+ *
+ * fqd_size_order_ex: fqd_size_order, which also reports what the call itself counted and did (info: host, may be NULL;
+ * all 0 where the call fails or writes nothing): written = W; large = L, the pairs tier 2 sorted apart; largest = the largest
+ * size among the kept places; tier2_passes = the 8-bit passes launched over those L pairs (0 where L <= 1 or all of them
+ * have one size).
+ *
+ * fqd_take_u32: out[k] = values[idx[k]] for k < n (all device; values holds an entry for every idx[k], which the caller
+ * guarantees; out overlaps neither input): brings a per-record array into the written order.  Only launches. */
+int  fqd_size_filter(fqd_engine* e, const uint32_t* size, uint64_t n, uint32_t min_size, uint32_t max_size, uint8_t* keep,
+                     uint64_t* clusters_dropped, uint64_t* records_dropped);
+int  fqd_size_order(fqd_engine* e, const uint32_t* perm, const uint8_t* head, const uint32_t* size, const uint8_t* keep, uint64_t n,
+                    uint32_t* order, uint64_t* n_written);
+typedef struct fqd_size_order_info {
+    uint64_t written;
+    uint64_t large;
+    uint32_t largest;
+    uint32_t tier2_passes;
+} fqd_size_order_info;
+int  fqd_size_order_ex(fqd_engine* e, const uint32_t* perm, const uint8_t* head, const uint32_t* size, const uint8_t* keep, uint64_t n,
+                       uint32_t* order, uint64_t* n_written, fqd_size_order_info* info);
+int  fqd_take_u32(fqd_engine* e, const uint32_t* values, const uint32_t* idx, uint64_t n, uint32_t* out);
+
 /* ---- FQD_FAST_UMI_MISMATCH=1|2: exact UMI clusters of one sequence that differ in a base or two are one molecule (added
  * within ABI version 5: purely additive; no existing entry launches anything new).  Rule and proofs:
  * csrc/fqd_umi_merge_core.hpp.  A sequence group is the records with identical sequences (UMI left out); a node is one
