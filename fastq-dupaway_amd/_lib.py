@@ -67,6 +67,15 @@ class SizeOrderInfo(C.Structure):                            # fqd_size_order_in
     _fields_ = [("written", C.c_uint64), ("large", C.c_uint64), ("largest", C.c_uint32), ("tier2_passes", C.c_uint32)]
 
 
+class SizeinInfo(C.Structure):                               # fqd_sizein_info
+    _fields_ = [("bad_record", C.c_uint64), ("bad_reason", C.c_uint32), ("reserved", C.c_uint32), ("annotated", C.c_uint64),
+                ("total_weight", C.c_uint64)]
+
+
+class WeightsInfo(C.Structure):                              # fqd_weights_info
+    _fields_ = [("over_record", C.c_uint64), ("over_sum", C.c_uint64)]
+
+
 UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
 UMI_OK, UMI_NO_SEPARATOR, UMI_EMPTY, UMI_TOO_LONG, UMI_BAD_BYTE, UMI_NO_BASE, UMI_SHAPE_DIFFERS = range(7)
 
@@ -177,6 +186,10 @@ def load_library():
     L.fqd_size_order.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64)]
     L.fqd_size_order_ex.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.POINTER(u64), C.POINTER(SizeOrderInfo)]
     L.fqd_take_u32.argtypes = [vp, vp, vp, u64, vp]
+    L.fqd_size_annotations.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(SizeinInfo)]
+    L.fqd_cluster_weights.argtypes = [vp, vp, vp, vp, u64, vp, C.POINTER(SizeLevels), C.POINTER(WeightsInfo)]
+    L.fqd_size_relabel.argtypes = [vp, vp, vp, vp, vp, u64, vp]
+    L.fqd_copy_relabelled.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_extract_tags.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.fqd_join_tags.argtypes = [vp, C.POINTER(TagsDesc), C.POINTER(TagsDesc), C.POINTER(JoinDesc)]
     L.fqd_gather_seqs.argtypes = [vp, vp, u64, vp, vp, vp, vp]

@@ -412,6 +412,38 @@ class Engine:
         """out[k] = values[idx[k]] for k < n (uint32, device)."""
         self._check(self._L.fqd_take_u32(self._h, self._p(values), self._p(idx), n, self._p(out)))
 
+    # -- FQD_FAST_SIZEIN (csrc/fqd_sizein.hip) ------------------------------------------------------------
+    def size_annotations(self, text, start, id_len, n: int, expect, weight, label_at, cut, info=True):
+        """Per record of one file (device memory; weight, label_at and cut may each be None): weight = what the `;size=N`
+        annotation in the first word of its ID line says, 1 where there is none; label_at = the annotation's start, or the
+        first word's end; cut = the annotation's length, 0 for none.  expect: file 1's weights for a call over file 2, else
+        None.  Returns the call's fqd_sizein_info (_lib.SizeinInfo): the lowest refused record with its reason, the records
+        with an annotation and the total weight.  info=None hands the library a null pointer, which it refuses."""
+        got = _lib.SizeinInfo() if info else None
+        self._check(self._L.fqd_size_annotations(self._h, self._p(text), self._p(start), self._p(id_len), n, self._p(expect), self._p(weight),
+                                                 self._p(label_at), self._p(cut), C.byref(got) if info else None))
+        return got
+
+    def cluster_weights(self, perm, head, weight, n: int, size, levels: bool = True, info=True):
+        """cluster_sizes with a weight per record: size[perm[k]] = the sum of weight over the run that starts at place k where
+        head[k], 0 at every other place.  Returns (the call's fqd_size_levels or None, its fqd_weights_info
+        (_lib.WeightsInfo): the lowest record at the head of a run above 2^31-1 and that run's sum)."""
+        got = _lib.SizeLevels() if levels else None
+        over = _lib.WeightsInfo() if info else None
+        self._check(self._L.fqd_cluster_weights(self._h, self._p(perm), self._p(head), self._p(weight), n, self._p(size),
+                                                C.byref(got) if levels else None, C.byref(over) if info else None))
+        return got, over
+
+    def size_relabel(self, rec_size, keep, size, cut, n: int, out_size):
+        """out_size = the record's size without its annotation's cut bytes and with the label of size where keep is set:
+        output_plan's `sizes`."""
+        self._check(self._L.fqd_size_relabel(self._h, self._p(rec_size), self._p(keep), self._p(size), self._p(cut), n, self._p(out_size)))
+
+    def copy_relabelled(self, src, src_off, lens, label_at, cut, size, n: int, dst, dst_off):
+        """copy_labelled that leaves the cut[i] bytes behind label_at[i] out.  dst may be an address (int)."""
+        self._check(self._L.fqd_copy_relabelled(self._h, self._p(src), self._p(src_off), self._p(lens), self._p(label_at), self._p(cut), self._p(size), n,
+                                                self._p(dst), self._p(dst_off)))
+
     def extract_tags(self, text, id_start, id_len, n: int, tag_off, tag_len):
         self._check(self._L.fqd_extract_tags(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tag_off), self._p(tag_len)))
 

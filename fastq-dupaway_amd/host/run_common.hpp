@@ -441,10 +441,14 @@ ParseFailure append_file(const std::string& name, Format format, bool want_tag, 
 // order) the caller also sets record_keep and records, the flags and the number of the RECORDS: fqd_size_labels runs per
 // record, the plan takes out_size through the index, and label_at and the sizes are gathered into arrays per pair
 // (fqd_take_u32: 4 bytes a pair and file, 4 bytes a pair), which label_at and cluster_size name from then on.
+// With FQD_FAST_SIZEIN as well the caller sets size_in: label_at is then the start of the annotation a line already carries
+// and cut its length (fqd_size_annotations, 4 bytes a record and file more), out_size leaves the annotation out
+// (fqd_size_relabel), cut travels with label_at through the index, and the windows are copied by fqd_copy_relabelled.
 struct SurvivorBuffers {
     struct PerFile {
         Device<uint64_t> src_off, dst_off; Device<uint32_t> len; uint64_t total = 0;
         Device<uint32_t> label_at, out_size;          // FQD_FAST_SIZEOUT only
+        Device<uint32_t> cut;                         // ... with FQD_FAST_SIZEIN
         Pinned<char> buf[2]; Device<char> d_win[2], d_members[2];      // a slot = pinned buffer k + the device buffers k
         bool on_device = false;                       // .gz: windows leave the device as finished BGZF members
     } f[2];
@@ -452,6 +456,7 @@ struct SurvivorBuffers {
     const uint32_t* cluster_size = nullptr;           // FQD_FAST_SIZEOUT: the label of record r says cluster_size[r]
     const uint8_t* record_keep = nullptr; uint64_t records = 0;      // FQD_FAST_SIZEOUT through an index: the flags per record
     Device<uint32_t> taken_size;                      // ... and the sizes per pair: cluster_size names it once the plan is made
+    bool size_in = false;                             // FQD_FAST_SIZEIN: the label replaces the annotation
     bool planned = false;
 };
 

@@ -105,6 +105,15 @@ uint32_t fast_size_bound(const char* name, uint32_t unset)
     return uint32_t(x);
 }
 
+// FQD_FAST_SIZEIN=1: a `;size=N` that the first word of an ID line already carries is the record's weight, a cluster's size
+// is the sum of its members' weights, and with FQD_FAST_SIZEOUT the new label takes the old annotation's place
+// (csrc/fqd_sizein_core.hpp).  Read here and nowhere else.
+bool fast_sizein()
+{
+    const char* v = std::getenv("FQD_FAST_SIZEIN");
+    return v && std::atoi(v) != 0;
+}
+
 } // namespace detail
 
 namespace {
@@ -119,12 +128,13 @@ const char* umi_switch(int umi) { return umi == ':' ? "FQD_FAST_UMI=colon" : umi
 const char* mismatch_switch(int mismatch) { return mismatch == 1 ? "FQD_FAST_UMI_MISMATCH=1" : mismatch == 2 ? "FQD_FAST_UMI_MISMATCH=2" : nullptr; }
 
 // (min_size 1 and max_size 0 are the two bounds that take nothing out: not named)
-std::string fast_switches(bool best, bool clusters, bool both, int umi, int mismatch, bool sizeout, bool levels, bool by_size, uint32_t min_size, uint32_t max_size)
+std::string fast_switches(bool best, bool clusters, bool both, int umi, int mismatch, bool sizeout, bool levels, bool by_size, uint32_t min_size, uint32_t max_size,
+                          bool sizein)
 {
     std::string s;
     for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr, umi_switch(umi),
                              mismatch_switch(mismatch), sizeout ? "FQD_FAST_SIZEOUT=1" : nullptr, levels ? "FQD_FAST_LEVELS=1" : nullptr,
-                             by_size ? "FQD_FAST_SORT=size" : nullptr})
+                             by_size ? "FQD_FAST_SORT=size" : nullptr, sizein ? "FQD_FAST_SIZEIN=1" : nullptr})
         if (name) s += (s.empty() ? "" : " and ") + std::string(name);
     if (min_size > 1) s += (s.empty() ? "" : " and ") + ("FQD_FAST_MINSIZE=" + std::to_string(min_size));
     if (max_size) s += (s.empty() ? "" : " and ") + ("FQD_FAST_MAXSIZE=" + std::to_string(max_size));
@@ -146,9 +156,23 @@ std::string umi_reason(uint32_t reason, int sep)
     return "its UMI was refused";
 }
 
+// Why fqd_size_annotations refuses a record (enum fqd_sizein_reason), in the words of csrc/fqd_sizein_core.hpp.
+std::string sizein_reason(uint32_t reason)
+{
+    switch (reason) {
+    case FQD_SIZEIN_NO_DIGITS: return "the `;size=` in the first word of its ID line is followed by no digit";
+    case FQD_SIZEIN_BAD_END: return "the digits of its `;size=` are followed by something other than ';' or the end of the ID line's first word";
+    case FQD_SIZEIN_ZERO: return "its annotation says `;size=0`: a record stands for at least one read";
+    case FQD_SIZEIN_TOO_LARGE: return "its `;size=` has more than 10 digits or says more than 2147483647";
+    case FQD_SIZEIN_TWICE: return "the first word of its ID line holds `;size=` twice";
+    case FQD_SIZEIN_MATES_DIFFER: return "its `;size=` does not say what the record's annotation in file 1 says (1 where file 1 has none)";
+    }
+    return "its `;size=` annotation was refused";
+}
+
 } // namespace
 
-// Everything about the ten switches that their values and the command line decide, before any GPU call.
+// Everything about the eleven switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     sort_by_size_ = fast_sort_by_size();
@@ -164,8 +188,12 @@ void HashDupRemover::read_fast_modes(bool unordered)
     umi_mismatch_ = fast_umi_mismatch();
     size_out_ = fast_sizeout();
     write_levels_ = fast_levels();
+    size_in_ = fast_sizein();
+    if (size_in_ && !size_out_ && !write_levels_ && !sort_by_size_ && !size_filter_)
+        throw FastModeRefusal("FQD_FAST_SIZEIN=1 changes what a cluster's size is and nothing else: set one of FQD_FAST_SIZEOUT=1, FQD_FAST_LEVELS=1, FQD_FAST_SORT=size, "
+                              "FQD_FAST_MINSIZE (above 1) or FQD_FAST_MAXSIZE as well, which read the sizes");
     if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_ && !umi_mismatch_ && !size_out_ && !write_levels_ && !sort_by_size_ && !size_filter_) return;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_);
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_, size_in_);
     if (umi_mismatch_ && !umi_sep_)
         throw FastModeRefusal(std::string(mismatch_switch(umi_mismatch_)) + " merges the UMIs that FQD_FAST_UMI finds: set FQD_FAST_UMI=colon or FQD_FAST_UMI=underscore as well");
     if (unordered)
@@ -213,6 +241,12 @@ void HashDupRemover::read_fast_modes(bool unordered)
 // pairs as it has entries; with FQD_FAST_SIZEOUT the labels are still found per record and brought into the order by
 // fqd_take_u32 (survivor_writer.cpp).  A filter without the order needs no index: the cleared flags go through the plan.
 //
+// With FQD_FAST_SIZEIN=1 (beside at least one of the five size switches) fqd_size_annotations reads every record's weight off
+// its ID line where fqd_umi_find runs, before the first submit — file 1 gives the weights, file 2 is held against them, and a
+// record it refuses ends the run —, fqd_cluster_weights stands wherever fqd_cluster_sizes would, and the weights are released
+// after the last such call.  Everything that reads sizes reads the weighted ones; the writer parses the annotations' places
+// once more per file (survivor_writer.cpp), so nothing but the weights is held in between.
+//
 // With FQD_FAST_UMI_MISMATCH=1|2 (also `linked`; FQD_FAST_UMI is set) the engine is used TWICE: the submit loop as above
 // keyed `UMI bases ‖ sequence` gives the exact owners and, through fqd_group_owners and fqd_cluster_sizes, every exact
 // cluster's count; after fqd_engine_reset the same batches go in again keyed by the sequences alone (the given or the
@@ -223,7 +257,7 @@ void HashDupRemover::read_fast_modes(bool unordered)
 bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
 {
     const bool linked = keep_best_ || write_clusters_ || size_out_ || write_levels_ || umi_mismatch_ || sort_by_size_ || size_filter_, modes = linked || both_strands_ || umi_sep_;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_);
+    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_, size_in_);
     // FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE: what `-v` says behind its first line
     auto print_not_written = [&](uint64_t clusters, uint64_t records) {
         if (verbose_ && size_filter_)
@@ -274,6 +308,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     Device<uint8_t> canon, turned; Device<uint64_t> canon_off[2]; Device<uint32_t> canon_len[2];   // FQD_FAST_STRAND=both
     Device<uint8_t> umi_text; Device<uint64_t> umi_off64; Device<uint32_t> umi_len, umi_off;        // FQD_FAST_UMI
     Device<uint32_t> owner_seq, exact_size, merged_owner;        // FQD_FAST_UMI_MISMATCH
+    Device<uint32_t> weight;                                     // FQD_FAST_SIZEIN: what every record stands for, while sizes are made
     fqd_umi_info umi_info{};
     uint32_t umi_bases = 0;
     std::string clusters[2];
@@ -368,6 +403,30 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
             engine_ok<DeviceError>(eng->e, fqd_umi_reads(eng->e, text0, dev[0].start.p, umi_off.p, &info, &mate0, n, umi_text.p, bound, umi_off64.p, umi_len.p));
             if (StageClock::on()) std::cerr << "fast: UMI, " << umi_bases << " bases behind the last '" << char(umi_sep_) << "' of the first word\n";
         }
+        if (size_in_) {
+            // the weights, before anything else is spent on an input with a malformed annotation
+            StageClock::Scope t2("fast: size annotations on the GPU");
+            weight.reserve(n);
+            fqd_sizein_info info{};
+            for (int s = 0; s < S; ++s) {
+                fqd_sizein_info found{};
+                engine_ok<DeviceError>(eng->e, fqd_size_annotations(eng->e, reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].start.p, dev[s].id_len.p, n,
+                                                                    s ? weight.p : nullptr, s ? nullptr : weight.p, nullptr, nullptr, &found));
+                if (found.bad_record != FQD_UMI_NO_RECORD)
+                    throw FastModeRefusal("FQD_FAST_SIZEIN=1: record " + std::to_string(found.bad_record) + " (counted from 0) of " + in[s] + ": " + sizein_reason(found.bad_reason));
+                if (s == 0) info = found;
+            }
+            if (StageClock::on()) std::cerr << "fast: size annotations, " << info.annotated << " of " << n << " records annotated, total weight " << info.total_weight << "\n";
+        }
+        // fqd_cluster_sizes, or with FQD_FAST_SIZEIN the weighted sizes: a cluster above 2^31-1 ends the run
+        auto cluster_sizes = [&](uint32_t* size, fqd_size_levels* lv) {
+            if (!size_in_) { engine_ok<DeviceError>(eng->e, fqd_cluster_sizes(eng->e, perm.p, head.p, n, size, lv)); return; }
+            fqd_weights_info over{};
+            engine_ok<DeviceError>(eng->e, fqd_cluster_weights(eng->e, perm.p, head.p, weight.p, n, size, lv, &over));
+            if (over.over_record != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal("FQD_FAST_SIZEIN=1: the cluster of record " + std::to_string(over.over_record) + " (counted from 0) of " + in[0] + " has the weighted size " +
+                                      std::to_string(over.over_sum) + ": at most 2147483647");
+        };
         // all n records through the engine, batch by batch; with_umi: mate 1 as `UMI bases ‖ sequence`
         auto submit_all = [&](bool with_umi) -> int {
             const size_t kBatch = 16u << 20;
@@ -399,7 +458,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
                 StageClock::Scope t2("fast: UMI mismatches, exact owners and counts on the GPU");
                 engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner.p));
                 engine_ok<DeviceError>(eng->e, fqd_group_owners(eng->e, owner.p, n, perm.p, head.p, &exact_clusters));
-                engine_ok<DeviceError>(eng->e, fqd_cluster_sizes(eng->e, perm.p, head.p, n, exact_size.p, nullptr));
+                cluster_sizes(exact_size.p, nullptr);
             }
             {
                 StageClock::Scope t2("fast: UMI mismatches, second pass by sequence on the GPU");
@@ -450,7 +509,8 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
             if (size_out_ || write_levels_ || sort_by_size_ || size_filter_) {
                 StageClock::Scope t2("fast: cluster sizes on the GPU");
                 cluster_size.reserve(n);
-                engine_ok<DeviceError>(eng->e, fqd_cluster_sizes(eng->e, perm.p, head.p, n, cluster_size.p, &levels));
+                cluster_sizes(cluster_size.p, &levels);
+                weight.release();
                 if (StageClock::on()) std::cerr << "fast: cluster sizes, " << n_clusters << " clusters, largest " << levels.largest << "\n";
             }
             if (size_filter_) {
@@ -482,7 +542,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         bool gz_out[2] = {false, false};
         for (int s = 0; s < S; ++s) gz_out[s] = has_gz_extension(out[s]);
         FileOnDevice* files[2] = {&dev[0], &dev[1]};
-        if (size_out_) buffers.cluster_size = cluster_size.p;
+        if (size_out_) { buffers.cluster_size = cluster_size.p; buffers.size_in = size_in_; }
         if (sort_by_size_) {
             // pair k is record order[k], of both files; every pair is written
             const uint32_t* idx[2] = {order.p, order.p};
@@ -501,7 +561,9 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         const std::string sizes = (!sized ? std::string() :
             std::string("; the cluster sizes of ") + (size_out_ ? "FQD_FAST_SIZEOUT" : write_levels_ ? "FQD_FAST_LEVELS" : sort_by_size_ ? "FQD_FAST_SORT" : "FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE") +
             " take 4 bytes a record more" +
-            (size_out_ ? " and the labels' places and grown sizes 8 bytes a record and file" : "")) +
+            (size_out_ ? " and the labels' places and grown sizes 8 bytes a record and file" : "") +
+            (size_in_ ? std::string("; FQD_FAST_SIZEIN takes 4 bytes a record for the weights while the sizes are made") +
+                        (size_out_ ? " and 4 bytes a record and file for the annotations' lengths in the writer" : "") : std::string())) +
             (!sort_by_size_ ? std::string() : std::string("; FQD_FAST_SORT=size takes 4 bytes a cluster for the written order, 1 byte a cluster for its flags and, while it sorts, "
                                                           "24 bytes a cluster of scratch (the scratch of the grouping serves where it is as large)") +
                                               (size_out_ ? ", and the labels' places and the sizes in written order 4 bytes a cluster and file and 4 bytes a cluster" : "")) +

@@ -80,7 +80,7 @@ void plan_survivors(fqd_engine* e, int S, FileOnDevice* const* file, const uint3
         SurvivorBuffers::PerFile& o = b.f[s];
         o.src_off.reserve(upto); o.dst_off.reserve(upto + 1); o.len.reserve(upto);
         const uint32_t* sizes = file[s]->size.p;
-        Device<uint32_t> taken_at;                            // FQD_FAST_SIZEOUT through an index: label_at per pair, while it is gathered
+        Device<uint32_t> taken_at, taken_cut;                 // FQD_FAST_SIZEOUT through an index: label_at (and cut) per pair, while gathered
         if (b.cluster_size) {
             // FQD_FAST_SIZEOUT: the plan from the records' sizes WITH their labels, so that len and dst_off leave the labels' room
             // (through an index the labels are still found per RECORD: the plan below takes out_size at idx[s][k])
@@ -88,16 +88,29 @@ void plan_survivors(fqd_engine* e, int S, FileOnDevice* const* file, const uint3
             const uint64_t records = idx[s] ? b.records : upto;
             o.label_at.reserve(records); o.out_size.reserve(records);
             if (idx[s]) taken_at.reserve(upto);
-            engine_ok<DeviceError>(e, fqd_size_labels(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), file[s]->start.p, file[s]->id_len.p, file[s]->size.p,
-                                                      idx[s] ? b.record_keep : keep, b.cluster_size, records, o.label_at.p, o.out_size.p));
+            if (b.size_in) {
+                // FQD_FAST_SIZEIN: the label goes where the line's annotation stands, whose bytes leave the record
+                o.cut.reserve(records);
+                if (idx[s]) taken_cut.reserve(upto);
+                fqd_sizein_info info{};
+                engine_ok<DeviceError>(e, fqd_size_annotations(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), file[s]->start.p, file[s]->id_len.p, records,
+                                                               nullptr, nullptr, o.label_at.p, o.cut.p, &info));
+                if (info.bad_record != FQD_UMI_NO_RECORD) throw DeviceError("GPU engine: internal error (an annotation that the run accepted is refused by the writer)");
+                engine_ok<DeviceError>(e, fqd_size_relabel(e, file[s]->size.p, idx[s] ? b.record_keep : keep, b.cluster_size, o.cut.p, records, o.out_size.p));
+            } else {
+                engine_ok<DeviceError>(e, fqd_size_labels(e, reinterpret_cast<const uint8_t*>(file[s]->text.p), file[s]->start.p, file[s]->id_len.p, file[s]->size.p,
+                                                          idx[s] ? b.record_keep : keep, b.cluster_size, records, o.label_at.p, o.out_size.p));
+            }
             sizes = o.out_size.p;
         }
         engine_ok<DeviceError>(e, fqd_output_plan(e, keep, idx[s], upto, file[s]->start.p, sizes, o.src_off.p, o.len.p, o.dst_off.p, &o.total));
         if (b.cluster_size && idx[s]) {
             // label_at per pair from here on: the window loop advances it by pairs
             engine_ok<DeviceError>(e, fqd_take_u32(e, o.label_at.p, idx[s], upto, taken_at.p));
+            if (b.size_in) engine_ok<DeviceError>(e, fqd_take_u32(e, o.cut.p, idx[s], upto, taken_cut.p));
             engine_ok<DeviceError>(e, fqd_engine_sync(e));
             o.label_at.swap(taken_at);                       // (the per-record array leaves with this scope)
+            if (b.size_in) o.cut.swap(taken_cut);
             o.out_size.release();
         }
         o.on_device = gz_out[s] && deflate_on_device();
@@ -137,12 +150,13 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
     struct Out {
         Device<uint64_t>& src_off; Device<uint64_t>& dst_off; Device<uint32_t>& len; uint64_t total;
         const uint32_t* label_at;                         // FQD_FAST_SIZEOUT: not null
+        const uint32_t* cut;                              // ... with FQD_FAST_SIZEIN: not null
         Pinned<char>* buf; Device<char>* d_win; Device<char>* d_members;
         Channel<int> free_bufs, full_bufs; int slot_id[2] = {0, 1}; size_t bytes[2] = {0, 0};
         hipEvent_t copied[2] = {nullptr, nullptr};        // the slot's window has reached its pinned buffer
         bool on_device = false;
         std::thread writer; std::exception_ptr error;
-        explicit Out(SurvivorBuffers::PerFile& p) : src_off(p.src_off), dst_off(p.dst_off), len(p.len), total(p.total), label_at(p.label_at.p), buf(p.buf), d_win(p.d_win), d_members(p.d_members), on_device(p.on_device) {}
+        explicit Out(SurvivorBuffers::PerFile& p) : src_off(p.src_off), dst_off(p.dst_off), len(p.len), total(p.total), label_at(p.label_at.p), cut(p.cut.p), buf(p.buf), d_win(p.d_win), d_members(p.d_members), on_device(p.on_device) {}
     };
     Out o[2] = {Out(planned->f[0]), Out(planned->f[1])};
     static int kStop = -1;
@@ -221,7 +235,10 @@ void write_survivors(fqd_engine* e, hipStream_t stream, int S, FileOnDevice* con
                     // dst_off is absolute in the output: the window's buffer starts `lo` bytes in
                     const uint8_t* text = reinterpret_cast<const uint8_t*>(file[s]->text.p);
                     uint8_t* win = reinterpret_cast<uint8_t*>(d_win.p) - lo;
-                    if (planned->cluster_size)
+                    if (planned->cluster_size && planned->size_in)
+                        engine_ok(e, fqd_copy_relabelled(e, text, o[s].src_off.p + at[s], o[s].len.p + at[s], o[s].label_at + at[s], o[s].cut + at[s],
+                                                         planned->cluster_size + at[s], take, win, o[s].dst_off.p + at[s]));
+                    else if (planned->cluster_size)
                         engine_ok(e, fqd_copy_labelled(e, text, o[s].src_off.p + at[s], o[s].len.p + at[s], o[s].label_at + at[s], planned->cluster_size + at[s], take,
                                                        win, o[s].dst_off.p + at[s]));
                     else

@@ -740,6 +740,73 @@ int  fqd_size_order_ex(fqd_engine* e, const uint32_t* perm, const uint8_t* head,
                        uint32_t* order, uint64_t* n_written, fqd_size_order_info* info);
 int  fqd_take_u32(fqd_engine* e, const uint32_t* values, const uint32_t* idx, uint64_t n, uint32_t* out);
 
+/* ---- FQD_FAST_SIZEIN=1: a `;size=N` that the input's ID lines already carry is the record's weight, a cluster's size is the
+ * sum of its members' weights, and the new label takes the old annotation's place (added within ABI version 5: purely
+ * additive; no existing entry launches anything new).  Rules and proofs: csrc/fqd_sizein_core.hpp.  W is the first word of
+ * an ID line as above.  A candidate is a position p >= 1 at which the six bytes `;size=` stand inside W, compared exactly; it
+ * is well-formed when 1 .. 10 decimal digits follow (leading zeros allowed), then W's end or a ';', and the value is in
+ * 1 .. 2^31-1.  No candidate: weight 1.  Exactly one, well-formed: weight = its value, and the annotation is the bytes
+ * `;size=<digits>`.  Anything else refuses the record, for the first of these that holds of the FIRST candidate from the
+ * left: FQD_SIZEIN_NO_DIGITS; FQD_SIZEIN_TOO_LARGE for eleven digits or more (no more are looked at); FQD_SIZEIN_BAD_END for
+ * another byte behind the digits; FQD_SIZEIN_ZERO; FQD_SIZEIN_TOO_LARGE for a value above 2^31-1; FQD_SIZEIN_TWICE where a
+ * second candidate follows.
+ *
+ * fqd_size_annotations: device memory only (info: host, not NULL), all arrays per record r < n of ONE file.  Line r is the
+ * id_len[r] bytes at text + start[r].  weight, label_at and cut are n uint32 each and each may be NULL: weight[r] as above;
+ * label_at[r] = the annotation's start, or the first word's end where there is none (fqd_size_labels' value); cut[r] = the
+ * annotation's length, 0 for none.  expect (may be NULL: file 1) = file 1's weights for a call over file 2: an annotation in
+ * line r must then say expect[r], FQD_SIZEIN_MATES_DIFFER otherwise; a line without one is fine.  *info: bad_record = the
+ * LOWEST refused record (FQD_UMI_NO_RECORD: none) and bad_reason why; annotated = the records with an annotation and
+ * total_weight = the sum of the weights (both of the records that are not refused).  A refused record makes the call return
+ * FQD_OK with info set; the arrays' contents are then unspecified.  n <= 2^32-2.  Sixteen lanes a record, one launch; returns
+ * after the stream has drained (once).
+ *
+ * fqd_cluster_weights: fqd_cluster_sizes with a weight per record (device memory only; levels: host, may be NULL; info: host,
+ * not NULL).  size[perm[s]] (n uint32) = the sum of weight[perm[k]] over the run that starts at head place s, 0 at every
+ * other place: every entry is written exactly once.  levels as in fqd_cluster_sizes, from the weighted sizes.  Sums are 64-bit
+ * throughout.  A run whose sum exceeds 2^31-1 is reported: info->over_record = the lowest record at the head place of such a
+ * run (FQD_UMI_NO_RECORD: none), over_sum = that run's exact sum; the call returns FQD_OK, levels is all 0 and nothing is
+ * promised about size.  n < 2^31.  head[0] == 0 with n > 0 (nothing is written to size), or a weight of 0 (counted on the
+ * device, reported once), is FQD_ERR_ARG.  One segmented sum in three launches (tile values, one block over them, the
+ * places), no block waiting for another; 16 bytes of scratch per 2048 records.  Returns after the stream has drained.
+ *
+ * fqd_size_relabel: device memory only, elementwise: out_size[r] = rec_size[r] - cut[r] + 6 + the decimal digits of size[r]
+ * where keep[r], rec_size[r] elsewhere — what fqd_output_plan takes for `sizes`.  A kept record whose size is 0 is FQD_ERR_ARG
+ * (counted on the device, reported once).  Returns after the stream has drained.
+ *
+ * fqd_copy_relabelled: fqd_copy_labelled that leaves the cut[i] bytes behind label_at[i] out: dst + dst_off[i] receives the
+ * first label_at[i] bytes at src + src_off[i], then `;size=<size[i]>`, then the source from label_at[i] + cut[i] on, len[i]
+ * bytes in all (the GROWN length that fqd_output_plan produced from fqd_size_relabel's out_size, 0 for a span that is not
+ * written).  cut[i] = 0 is fqd_copy_labelled.  Only launches. */
+enum fqd_sizein_reason {
+    FQD_SIZEIN_OK = 0,
+    FQD_SIZEIN_NO_DIGITS = 1,    /* `;size=` and no digit behind it */
+    FQD_SIZEIN_BAD_END = 2,      /* the digits are followed by something other than ';' or the word's end */
+    FQD_SIZEIN_ZERO = 3,         /* the value is 0 */
+    FQD_SIZEIN_TOO_LARGE = 4,    /* more than 10 digits, or a value above 2^31-1 */
+    FQD_SIZEIN_TWICE = 5,        /* a well-formed annotation and another `;size=` behind it */
+    FQD_SIZEIN_MATES_DIFFER = 6  /* file 2's annotation does not say file 1's weight */
+};
+typedef struct fqd_sizein_info {
+    uint64_t bad_record;
+    uint32_t bad_reason;        /* enum fqd_sizein_reason */
+    uint32_t reserved;
+    uint64_t annotated;
+    uint64_t total_weight;
+} fqd_sizein_info;
+typedef struct fqd_weights_info {
+    uint64_t over_record;
+    uint64_t over_sum;
+} fqd_weights_info;
+int  fqd_size_annotations(fqd_engine* e, const uint8_t* text, const uint64_t* start, const uint32_t* id_len, uint64_t n, const uint32_t* expect,
+                          uint32_t* weight, uint32_t* label_at, uint32_t* cut, fqd_sizein_info* info);
+int  fqd_cluster_weights(fqd_engine* e, const uint32_t* perm, const uint8_t* head, const uint32_t* weight, uint64_t n, uint32_t* size,
+                         fqd_size_levels* levels, fqd_weights_info* info);
+int  fqd_size_relabel(fqd_engine* e, const uint32_t* rec_size, const uint8_t* keep, const uint32_t* size, const uint32_t* cut, uint64_t n,
+                      uint32_t* out_size);
+int  fqd_copy_relabelled(fqd_engine* e, const uint8_t* src, const uint64_t* src_off, const uint32_t* len, const uint32_t* label_at,
+                         const uint32_t* cut, const uint32_t* size, uint64_t n, uint8_t* dst, const uint64_t* dst_off);
+
 /* ---- FQD_FAST_UMI_MISMATCH=1|2: exact UMI clusters of one sequence that differ in a base or two are one molecule (added
  * within ABI version 5: purely additive; no existing entry launches anything new).  Rule and proofs:
  * csrc/fqd_umi_merge_core.hpp.  A sequence group is the records with identical sequences (UMI left out); a node is one
