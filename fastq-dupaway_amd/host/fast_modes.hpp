@@ -1,0 +1,59 @@
+// fast_modes.hpp — the eleven FQD_FAST_* switches of the `--fast` mode as one value: read from the environment in one place
+// (FastModes::from_env), checked against the command line before any GPU call (check), and asked by the run
+// (run_resident.cpp) through the predicates below.  Also the words of every refusal the switches can cause.
+// Plain C++: no HIP, nothing of run_common.hpp.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+
+#include "records.hpp"
+
+namespace fqdhost {
+namespace detail {
+
+// Why a run with a switch set ends: the modes need every record's flag to stay open until the last record is in, or turn
+// the reads where they lie in HBM, which only the GPU-resident ordered run offers (the streaming run's flags are final
+// batch by batch).  Thrown before any output exists.
+struct FastModeRefusal : std::runtime_error { using std::runtime_error::runtime_error; };
+
+struct FastModes {
+    bool keep_best = false;      // FQD_FAST_KEEP=first|best: a cluster's first member in the input is written, as in the reference, or the one with the best quality line (csrc/fqd_seq_pick_core.hpp)
+    bool clusters = false;       // FQD_FAST_CLUSTERS=1: `<output>.clusters` beside every output
+    bool both_strands = false;   // FQD_FAST_STRAND=given|both: both: a read and its reverse complement — a pair and the pair with its mates exchanged — are one key (csrc/fqd_strand_core.hpp)
+    int umi = 0;                 // FQD_FAST_UMI=off|colon|underscore: 0, ':' or '_'; the UMI bases behind the last such byte of the first word of file 1's ID line are keyed in front of the sequence(s) (csrc/fqd_umi_core.hpp)
+    int umi_mismatch = 0;        // FQD_FAST_UMI_MISMATCH=0|1|2: exact UMI clusters of one sequence (pair) whose UMIs differ in at most that many bases merge by UMI-tools' directional rule (csrc/fqd_umi_merge_core.hpp)
+    bool size_out = false;       // FQD_FAST_SIZEOUT=1: every record written carries `;size=N`, its cluster's member count, behind the first word of its ID line (csrc/fqd_size_core.hpp)
+    bool levels = false;         // FQD_FAST_LEVELS=1: `<output 1>.duplevels`, the clusters and records per duplication level
+    bool sort_by_size = false;   // FQD_FAST_SORT=input|size: size: by decreasing cluster size, clusters of one size in the order of their first member (csrc/fqd_size_order_core.hpp)
+    uint32_t min_size = 1, max_size = 0;   // FQD_FAST_MINSIZE=N / FQD_FAST_MAXSIZE=N in 1 .. 2^31-1: a cluster of fewer / more members is not written; unset: 1 and 0, the two that take nothing out
+    bool size_in = false;        // FQD_FAST_SIZEIN=1: a `;size=N` an ID line already carries is the record's weight, a cluster's size the sum of its members' weights (csrc/fqd_sizein_core.hpp)
+
+    // Reads the eleven variables.  Throws std::runtime_error on a value that is none of the above, and FastModeRefusal for
+    // a MAXSIZE below MINSIZE, in the order KEEP, SORT, MINSIZE, MAXSIZE, MAXSIZE below MINSIZE, STRAND, UMI, UMI_MISMATCH.
+    static FastModes from_env();
+    // What the values and the command line decide, before any GPU call; throws FastModeRefusal.  In this order: SIZEIN with
+    // nothing that reads sizes, UMI_MISMATCH without UMI, `--unordered`, several devices, KEEP=best with FASTA.
+    void check(bool unordered, size_t n_devices, Format format) const;
+
+    bool size_filter() const { return min_size > 1 || max_size != 0; }                 // a bound that can take a cluster out
+    bool sized() const { return size_out || levels || sort_by_size || size_filter(); } // something reads the cluster sizes
+    bool linked() const { return keep_best || clusters || umi_mismatch || sized(); }   // the duplicates must be linked to their clusters
+    bool any() const { return linked() || both_strands || umi; }                       // only the GPU-resident ordered run will do
+
+    // The switches that are set, as the messages name them: "FQD_FAST_KEEP=best and FQD_FAST_UMI=colon"; "" for none.
+    std::string names() const;
+    std::string umi_name() const { return umi == ':' ? "FQD_FAST_UMI=colon" : umi == '_' ? "FQD_FAST_UMI=underscore" : ""; }
+    std::string mismatch_name() const { return umi_mismatch ? "FQD_FAST_UMI_MISMATCH=" + std::to_string(umi_mismatch) : std::string(); }
+    // What did not fit when the GPU-resident run meets the end of HBM, for the refusal.
+    std::string out_of_memory_note() const;
+};
+
+// Why fqd_umi_find (enum fqd_umi_reason) and fqd_size_annotations (enum fqd_sizein_reason) refuse a record, in the words of
+// csrc/fqd_umi_core.hpp and csrc/fqd_sizein_core.hpp.
+std::string umi_reason(uint32_t reason, int sep);
+std::string sizein_reason(uint32_t reason);
+
+} // namespace detail
+} // namespace fqdhost

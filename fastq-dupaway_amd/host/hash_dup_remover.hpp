@@ -12,6 +12,7 @@
 #include <sys/types.h>
 #include <vector>
 
+#include "fast_modes.hpp"
 #include "records.hpp"
 
 namespace fqdhost {
@@ -60,7 +61,7 @@ public:
                   const std::string& outfile1, const std::string& outfile2, bool unordered);
     const Summary& summary() const { return summary_; }
 private:
-    void read_fast_modes(bool unordered);             // FQD_FAST_KEEP / _CLUSTERS / _STRAND / _UMI / _UMI_MISMATCH / _SIZEOUT / _LEVELS / _SORT / _MINSIZE / _MAXSIZE / _SIZEIN: read and checked before any GPU call
+    void read_fast_modes(bool unordered);             // the FQD_FAST_* switches: read and checked before any GPU call
     void run_ordered(int n_files, const std::string* in, const std::string* out);
     bool run_ordered_resident(int n_files, const std::string* in, const std::string* out);   // false: not taken, nothing touched
     void run_ordered_multi(int n_files, const std::string* in, const std::string* out);
@@ -75,33 +76,11 @@ private:
     bool                verbose_;
     Tuning              tuning_;
     Summary             summary_;
-    bool                keep_best_ = false;      // FQD_FAST_KEEP=best
-    bool                write_clusters_ = false; // FQD_FAST_CLUSTERS=1
-    bool                both_strands_ = false;   // FQD_FAST_STRAND=both
-    int                 umi_sep_ = 0;            // FQD_FAST_UMI=colon|underscore: ':' or '_', 0 for off
-    int                 umi_mismatch_ = 0;       // FQD_FAST_UMI_MISMATCH=1|2: UMI clusters of one sequence this many bases apart merge; 0 for off
-    bool                size_out_ = false;       // FQD_FAST_SIZEOUT=1
-    bool                write_levels_ = false;   // FQD_FAST_LEVELS=1
-    bool                sort_by_size_ = false;   // FQD_FAST_SORT=size
-    uint32_t            min_size_ = 1;           // FQD_FAST_MINSIZE=N
-    uint32_t            max_size_ = 0;           // FQD_FAST_MAXSIZE=N; 0 for none
-    bool                size_filter_ = false;    // either of the two is set to something that can take a cluster out
-    bool                size_in_ = false;        // FQD_FAST_SIZEIN=1
+    detail::FastModes   fast_;                   // the FQD_FAST_* switches (fast_modes.hpp), set by read_fast_modes
 };
 
 // FQD_GZ_DEVICE_RATIO=fast|high -> FQD_BGZF_FAST / FQD_BGZF_SEARCH for the device deflate of `.gz` outputs; throws on any
 // other value (survivor_writer.cpp; main() asks before a run starts, the writer when it deflates).
 namespace detail { uint32_t device_deflate_effort(); uint64_t seq_range_target_bytes(); }
-
-// FQD_FAST_KEEP=first|best and FQD_FAST_CLUSTERS=1 of the `--fast` mode (run_resident.cpp, the one place each is read):
-// throw on any other value of FQD_FAST_KEEP.  main() asks before a run starts, HashDupRemover before any GPU call.
-// FQD_FAST_STRAND=given|both (same place): throws on any other value; asked by HashDupRemover::read_fast_modes only, which
-// runs before any GPU call.  FQD_FAST_UMI=off|colon|underscore likewise: 0, ':' or '_', and
-// FQD_FAST_UMI_MISMATCH=0|1|2: its value.  FQD_FAST_SIZEOUT=1 and
-// FQD_FAST_LEVELS=1 are parsed as FQD_FAST_CLUSTERS is.  FQD_FAST_SORT=input|size: throws on any other value;
-// FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE (fast_size_bound): a decimal integer in 1 .. 2^31-1 or the default for unset, throws on
-// anything else.  FQD_FAST_SIZEIN=1 is parsed as FQD_FAST_CLUSTERS is.
-namespace detail { bool fast_keep_best(); bool fast_clusters(); bool fast_both_strands(); int fast_umi(); int fast_umi_mismatch(); bool fast_sizeout(); bool fast_levels();
-                   bool fast_sort_by_size(); uint32_t fast_size_bound(const char* name, uint32_t unset); bool fast_sizein(); }
 
 } // namespace fqdhost

@@ -259,10 +259,6 @@ int main(int argc, char** argv)                                // main.cpp:181-2
             else                    remover.filterSE(opts.input_1, opts.output_1);
             return 0;
         }
-        (void)fqdhost::detail::fast_keep_best();               // a misspelt FQD_FAST_KEEP ends the run before any GPU call
-        (void)fqdhost::detail::fast_sort_by_size();            // (FQD_FAST_SORT, FQD_FAST_MINSIZE and FQD_FAST_MAXSIZE likewise)
-        (void)fqdhost::detail::fast_size_bound("FQD_FAST_MINSIZE", 1);
-        (void)fqdhost::detail::fast_size_bound("FQD_FAST_MAXSIZE", 0);
         fqdhost::HashDupRemover remover(fmt, opts.memLimit, &tempdir, opts.verbose, tune);   // main.cpp:218-242
         if (opts.mode & PAIRED) remover.filterPE(opts.input_1, opts.input_2, opts.output_1, opts.output_2, opts.unordered);
         else                    remover.filterSE(opts.input_1, opts.output_1);

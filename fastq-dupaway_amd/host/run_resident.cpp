@@ -1,610 +1,440 @@
 // run_resident.cpp — the two runs whose text is resident in HBM, ordered (run_ordered_resident) and `--unordered`
-// (run_unordered_resident); how the files get there is resident_input.cpp's.
+// (run_unordered_resident); how the files get there is resident_input.cpp's, what the FQD_FAST_* switches are fast_modes.hpp's.
 #include "run_common.hpp"
+#include <future>
 
 namespace fqdhost {
 using namespace detail;
 
-namespace detail {
-
-// FQD_FAST_KEEP=first|best: which member of a cluster of identical reads (pairs) `--fast` writes.  first (and unset): the
-// first in the input, as the reference does; best: the one with the best quality line, at its own place in the input
-// (csrc/fqd_owner_core.hpp, csrc/fqd_seq_pick_core.hpp).  Read here and nowhere else.
-bool fast_keep_best()
-{
-    const char* v = std::getenv("FQD_FAST_KEEP");
-    if (!v || std::strcmp(v, "first") == 0) return false;
-    if (std::strcmp(v, "best") == 0) return true;
-    throw std::runtime_error(std::string("FQD_FAST_KEEP must be 'first' or 'best', not '") + v + "'");
-}
-
-// FQD_FAST_CLUSTERS=1: `--fast` writes `<output>.clusters` beside every output.  Read here and nowhere else.
-bool fast_clusters()
-{
-    const char* v = std::getenv("FQD_FAST_CLUSTERS");
-    return v && std::atoi(v) != 0;
-}
-
-// FQD_FAST_STRAND=given|both: whether `--fast` tells the two strands of a fragment apart.  given (and unset): a read is
-// what its bytes are, as in the reference; both: a read and its reverse complement — a pair and the pair with its mates
-// exchanged — are one key (csrc/fqd_strand_core.hpp).  Read here and nowhere else.
-bool fast_both_strands()
-{
-    const char* v = std::getenv("FQD_FAST_STRAND");
-    if (!v || std::strcmp(v, "given") == 0) return false;
-    if (std::strcmp(v, "both") == 0) return true;
-    throw std::runtime_error(std::string("FQD_FAST_STRAND must be 'given' or 'both', not '") + v + "'");
-}
-
-// FQD_FAST_UMI=off|colon|underscore: whether `--fast` keys a read (pair) by the unique molecular identifier in file 1's ID
-// lines as well.  off (and unset): by its sequence(s) alone; colon / underscore: by the UMI bases behind the last ':' / '_'
-// of the ID line's first word, then the sequence(s) (csrc/fqd_umi_core.hpp).  Returns 0, ':' or '_'.  Read here and
-// nowhere else.
-int fast_umi()
-{
-    const char* v = std::getenv("FQD_FAST_UMI");
-    if (!v || std::strcmp(v, "off") == 0) return 0;
-    if (std::strcmp(v, "colon") == 0) return ':';
-    if (std::strcmp(v, "underscore") == 0) return '_';
-    throw std::runtime_error(std::string("FQD_FAST_UMI must be 'off', 'colon' or 'underscore', not '") + v + "'");
-}
-
-// FQD_FAST_UMI_MISMATCH=0|1|2: with FQD_FAST_UMI, whether the exact UMI clusters of one sequence (pair of sequences) whose UMIs
-// differ in at most that many bases are merged by UMI-tools' directional rule (csrc/fqd_umi_merge_core.hpp).  0 (and unset):
-// a UMI is told apart by every base.  Read here and nowhere else.
-int fast_umi_mismatch()
-{
-    const char* v = std::getenv("FQD_FAST_UMI_MISMATCH");
-    if (!v || std::strcmp(v, "0") == 0) return 0;
-    if (std::strcmp(v, "1") == 0) return 1;
-    if (std::strcmp(v, "2") == 0) return 2;
-    throw std::runtime_error(std::string("FQD_FAST_UMI_MISMATCH must be 0, 1 or 2, not '") + v + "'");
-}
-
-// FQD_FAST_SIZEOUT=1: every record `--fast` writes carries `;size=N`, its cluster's member count, behind the first word of
-// its ID line (csrc/fqd_size_core.hpp).  Read here and nowhere else.
-bool fast_sizeout()
-{
-    const char* v = std::getenv("FQD_FAST_SIZEOUT");
-    return v && std::atoi(v) != 0;
-}
-
-// FQD_FAST_LEVELS=1: `--fast` writes `<output 1>.duplevels`, the clusters and records per duplication level.  Read here and
-// nowhere else.
-bool fast_levels()
-{
-    const char* v = std::getenv("FQD_FAST_LEVELS");
-    return v && std::atoi(v) != 0;
-}
-
-// FQD_FAST_SORT=input|size: the order of the records `--fast` writes.  input (and unset): the input's; size: by decreasing
-// cluster size, clusters of one size in the order of their first member (csrc/fqd_size_order_core.hpp).  Read here and
-// nowhere else.
-bool fast_sort_by_size()
-{
-    const char* v = std::getenv("FQD_FAST_SORT");
-    if (!v || std::strcmp(v, "input") == 0) return false;
-    if (std::strcmp(v, "size") == 0) return true;
-    throw std::runtime_error(std::string("FQD_FAST_SORT must be 'input' or 'size', not '") + v + "'");
-}
-
-// FQD_FAST_MINSIZE=N / FQD_FAST_MAXSIZE=N: a cluster of fewer / more members than N is not written.  `unset` where the
-// variable is not set (1 and 0, "no bound").  Read here and nowhere else.
-uint32_t fast_size_bound(const char* name, uint32_t unset)
-{
-    const char* v = std::getenv(name);
-    if (!v) return unset;
-    uint64_t x = 0;
-    size_t digits = 0;
-    for (const char* p = v; *p; ++p, ++digits) {
-        if (*p < '0' || *p > '9' || digits >= 10) { digits = 0; break; }
-        x = x * 10 + uint64_t(*p - '0');
-    }
-    if (!digits || x < 1 || x > 0x7FFFFFFFull)
-        throw std::runtime_error(std::string(name) + " must be a decimal integer in 1 .. 2147483647, not '" + v + "'");
-    return uint32_t(x);
-}
-
-// FQD_FAST_SIZEIN=1: a `;size=N` that the first word of an ID line already carries is the record's weight, a cluster's size
-// is the sum of its members' weights, and with FQD_FAST_SIZEOUT the new label takes the old annotation's place
-// (csrc/fqd_sizein_core.hpp).  Read here and nowhere else.
-bool fast_sizein()
-{
-    const char* v = std::getenv("FQD_FAST_SIZEIN");
-    return v && std::atoi(v) != 0;
-}
-
-} // namespace detail
-
 namespace {
 
-// Why a run with FQD_FAST_KEEP=best or FQD_FAST_CLUSTERS=1 ends: these modes need every record's flag to stay open until
-// the last record is in, which only the GPU-resident run offers (the streaming run's flags are final batch by batch).
-// FQD_FAST_STRAND=both ends the same way: it turns the reads where they lie in HBM, in front of the engine.
-struct FastModeRefusal : std::runtime_error { using std::runtime_error::runtime_error; };
-
-const char* umi_switch(int umi) { return umi == ':' ? "FQD_FAST_UMI=colon" : umi == '_' ? "FQD_FAST_UMI=underscore" : nullptr; }
-
-const char* mismatch_switch(int mismatch) { return mismatch == 1 ? "FQD_FAST_UMI_MISMATCH=1" : mismatch == 2 ? "FQD_FAST_UMI_MISMATCH=2" : nullptr; }
-
-// (min_size 1 and max_size 0 are the two bounds that take nothing out: not named)
-std::string fast_switches(bool best, bool clusters, bool both, int umi, int mismatch, bool sizeout, bool levels, bool by_size, uint32_t min_size, uint32_t max_size,
-                          bool sizein)
+// The engine — its key store and table sized from the files' sizes (guess_capacity) — made on a helper thread under the
+// reads of the inputs: its first use comes after them.  also_make(reads) runs on that thread behind it.  get() waits for the
+// thread and rethrows what it threw, and so does the destructor of the last copy (the waiting, not the throwing).
+using EngineUnderTheRead = std::shared_future<std::shared_ptr<EngineHandle>>;
+template <class AlsoMake>
+EngineUnderTheRead engine_under_the_read(int S, const std::string* in, int device, hipStream_t stream, const char* stage, AlsoMake also_make)
 {
-    std::string s;
-    for (const char* name : {best ? "FQD_FAST_KEEP=best" : nullptr, clusters ? "FQD_FAST_CLUSTERS=1" : nullptr, both ? "FQD_FAST_STRAND=both" : nullptr, umi_switch(umi),
-                             mismatch_switch(mismatch), sizeout ? "FQD_FAST_SIZEOUT=1" : nullptr, levels ? "FQD_FAST_LEVELS=1" : nullptr,
-                             by_size ? "FQD_FAST_SORT=size" : nullptr, sizein ? "FQD_FAST_SIZEIN=1" : nullptr})
-        if (name) s += (s.empty() ? "" : " and ") + std::string(name);
-    if (min_size > 1) s += (s.empty() ? "" : " and ") + ("FQD_FAST_MINSIZE=" + std::to_string(min_size));
-    if (max_size) s += (s.empty() ? "" : " and ") + ("FQD_FAST_MAXSIZE=" + std::to_string(max_size));
-    return s;
+    uint64_t cap_reads = 0, cap_bases = 0;
+    guess_capacity(S, in, cap_reads, cap_bases);
+    return std::async(std::launch::async, [=] {
+        HIP_OK(hipSetDevice(device));
+        StageClock::Scope t(stage);
+        auto made = std::make_shared<EngineHandle>(S, device, stream, cap_reads, cap_bases);
+        also_make(cap_reads);
+        return made;
+    }).share();
 }
 
-// Why fqd_umi_find refuses a record (enum fqd_umi_reason), in the words of csrc/fqd_umi_core.hpp.
-std::string umi_reason(uint32_t reason, int sep)
+// ---- the ordered run, stage by stage --------------------------------------------------------------------------------
+
+// With a switch set (FastModes::any) there is no hand-over: whatever would have sent the input to the streaming run ends
+// the run with a message that names the switches and the reason, still before any output exists.
+bool give_up(const FastModes& fast, const std::string& why)
 {
-    const std::string c(1, char(sep));
-    switch (reason) {
-    case FQD_UMI_NO_SEPARATOR: return "the first word of its ID line holds no '" + c + "'";
-    case FQD_UMI_EMPTY: return "its UMI is empty: the last '" + c + "' is the last byte of the ID line's first word";
-    case FQD_UMI_TOO_LONG: return "its UMI is longer than 64 bytes";
-    case FQD_UMI_BAD_BYTE: return "its UMI holds a byte outside ACGTN+-_";
-    case FQD_UMI_NO_BASE: return "its UMI has no base";
-    case FQD_UMI_SHAPE_DIFFERS: return "the shape of its UMI (its length and the places of '+', '-', '_') differs from record 0's: UMIs of varying length are not supported";
-    }
-    return "its UMI was refused";
+    if (fast.any()) throw FastModeRefusal(fast.names() + ": the GPU-resident run cannot take this input (" + why + "), and the streaming run cannot serve these modes");
+    return false;
 }
 
-// Why fqd_size_annotations refuses a record (enum fqd_sizein_reason), in the words of csrc/fqd_sizein_core.hpp.
-std::string sizein_reason(uint32_t reason)
+// Stage 1, decided before any GPU call: whether the run is taken.  Without a switch, only when a codec is involved — a
+// BGZF input, or a `.gz` output the GPU can deflate (plain files in and out are better off in the streaming run, where
+// reading, the GPU and writing overlap).  With a switch, for plain files as well; nothing: all of them are empty.
+bool resident_run_taken(const FastModes& fast, int S, const std::string* in, const std::string* out, bool& nothing)
 {
-    switch (reason) {
-    case FQD_SIZEIN_NO_DIGITS: return "the `;size=` in the first word of its ID line is followed by no digit";
-    case FQD_SIZEIN_BAD_END: return "the digits of its `;size=` are followed by something other than ';' or the end of the ID line's first word";
-    case FQD_SIZEIN_ZERO: return "its annotation says `;size=0`: a record stands for at least one read";
-    case FQD_SIZEIN_TOO_LARGE: return "its `;size=` has more than 10 digits or says more than 2147483647";
-    case FQD_SIZEIN_TWICE: return "the first word of its ID line holds `;size=` twice";
-    case FQD_SIZEIN_MATES_DIFFER: return "its `;size=` does not say what the record's annotation in file 1 says (1 where file 1 has none)";
-    }
-    return "its `;size=` annotation was refused";
-}
-
-} // namespace
-
-// Everything about the eleven switches that their values and the command line decide, before any GPU call.
-void HashDupRemover::read_fast_modes(bool unordered)
-{
-    sort_by_size_ = fast_sort_by_size();
-    min_size_ = fast_size_bound("FQD_FAST_MINSIZE", 1);
-    max_size_ = fast_size_bound("FQD_FAST_MAXSIZE", 0);
-    if (max_size_ && max_size_ < min_size_)
-        throw FastModeRefusal("FQD_FAST_MAXSIZE=" + std::to_string(max_size_) + " is below FQD_FAST_MINSIZE=" + std::to_string(min_size_) + ": no cluster could be written");
-    size_filter_ = min_size_ > 1 || max_size_ != 0;
-    keep_best_ = fast_keep_best();
-    write_clusters_ = fast_clusters();
-    both_strands_ = fast_both_strands();
-    umi_sep_ = fast_umi();
-    umi_mismatch_ = fast_umi_mismatch();
-    size_out_ = fast_sizeout();
-    write_levels_ = fast_levels();
-    size_in_ = fast_sizein();
-    if (size_in_ && !size_out_ && !write_levels_ && !sort_by_size_ && !size_filter_)
-        throw FastModeRefusal("FQD_FAST_SIZEIN=1 changes what a cluster's size is and nothing else: set one of FQD_FAST_SIZEOUT=1, FQD_FAST_LEVELS=1, FQD_FAST_SORT=size, "
-                              "FQD_FAST_MINSIZE (above 1) or FQD_FAST_MAXSIZE as well, which read the sizes");
-    if (!keep_best_ && !write_clusters_ && !both_strands_ && !umi_sep_ && !umi_mismatch_ && !size_out_ && !write_levels_ && !sort_by_size_ && !size_filter_) return;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_, size_in_);
-    if (umi_mismatch_ && !umi_sep_)
-        throw FastModeRefusal(std::string(mismatch_switch(umi_mismatch_)) + " merges the UMIs that FQD_FAST_UMI finds: set FQD_FAST_UMI=colon or FQD_FAST_UMI=underscore as well");
-    if (unordered)
-        throw FastModeRefusal(which + " with --unordered: these modes run on ordered inputs only");
-    if (tuning_.devices.size() > 1)
-        throw FastModeRefusal(which + " runs on one GPU: FQD_DEVICES may name one device only");
-    if (keep_best_ && format_ == Format::Fasta)
-        throw FastModeRefusal("FQD_FAST_KEEP=best needs the quality lines of FASTQ records: --format fasta has none");
-    if (tuning_.devices.size() == 1) { tuning_.device = tuning_.devices[0]; tuning_.devices.clear(); }
-}
-
-// An ordered run (single-end, or paired files read side by side) with a codec at either end — BGZF inputs, or `.gz`
-// outputs of plain regular inputs: the files go to HBM as they lie on disk, are inflated (if compressed) and cut into
-// records there, every read (pair) is deduplicated where it lies, and the
-// survivors leave in input order window by window (deflated on the device for `.gz` outputs).  Taken only when
-// everything is plain sailing — regular BGZF files of whole records, as many in file 2 as in file 1, no unknown
-// base, everything fits in HBM; otherwise false is returned BEFORE any output is touched and the streaming run
-// (run_ordered), which reproduces the reference's behaviour for every irregular input, does the job.
-//
-// With FQD_FAST_KEEP=best or FQD_FAST_CLUSTERS=1 (`modes`) the run is taken for plain files as well, links every duplicate
-// to an earlier record of its key (fqd_submit_linked), resolves the links to the first record (fqd_owners), groups the
-// records by it (fqd_group_owners) and, for `best`, moves the keep flag of every cluster to its best member
-// (pick_best_members, fqd_heads_to_keep).  There is no hand-over then: whatever would have sent the input to the
-// streaming run ends the run with a message that names the switch and the reason, still before any output exists.
-//
-// With FQD_FAST_STRAND=both (also `modes`) one fqd_canonical_reads over all n records stands between the record scan and
-// the submit loop, which then submits the canonical descriptors; whatever comes after the loop sees flags and links as
-// before, and the writers take the records' ORIGINAL text.
-//
-// With FQD_FAST_UMI=colon|underscore (also `modes`) one more rewrite stands at that place, behind the strand block:
-// fqd_umi_find over file 1's ID lines — a record it refuses ends the run — then fqd_umi_reads, which packs `UMI bases ‖
-// sequence` of mate 1 (the canonical mate 1 with FQD_FAST_STRAND=both) for the submit loop's segment 0.  Mate 2 goes to the
-// submit as it is.
-//
-// With FQD_FAST_SIZEOUT=1 or FQD_FAST_LEVELS=1 (both `linked`) one fqd_cluster_sizes follows the grouping and the pick: the
-// member count of every cluster at the record that is written, 4 bytes a record, and the level table.  The table becomes
-// `<output 1>.duplevels`; the sizes stay for the writer when FQD_FAST_SIZEOUT is set, which then plans the outputs from the
-// records' sizes with their labels and copies the windows with fqd_copy_labelled (survivor_writer.cpp), and are released
-// at once otherwise.
-//
-// With FQD_FAST_SORT=size, FQD_FAST_MINSIZE or FQD_FAST_MAXSIZE (all `linked`) the sizes are computed as well, while perm and
-// head still exist: fqd_size_filter clears the flags of the clusters outside the bounds — behind the cluster files and the
-// level table, which hold all clusters — and fqd_size_order writes the records that stay in order of decreasing cluster
-// size.  The writer then takes that order as its index for both files, a set flag for each of its entries, and as many
-// pairs as it has entries; with FQD_FAST_SIZEOUT the labels are still found per record and brought into the order by
-// fqd_take_u32 (survivor_writer.cpp).  A filter without the order needs no index: the cleared flags go through the plan.
-//
-// With FQD_FAST_SIZEIN=1 (beside at least one of the five size switches) fqd_size_annotations reads every record's weight off
-// its ID line where fqd_umi_find runs, before the first submit — file 1 gives the weights, file 2 is held against them, and a
-// record it refuses ends the run —, fqd_cluster_weights stands wherever fqd_cluster_sizes would, and the weights are released
-// after the last such call.  Everything that reads sizes reads the weighted ones; the writer parses the annotations' places
-// once more per file (survivor_writer.cpp), so nothing but the weights is held in between.
-//
-// With FQD_FAST_UMI_MISMATCH=1|2 (also `linked`; FQD_FAST_UMI is set) the engine is used TWICE: the submit loop as above
-// keyed `UMI bases ‖ sequence` gives the exact owners and, through fqd_group_owners and fqd_cluster_sizes, every exact
-// cluster's count; after fqd_engine_reset the same batches go in again keyed by the sequences alone (the given or the
-// canonical descriptors), into the same flags and links, which gives every record's sequence group.  fqd_umi_merge makes
-// the merged owners of the three, fqd_owners_to_keep the flags, and the grouping, the pick, the cluster files, the sizes
-// and the writers follow as they do for any other owners.  The canonical and keyed buffers stay until the second pass is
-// through, the UMI offsets until the merge is.
-bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
-{
-    const bool linked = keep_best_ || write_clusters_ || size_out_ || write_levels_ || umi_mismatch_ || sort_by_size_ || size_filter_, modes = linked || both_strands_ || umi_sep_;
-    const std::string which = fast_switches(keep_best_, write_clusters_, both_strands_, umi_sep_, umi_mismatch_, size_out_, write_levels_, sort_by_size_, min_size_, max_size_, size_in_);
-    // FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE: what `-v` says behind its first line
-    auto print_not_written = [&](uint64_t clusters, uint64_t records) {
-        if (verbose_ && size_filter_)
-            std::cout << clusters << " clusters holding " << records << (S == 1 ? " reads" : " read pairs") << " were not written (FQD_FAST_MINSIZE=" << min_size_
-                      << ", FQD_FAST_MAXSIZE=" << (max_size_ ? std::to_string(max_size_) : std::string("none")) << ").\n";
-    };
-    auto give_up = [&](const std::string& why) -> bool {
-        if (modes) throw FastModeRefusal(which + ": the GPU-resident run cannot take this input (" + why +
-                                         "), and the streaming run cannot serve these modes");
-        return false;
-    };
-    // (both are decided before any GPU call)
-    if (const char* v = std::getenv("FQD_ORDERED_RESIDENT")) if (std::atoi(v) == 0) return give_up("FQD_ORDERED_RESIDENT=0 turns that run off");
+    if (const char* v = std::getenv("FQD_ORDERED_RESIDENT")) if (std::atoi(v) == 0) return give_up(fast, "FQD_ORDERED_RESIDENT=0 turns that run off");
     if (!inflate_on_device()) {
-        bool gz = !modes;                                         // with a switch set only a `.gz` input needs the device inflate
+        bool gz = !fast.any();                                    // with a switch set only a `.gz` input needs the device inflate
         for (int s = 0; s < S; ++s) gz |= has_gz_extension(in[s]);
-        if (gz) return give_up("FQD_GUNZIP_DEVICE=0 keeps `.gz` inputs off the GPU");
+        if (gz) return give_up(fast, "FQD_GUNZIP_DEVICE=0 keeps `.gz` inputs off the GPU");
     }
-    // worth it when a codec is involved: a BGZF input, or a `.gz` output the GPU can deflate (plain files in and
-    // out are better off in the streaming run, where reading, the GPU and writing overlap)
     bool any_gz_in = false, any_gz_out = false, all_empty = true;
     for (int s = 0; s < S; ++s) {
         uint64_t size = 0;
-        if (!is_regular_file(in[s], size)) return give_up(in[s] + " is not a regular file: a pipe cannot be held in GPU memory");
+        if (!is_regular_file(in[s], size)) return give_up(fast, in[s] + " is not a regular file: a pipe cannot be held in GPU memory");
         all_empty &= size == 0;
         any_gz_in |= has_gz_extension(in[s]);
         any_gz_out |= has_gz_extension(out[s]);
     }
-    if (!modes && !any_gz_in && !(any_gz_out && deflate_on_device())) return false;
-    if (modes && all_empty) {
-        // no record, no cluster, nothing to choose: what the default run makes of empty files, and empty cluster files
-        // (the table of zeros is written whatever the default run makes of an empty file, behind its outputs)
-        struct LevelsOfNothing { bool on; const std::string& name; ~LevelsOfNothing() { if (on) write_cluster_lines(duplevels_text(fqd_size_levels{}), name + ".duplevels"); } }
-            levels_of_nothing{write_levels_, out[0]};
-        run_ordered(S, in, out);                                  // (no cluster, no filter: the second `-v` line is not said either)
-        if (write_clusters_) for (int s = 0; s < S; ++s) write_cluster_lines(std::string(), out[s] + ".clusters");
-        return true;
-    }
-    HIP_OK(hipSetDevice(tuning_.device));
-    StreamGuard stream;
-    const size_t fetch_bytes = fetch_bytes_for(block_bytes_for(tuning_, memlimit_), memlimit_);
-    FileOnDevice dev[2];
-    Device<uint8_t> keep;
-    Device<uint32_t> link, owner, perm; Device<uint8_t> head;     // FQD_FAST_KEEP / FQD_FAST_CLUSTERS / FQD_FAST_SIZEOUT / FQD_FAST_LEVELS
-    Device<uint32_t> cluster_size; fqd_size_levels levels{};      // FQD_FAST_SIZEOUT / FQD_FAST_LEVELS / FQD_FAST_SORT / FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE
-    Device<uint32_t> order; Device<uint8_t> all_kept;             // FQD_FAST_SORT=size: the written order and a set flag for each of its entries
-    uint64_t n_written = 0, dropped_clusters = 0, dropped_records = 0;
+    nothing = fast.any() && all_empty;
+    return fast.any() || any_gz_in || (any_gz_out && deflate_on_device());
+}
+
+// The buffers of a few stages, each released by the scope that ends behind its last reader.
+// FQD_FAST_STRAND=both and FQD_FAST_UMI: what the engine is given in place of the reads as they lie in the files, until the
+// last submit is through (with FQD_FAST_UMI_MISMATCH the second pass, and the merge, which reads umi_off).
+struct KeyedReads {
     Device<uint8_t> canon, turned; Device<uint64_t> canon_off[2]; Device<uint32_t> canon_len[2];   // FQD_FAST_STRAND=both
     Device<uint8_t> umi_text; Device<uint64_t> umi_off64; Device<uint32_t> umi_len, umi_off;        // FQD_FAST_UMI
-    Device<uint32_t> owner_seq, exact_size, merged_owner;        // FQD_FAST_UMI_MISMATCH
-    Device<uint32_t> weight;                                     // FQD_FAST_SIZEIN: what every record stands for, while sizes are made
     fqd_umi_info umi_info{};
-    uint32_t umi_bases = 0;
-    std::string clusters[2];
+    fqd_reads reads[2] = {}, umi_mate{};                         // what is submitted: the given or the canonical reads; mate 1 as `UMI bases ‖ sequence`
+};
+// Every duplicate's link to an earlier record of its key and the first record of the key, until the records are grouped.
+struct Links { Device<uint32_t> link, owner; };
+// The records grouped by owner: an order of the n records and a flag at the first place of every cluster; with
+// FQD_FAST_SIZEIN what every record stands for, while sizes are made.  Until the outputs are planned.
+struct Clusters { Device<uint32_t> perm; Device<uint8_t> head; Device<uint32_t> weight; uint64_t count = 0; };
+
+// What lives from stage to stage, in the order it comes to be.  A stage that returns false has found the input one for the
+// streaming run (give_up) before any output exists.
+struct OrderedResidentRun {
+    const FastModes& fast; const int S; const std::string* const in; const std::string* const out;
+    const Format format; const long long memlimit; const int device;
+    StreamGuard stream;
+    FileOnDevice dev[2]; FileOnDevice* files[2] = {&dev[0], &dev[1]};
     uint64_t n = 0, dups = 0;
-    std::unique_ptr<EngineHandle> eng;
+    Device<uint8_t> keep;
+    uint64_t merged_clusters = 0;                                // FQD_FAST_UMI_MISMATCH: the clusters the merge leaves
+    std::string cluster_text[2];                                 // FQD_FAST_CLUSTERS
+    Device<uint32_t> cluster_size; fqd_size_levels levels{};     // FQD_FAST_SIZEOUT / _LEVELS / _SORT / _MINSIZE / _MAXSIZE
+    uint64_t dropped_clusters = 0, dropped_records = 0;          // FQD_FAST_MINSIZE / _MAXSIZE
+    Device<uint32_t> order; Device<uint8_t> all_kept;            // FQD_FAST_SORT=size: the written order and a set flag for each of its entries
+    // what is written: pair k < upto is record idx[s][k] of file s (nullptr: record k), iff flags[k]; not_written only sizes
+    // the writer's windows.  Made once, for plan_survivors and write_survivors alike
+    const uint32_t* idx[2] = {nullptr, nullptr}; const uint8_t* flags = nullptr; uint64_t upto = 0, not_written = 0;
+    EngineUnderTheRead engine; fqd_engine* e = nullptr;
     SurvivorBuffers buffers;
-    std::thread make_engine; std::exception_ptr engine_error;
-    struct JoinGuard { std::thread& t; ~JoinGuard() { if (t.joinable()) t.join(); } } join_guard{make_engine};
-    try {
-        Fetched got[2];                                            // (way None: not fetched, an exception included)
+
+    OrderedResidentRun(const FastModes& fast_, int S_, const std::string* in_, const std::string* out_, Format format_, long long memlimit_, int device_)
+        : fast(fast_), S(S_), in(in_), out(out_), format(format_), memlimit(memlimit_), device(device_) {}
+
+    // Stage 2: the files go to HBM as they lie on disk, on a thread each, while the engine is made; they are inflated (if
+    // compressed) and cut into records there.  Only regular files of whole records, as many in file 2 as in file 1, go on.
+    bool fetch_and_scan(size_t fetch_bytes, Fetched (&got)[2])
+    {
         bool no_room[2] = {false, false};
         std::exception_ptr fetch_error[2];
-        // the engine — its key store and table sized from the files' sizes — is made on a helper thread under the reads
-        uint64_t cap_reads = 0, cap_bases = 0;
-        guess_capacity(S, in, cap_reads, cap_bases);
-        make_engine = std::thread([&] {
-            try { HIP_OK(hipSetDevice(tuning_.device)); StageClock::Scope t("  on the GPU: engine, key store, table (under the read)"); eng = std::make_unique<EngineHandle>(S, tuning_.device, stream, cap_reads, cap_bases); }
-            catch (...) { engine_error = std::current_exception(); }
-        });
+        engine = engine_under_the_read(S, in, device, stream, "  on the GPU: engine, key store, table (under the read)", [](uint64_t) {});
         {
             StageClock::Scope t("ordered/resident: files to HBM");
-            auto fetch = [&](int s) {
-                try { fetch_file(in[s], fetch_bytes, tuning_.device, dev[s], got[s]); }
+            run_parts(unsigned(S), [&](unsigned s) {
+                try { fetch_file(in[s], fetch_bytes, device, dev[s], got[s]); }
                 catch (const DeviceOutOfMemory&) { no_room[s] = true; }
                 catch (const DeviceError&) { fetch_error[s] = std::current_exception(); }
                 catch (const std::exception&) {}                           // the host reader will say what is wrong with the file
-            };
-            std::thread second;
-            if (S == 2) second = std::thread(fetch, 1);
-            fetch(0);
-            if (S == 2) second.join();
+            });
         }
-        if (make_engine.joinable()) make_engine.join();
+        engine.wait();
         for (int s = 0; s < S; ++s) if (fetch_error[s]) std::rethrow_exception(fetch_error[s]);
         for (int s = 0; s < S; ++s)
-            if (got[s].way == Fetched::None) return give_up(no_room[s] ? in[s] + " does not fit in GPU memory" : in[s] + " could not be taken to GPU memory as it lies on disk (empty, damaged, or changed while it was read)");
-        if (engine_error) std::rethrow_exception(engine_error);
+            if (got[s].way == Fetched::None) return give_up(fast, no_room[s] ? in[s] + " does not fit in GPU memory" : in[s] + " could not be taken to GPU memory as it lies on disk (empty, damaged, or changed while it was read)");
+        e = engine.get()->e;
         {
             StageClock::Scope t("ordered/resident: inflate + record scan on the GPU");
             for (int s = 0; s < S; ++s)
-                if (!cut_records(eng->e, stream, format_, got[s], dev[s])) return give_up(in[s] + " does not hold whole, well-formed records");
+                if (!cut_records(e, stream, format, got[s], dev[s])) return give_up(fast, in[s] + " does not hold whole, well-formed records");
         }
-        if (S == 2 && dev[0].n != dev[1].n) return give_up("the two files hold different numbers of records");
+        if (S == 2 && dev[0].n != dev[1].n) return give_up(fast, "the two files hold different numbers of records");
         n = dev[0].n;
-        if (linked && n >= 0x80000000ull)
-            throw FastModeRefusal(which + ": at most 2^31-1 records (pairs) per run, the input holds " + std::to_string(n));
-        if ((both_strands_ || umi_sep_) && n > 0xFFFFFFFEull)
-            throw FastModeRefusal(which + ": at most 2^32-2 records (pairs) per run, the input holds " + std::to_string(n));
-        StageClock::Scope t("ordered/resident: dedup on the GPU");
-        keep.reserve(n);
-        if (linked) { link.reserve(n); owner.reserve(n); perm.reserve(n); head.reserve(n); }
-        if (umi_mismatch_) { owner_seq.reserve(n); exact_size.reserve(n); merged_owner.reserve(n); }
+        if (fast.linked() && n >= 0x80000000ull)
+            throw FastModeRefusal(fast.names() + ": at most 2^31-1 records (pairs) per run, the input holds " + std::to_string(n));
+        if ((fast.both_strands || fast.umi) && n > 0xFFFFFFFEull)
+            throw FastModeRefusal(fast.names() + ": at most 2^32-2 records (pairs) per run, the input holds " + std::to_string(n));
+        return true;
+    }
+
+    // Stage 3, between the record scan and the submit loop.  FQD_FAST_STRAND=both: one fqd_canonical_reads over all n records.
+    // FQD_FAST_UMI behind it: fqd_umi_find over file 1's ID lines, then fqd_umi_reads, which packs `UMI bases ‖ sequence` of
+    // (the canonical) mate 1 for the submit loop's segment 0.  FQD_FAST_SIZEIN: fqd_size_annotations reads every record's weight
+    // off file 1's ID lines and holds file 2 against them.  A record that any of them refuses ends the run.
+    void rewrite_keys(KeyedReads& k, Clusters& clusters)
+    {
         // no more than a file's sequence bytes — a FASTQ record is its sequence twice (bases, qualities) and at least six
         // more bytes, a FASTA record its sequence and at least three
         auto seq_bound = [&](int s) -> uint64_t {
-            return format_ == Format::Fasta ? dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 3 * n)
-                                            : (dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 6 * n)) / 2 + 1;
+            return format == Format::Fasta ? dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 3 * n)
+                                           : (dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 6 * n)) / 2 + 1;
         };
-        fqd_reads given[2] = {};
-        for (int s = 0; s < S; ++s) {
-            given[s].bases = reinterpret_cast<const uint8_t*>(dev[s].text.p);
-            given[s].offsets = dev[s].seq_off.p; given[s].lengths = dev[s].seq_len.p;
-        }
-        if (both_strands_) {
+        for (int s = 0; s < S; ++s) k.reads[s] = fqd_reads{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].seq_off.p, dev[s].seq_len.p, 0, 0};
+        if (fast.both_strands) {
             // the canonical sequences and their descriptors
             uint64_t bound = 0;
             for (int s = 0; s < S; ++s) bound += seq_bound(s);
-            canon.reserve(bound + 64); turned.reserve(n);
-            for (int s = 0; s < S; ++s) { canon_off[s].reserve(n); canon_len[s].reserve(n); }
-            StageClock::Scope t2("fast: both strands, canonical reads on the GPU");
+            k.canon.reserve(bound + 64); k.turned.reserve(n);
+            for (int s = 0; s < S; ++s) { k.canon_off[s].reserve(n); k.canon_len[s].reserve(n); }
+            StageClock::Scope t("fast: both strands, canonical reads on the GPU");
             uint64_t n_turned = 0;
-            engine_ok<DeviceError>(eng->e, fqd_canonical_reads(eng->e, given, n, canon.p, bound, canon_off[0].p, canon_len[0].p,
-                                                               S == 2 ? canon_off[1].p : nullptr, S == 2 ? canon_len[1].p : nullptr, turned.p,
-                                                               StageClock::on() ? &n_turned : nullptr));
+            engine_ok<DeviceError>(e, fqd_canonical_reads(e, k.reads, n, k.canon.p, bound, k.canon_off[0].p, k.canon_len[0].p, S == 2 ? k.canon_off[1].p : nullptr,
+                                                          S == 2 ? k.canon_len[1].p : nullptr, k.turned.p, StageClock::on() ? &n_turned : nullptr));
+            for (int s = 0; s < S; ++s) k.reads[s] = fqd_reads{k.canon.p, k.canon_off[s].p, k.canon_len[s].p, 0, 0};
             if (StageClock::on()) std::cerr << "fast: both strands, " << n_turned << " of " << n << " records turned\n";
         }
-        if (umi_sep_) {
-            StageClock::Scope t2("fast: UMI, find and pack on the GPU");
+        if (fast.umi) {
+            StageClock::Scope t("fast: UMI, find and pack on the GPU");
             const uint8_t* text0 = reinterpret_cast<const uint8_t*>(dev[0].text.p);
-            umi_off.reserve(n);
-            fqd_umi_info& info = umi_info;
-            engine_ok<DeviceError>(eng->e, fqd_umi_find(eng->e, text0, dev[0].start.p, dev[0].id_len.p, n, umi_sep_, umi_off.p, &info));
+            k.umi_off.reserve(n);
+            fqd_umi_info& info = k.umi_info;
+            engine_ok<DeviceError>(e, fqd_umi_find(e, text0, dev[0].start.p, dev[0].id_len.p, n, fast.umi, k.umi_off.p, &info));
             if (info.bad_record != FQD_UMI_NO_RECORD)
-                throw FastModeRefusal(std::string(umi_switch(umi_sep_)) + ": record " + std::to_string(info.bad_record) + " (counted from 0) of " + in[0] +
-                                      ": " + umi_reason(info.bad_reason, umi_sep_));
-            umi_bases = info.n_bases;
+                throw FastModeRefusal(fast.umi_name() + ": record " + std::to_string(info.bad_record) + " (counted from 0) of " + in[0] + ": " + umi_reason(info.bad_reason, fast.umi));
             // mate 1's sequence bytes (with both strands the canonical mate 1 of a pair may be either file's read), the UMI
             // bases of every record, and the descriptors
-            const uint64_t bound = seq_bound(0) + (both_strands_ && S == 2 ? seq_bound(1) : 0) + uint64_t(umi_bases) * n;
-            umi_text.reserve(bound + 64); umi_off64.reserve(n); umi_len.reserve(n);
-            const fqd_reads mate0 = both_strands_ ? fqd_reads{canon.p, canon_off[0].p, canon_len[0].p, 0, 0} : given[0];
-            engine_ok<DeviceError>(eng->e, fqd_umi_reads(eng->e, text0, dev[0].start.p, umi_off.p, &info, &mate0, n, umi_text.p, bound, umi_off64.p, umi_len.p));
-            if (StageClock::on()) std::cerr << "fast: UMI, " << umi_bases << " bases behind the last '" << char(umi_sep_) << "' of the first word\n";
+            const uint64_t bound = seq_bound(0) + (fast.both_strands && S == 2 ? seq_bound(1) : 0) + uint64_t(info.n_bases) * n;
+            k.umi_text.reserve(bound + 64); k.umi_off64.reserve(n); k.umi_len.reserve(n);
+            engine_ok<DeviceError>(e, fqd_umi_reads(e, text0, dev[0].start.p, k.umi_off.p, &info, &k.reads[0], n, k.umi_text.p, bound, k.umi_off64.p, k.umi_len.p));
+            k.umi_mate = fqd_reads{k.umi_text.p, k.umi_off64.p, k.umi_len.p, 0, 0};
+            if (StageClock::on()) std::cerr << "fast: UMI, " << info.n_bases << " bases behind the last '" << char(fast.umi) << "' of the first word\n";
         }
-        if (size_in_) {
+        if (fast.size_in) {
             // the weights, before anything else is spent on an input with a malformed annotation
-            StageClock::Scope t2("fast: size annotations on the GPU");
-            weight.reserve(n);
+            StageClock::Scope t("fast: size annotations on the GPU");
+            clusters.weight.reserve(n);
             fqd_sizein_info info{};
             for (int s = 0; s < S; ++s) {
                 fqd_sizein_info found{};
-                engine_ok<DeviceError>(eng->e, fqd_size_annotations(eng->e, reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].start.p, dev[s].id_len.p, n,
-                                                                    s ? weight.p : nullptr, s ? nullptr : weight.p, nullptr, nullptr, &found));
+                engine_ok<DeviceError>(e, fqd_size_annotations(e, reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].start.p, dev[s].id_len.p, n,
+                                                               s ? clusters.weight.p : nullptr, s ? nullptr : clusters.weight.p, nullptr, nullptr, &found));
                 if (found.bad_record != FQD_UMI_NO_RECORD)
                     throw FastModeRefusal("FQD_FAST_SIZEIN=1: record " + std::to_string(found.bad_record) + " (counted from 0) of " + in[s] + ": " + sizein_reason(found.bad_reason));
                 if (s == 0) info = found;
             }
             if (StageClock::on()) std::cerr << "fast: size annotations, " << info.annotated << " of " << n << " records annotated, total weight " << info.total_weight << "\n";
         }
-        // fqd_cluster_sizes, or with FQD_FAST_SIZEIN the weighted sizes: a cluster above 2^31-1 ends the run
-        auto cluster_sizes = [&](uint32_t* size, fqd_size_levels* lv) {
-            if (!size_in_) { engine_ok<DeviceError>(eng->e, fqd_cluster_sizes(eng->e, perm.p, head.p, n, size, lv)); return; }
-            fqd_weights_info over{};
-            engine_ok<DeviceError>(eng->e, fqd_cluster_weights(eng->e, perm.p, head.p, weight.p, n, size, lv, &over));
-            if (over.over_record != FQD_UMI_NO_RECORD)
-                throw FastModeRefusal("FQD_FAST_SIZEIN=1: the cluster of record " + std::to_string(over.over_record) + " (counted from 0) of " + in[0] + " has the weighted size " +
-                                      std::to_string(over.over_sum) + ": at most 2147483647");
-        };
-        // all n records through the engine, batch by batch; with_umi: mate 1 as `UMI bases ‖ sequence`
-        auto submit_all = [&](bool with_umi) -> int {
-            const size_t kBatch = 16u << 20;
-            int rc = FQD_OK;
-            for (size_t a = 0; a < n && rc == FQD_OK; a += kBatch) {
-                fqd_reads seg[2] = {};
-                for (int s = 0; s < S; ++s) {
-                    seg[s].bases = both_strands_ ? canon.p : reinterpret_cast<const uint8_t*>(dev[s].text.p);
-                    seg[s].offsets = (both_strands_ ? canon_off[s].p : dev[s].seq_off.p) + a;
-                    seg[s].lengths = (both_strands_ ? canon_len[s].p : dev[s].seq_len.p) + a;
-                }
-                if (with_umi) seg[0] = fqd_reads{umi_text.p, umi_off64.p + a, umi_len.p + a, 0, 0};
-                if (linked) rc = fqd_submit_linked(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, link.p + a, a + kBatch < n ? 0 : 1);
-                else rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(eng->e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
-            }
-            if (rc == FQD_OK) rc = fqd_engine_sync(eng->e);
-            return rc;
-        };
-        int rc = submit_all(umi_sep_ != 0);
-        if (rc == FQD_ERR_BAD_BASE)                              // the streaming run cuts the output where the reference does
-            return give_up(std::string(fqd_last_error(eng->e)) + (umi_sep_ ? "; a position in mate 1 counts the " + std::to_string(umi_bases) + " UMI bases in front of the sequence" : std::string()));
-        if (rc != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e));
+    }
+
+    // Stage 4: all n records through the engine where they lie, batch by batch; with_umi: mate 1 as `UMI bases ‖ sequence`.
+    // The `linked` switches link every duplicate to an earlier record of its key (fqd_submit_linked).
+    int submit_all(const KeyedReads& k, Links& links, bool with_umi)
+    {
+        const size_t kBatch = 16u << 20;
+        int rc = FQD_OK;
+        for (size_t a = 0; a < n && rc == FQD_OK; a += kBatch) {
+            fqd_reads seg[2] = {with_umi ? k.umi_mate : k.reads[0], k.reads[1]};
+            for (int s = 0; s < S; ++s) { seg[s].offsets += a; seg[s].lengths += a; }
+            if (fast.linked()) rc = fqd_submit_linked(e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a, links.link.p + a, a + kBatch < n ? 0 : 1);
+            else rc = (a + kBatch < n ? fqd_submit : fqd_submit_final)(e, seg, std::min<size_t>(kBatch, n - a), FQD_MEM_DEVICE, keep.p + a);
+        }
+        if (rc == FQD_OK) rc = fqd_engine_sync(e);
+        return rc;
+    }
+
+    bool first_pass(const KeyedReads& k, Links& links)
+    {
+        const int rc = submit_all(k, links, fast.umi != 0);
+        if (rc == FQD_ERR_BAD_BASE)                                  // the streaming run cuts the output where the reference does
+            return give_up(fast, std::string(fqd_last_error(e)) + (fast.umi ? "; a position in mate 1 counts the " + std::to_string(k.umi_info.n_bases) + " UMI bases in front of the sequence" : std::string()));
+        if (rc != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(e));
+        return true;
+    }
+
+    // Stage 5, FQD_FAST_UMI_MISMATCH=1|2 (FQD_FAST_UMI is set): the engine is used TWICE.  The first pass, keyed `UMI bases ‖
+    // sequence`, gives the exact owners and, through fqd_group_owners and the sizes, every exact cluster's count; after
+    // fqd_engine_reset the same batches go in again keyed by the sequences alone, into the same flags and links — those of the
+    // first pass are used up by fqd_owners — which gives every record's sequence group.  fqd_umi_merge makes the merged owners
+    // of the three, fqd_owners_to_keep the flags; the merged owners are THE owners from here on.
+    void merge_umi_neighbours(const KeyedReads& k, Links& links, Clusters& clusters)
+    {
+        Device<uint32_t> owner_seq, exact_size, merged_owner;
+        owner_seq.reserve(n); exact_size.reserve(n); merged_owner.reserve(n);
+        uint64_t exact_clusters = 0;
+        {
+            StageClock::Scope t("fast: UMI mismatches, exact owners and counts on the GPU");
+            engine_ok<DeviceError>(e, fqd_owners(e, keep.p, links.link.p, n, links.owner.p));
+            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &exact_clusters));
+            cluster_sizes(clusters, exact_size.p, nullptr);
+        }
+        {
+            StageClock::Scope t("fast: UMI mismatches, second pass by sequence on the GPU");
+            engine_ok<DeviceError>(e, fqd_engine_reset(e));
+            if (submit_all(k, links, false) != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(e));
+            engine_ok<DeviceError>(e, fqd_owners(e, keep.p, links.link.p, n, owner_seq.p));
+        }
+        StageClock::Scope t("fast: UMI mismatches, networks on the GPU");
         fqd_umi_merge_info merged{};
-        if (umi_mismatch_) {
-            // the exact owners and counts, then the same records once more without their UMIs: the flags and links of the
-            // first pass are used up by fqd_owners and taken again
-            uint64_t exact_clusters = 0;
-            {
-                StageClock::Scope t2("fast: UMI mismatches, exact owners and counts on the GPU");
-                engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner.p));
-                engine_ok<DeviceError>(eng->e, fqd_group_owners(eng->e, owner.p, n, perm.p, head.p, &exact_clusters));
-                cluster_sizes(exact_size.p, nullptr);
-            }
-            {
-                StageClock::Scope t2("fast: UMI mismatches, second pass by sequence on the GPU");
-                engine_ok<DeviceError>(eng->e, fqd_engine_reset(eng->e));
-                if (submit_all(false) != FQD_OK) throw DeviceError(std::string("GPU engine: ") + fqd_last_error(eng->e));
-                engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner_seq.p));
-            }
-            StageClock::Scope t2("fast: UMI mismatches, networks on the GPU");
-            engine_ok<DeviceError>(eng->e, fqd_umi_merge(eng->e, reinterpret_cast<const uint8_t*>(dev[0].text.p), dev[0].start.p, umi_off.p, &umi_info, owner.p,
-                                                         owner_seq.p, exact_size.p, n, uint32_t(umi_mismatch_), merged_owner.p, &merged));
-            if (merged.over_limit_first != FQD_UMI_NO_RECORD)
-                throw FastModeRefusal(std::string(mismatch_switch(umi_mismatch_)) + ": the sequence of record " + std::to_string(merged.over_limit_first) + " (counted from 0) of " + in[0] +
-                                      " stands under " + std::to_string(merged.over_limit_nodes) + " different UMIs, a network of at most " + std::to_string(merged.max_group) +
-                                      " is merged (amplicon-style data: deduplicate it by exact UMI, without the switch)");
-            if (merged.nodes != exact_clusters) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
-            engine_ok<DeviceError>(eng->e, fqd_owners_to_keep(eng->e, merged_owner.p, n, keep.p));
-            if (StageClock::on())
-                std::cerr << "fast: UMI mismatches <= " << umi_mismatch_ << ", " << merged.merged << " of " << merged.nodes << " exact clusters merged into others, largest network "
-                          << merged.largest << ", " << merged.sweeps << " sweeps\n";
-            owner_seq.release(); exact_size.release();
-        }
-        canon.release(); turned.release();                       // the last submit is through: nothing below reads a turned byte
-        for (int s = 0; s < 2; ++s) { canon_off[s].release(); canon_len[s].release(); }
-        umi_text.release(); umi_off64.release(); umi_len.release(); umi_off.release();
-        if (std::getenv("FQD_TEST_FAIL_RESIDENT")) throw DeviceError("GPU engine: forced by FQD_TEST_FAIL_RESIDENT");      // tests: the hand-over is announced
+        engine_ok<DeviceError>(e, fqd_umi_merge(e, reinterpret_cast<const uint8_t*>(dev[0].text.p), dev[0].start.p, k.umi_off.p, &k.umi_info, links.owner.p,
+                                                owner_seq.p, exact_size.p, n, uint32_t(fast.umi_mismatch), merged_owner.p, &merged));
+        if (merged.over_limit_first != FQD_UMI_NO_RECORD)
+            throw FastModeRefusal(fast.mismatch_name() + ": the sequence of record " + std::to_string(merged.over_limit_first) + " (counted from 0) of " + in[0] + " stands under " +
+                                  std::to_string(merged.over_limit_nodes) + " different UMIs, a network of at most " + std::to_string(merged.max_group) +
+                                  " is merged (amplicon-style data: deduplicate it by exact UMI, without the switch)");
+        if (merged.nodes != exact_clusters) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
+        engine_ok<DeviceError>(e, fqd_owners_to_keep(e, merged_owner.p, n, keep.p));
+        if (StageClock::on())
+            std::cerr << "fast: UMI mismatches <= " << fast.umi_mismatch << ", " << merged.merged << " of " << merged.nodes << " exact clusters merged into others, largest network "
+                      << merged.largest << ", " << merged.sweeps << " sweeps\n";
+        merged_clusters = merged.nodes - merged.merged;
+        links.owner.swap(merged_owner);                              // (the exact owners leave with this stage)
+    }
+
+    // Stage 6: the duplicates are counted and, for the `linked` switches, the links resolved to the first record of every key
+    // (fqd_owners; done already where the merge made the owners) and the records grouped by it (fqd_group_owners) ...
+    void count_and_group(Links& links, Clusters& clusters)
+    {
         fqd_stats st{};
-        fqd_get_stats(eng->e, &st);
-        dups = umi_mismatch_ ? n - (merged.nodes - merged.merged) : st.duplicates;
-        FileOnDevice* all_files[2] = {&dev[0], &dev[1]};
-        if (linked) {
-            uint64_t n_clusters = 0;
-            {
-                StageClock::Scope t2("fast: owners and clusters on the GPU");
-                if (!umi_mismatch_) engine_ok<DeviceError>(eng->e, fqd_owners(eng->e, keep.p, link.p, n, owner.p));
-                engine_ok<DeviceError>(eng->e, fqd_group_owners(eng->e, umi_mismatch_ ? merged_owner.p : owner.p, n, perm.p, head.p, &n_clusters));
-            }
-            if (n_clusters + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
-            link.release(); owner.release(); merged_owner.release();
-            if (keep_best_) {
-                const uint64_t moved = pick_best_members(eng->e, S, all_files, n, head.p, perm.p, "fast: best-quality pick on the GPU");
-                engine_ok<DeviceError>(eng->e, fqd_heads_to_keep(eng->e, perm.p, head.p, n, keep.p));
-                if (StageClock::on()) std::cerr << "fast: best-quality pick, " << moved << " of " << n_clusters << " clusters changed\n";
-            }
-            if (write_clusters_) {
-                StageClock::Scope t2("fast: ID lines of the clusters out of HBM");
-                for (int s = 0; s < S; ++s) clusters[s] = cluster_lines(eng->e, stream, dev[s], perm.p, head.p, n);
-            }
-            if (size_out_ || write_levels_ || sort_by_size_ || size_filter_) {
-                StageClock::Scope t2("fast: cluster sizes on the GPU");
-                cluster_size.reserve(n);
-                cluster_sizes(cluster_size.p, &levels);
-                weight.release();
-                if (StageClock::on()) std::cerr << "fast: cluster sizes, " << n_clusters << " clusters, largest " << levels.largest << "\n";
-            }
-            if (size_filter_) {
-                // the clusters outside the bounds leave the flags; the cluster files and the level table have been made of all
-                StageClock::Scope t2("fast: size filter on the GPU");
-                engine_ok<DeviceError>(eng->e, fqd_size_filter(eng->e, cluster_size.p, n, min_size_, max_size_, keep.p, &dropped_clusters, &dropped_records));
-                if (StageClock::on()) std::cerr << "fast: size filter, " << dropped_clusters << " clusters of " << dropped_records << " records not written\n";
-            }
-            n_written = n_clusters - dropped_clusters;
-            if (sort_by_size_) {
-                order.reserve(std::max<uint64_t>(n_written, 1)); all_kept.reserve(std::max<uint64_t>(n_written, 1));    // (a filter may leave nothing)
-                uint64_t w = 0;
-                fqd_size_order_info sorted{};
-                {
-                    StageClock::Scope t2("fast: abundance order on the GPU");
-                    engine_ok<DeviceError>(eng->e, fqd_size_order_ex(eng->e, perm.p, head.p, cluster_size.p, keep.p, n, order.p, &w, &sorted));
-                    if (w != n_written) throw DeviceError("GPU engine: internal error (the written order and the kept clusters differ in number)");
-                    if (w) HIP_OK(hipMemsetAsync(all_kept.p, 1, w, stream));
-                    HIP_OK(hipStreamSynchronize(stream));
-                }
-                // (what the call counted: the pairs of tier 1's bucket 0, which alone went through tier 2's passes)
-                if (StageClock::on())
-                    std::cerr << "fast: abundance order, " << w << " clusters written, " << sorted.large << " of them above 255 members sorted apart\n";
-            }
-            if (!size_out_) cluster_size.release();
-            perm.release(); head.release();
+        fqd_get_stats(e, &st);
+        dups = fast.umi_mismatch ? n - merged_clusters : st.duplicates;
+        if (!fast.linked()) return;
+        {
+            StageClock::Scope t("fast: owners and clusters on the GPU");
+            if (!fast.umi_mismatch) engine_ok<DeviceError>(e, fqd_owners(e, keep.p, links.link.p, n, links.owner.p));
+            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
         }
-        // everything the writer needs is reserved HERE, while the run can still hand over: once an output exists it cannot
+        if (clusters.count + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
+    }
+
+    // fqd_cluster_sizes: the member count of every cluster at the record that is written, 4 bytes a record, and the level
+    // table; with FQD_FAST_SIZEIN fqd_cluster_weights stands in its place: a cluster above 2^31-1 ends the run.
+    void cluster_sizes(const Clusters& c, uint32_t* size, fqd_size_levels* lv)
+    {
+        if (!fast.size_in) { engine_ok<DeviceError>(e, fqd_cluster_sizes(e, c.perm.p, c.head.p, n, size, lv)); return; }
+        fqd_weights_info over{};
+        engine_ok<DeviceError>(e, fqd_cluster_weights(e, c.perm.p, c.head.p, c.weight.p, n, size, lv, &over));
+        if (over.over_record != FQD_UMI_NO_RECORD)
+            throw FastModeRefusal("FQD_FAST_SIZEIN=1: the cluster of record " + std::to_string(over.over_record) + " (counted from 0) of " + in[0] + " has the weighted size " +
+                                  std::to_string(over.over_sum) + ": at most 2147483647");
+    }
+
+    // ... then, while perm and head exist: FQD_FAST_KEEP=best moves the keep flag of every cluster to its best member
+    // (pick_best_members, fqd_heads_to_keep); FQD_FAST_CLUSTERS takes the clusters' ID lines; the sizes are made for whatever
+    // reads them (FastModes::sized), and the weights released behind them; fqd_size_filter clears the flags of the clusters
+    // outside the bounds — behind the cluster files and the level table, which hold all clusters; fqd_size_order writes the
+    // records that stay in order of decreasing cluster size.  The sizes stay for the writer with FQD_FAST_SIZEOUT only.
+    void pick_size_filter_order(Clusters& c)
+    {
+        if (fast.keep_best) {
+            const uint64_t moved = pick_best_members(e, S, files, n, c.head.p, c.perm.p, "fast: best-quality pick on the GPU");
+            engine_ok<DeviceError>(e, fqd_heads_to_keep(e, c.perm.p, c.head.p, n, keep.p));
+            if (StageClock::on()) std::cerr << "fast: best-quality pick, " << moved << " of " << c.count << " clusters changed\n";
+        }
+        if (fast.clusters) {
+            StageClock::Scope t("fast: ID lines of the clusters out of HBM");
+            for (int s = 0; s < S; ++s) cluster_text[s] = cluster_lines(e, stream, dev[s], c.perm.p, c.head.p, n);
+        }
+        if (fast.sized()) {
+            StageClock::Scope t("fast: cluster sizes on the GPU");
+            cluster_size.reserve(n);
+            cluster_sizes(c, cluster_size.p, &levels);
+            c.weight.release();
+            if (StageClock::on()) std::cerr << "fast: cluster sizes, " << c.count << " clusters, largest " << levels.largest << "\n";
+        }
+        if (fast.size_filter()) {
+            StageClock::Scope t("fast: size filter on the GPU");
+            engine_ok<DeviceError>(e, fqd_size_filter(e, cluster_size.p, n, fast.min_size, fast.max_size, keep.p, &dropped_clusters, &dropped_records));
+            if (StageClock::on()) std::cerr << "fast: size filter, " << dropped_clusters << " clusters of " << dropped_records << " records not written\n";
+        }
+        if (fast.sort_by_size) {
+            const uint64_t stay = c.count - dropped_clusters;
+            order.reserve(std::max<uint64_t>(stay, 1)); all_kept.reserve(std::max<uint64_t>(stay, 1));    // (a filter may leave nothing)
+            fqd_size_order_info sorted{};
+            {
+                StageClock::Scope t("fast: abundance order on the GPU");
+                engine_ok<DeviceError>(e, fqd_size_order_ex(e, c.perm.p, c.head.p, cluster_size.p, keep.p, n, order.p, &upto, &sorted));
+                if (upto != stay) throw DeviceError("GPU engine: internal error (the written order and the kept clusters differ in number)");
+                if (upto) HIP_OK(hipMemsetAsync(all_kept.p, 1, upto, stream));
+                HIP_OK(hipStreamSynchronize(stream));
+            }
+            // (what the call counted: the pairs of tier 1's bucket 0, which alone went through tier 2's passes)
+            if (StageClock::on()) std::cerr << "fast: abundance order, " << upto << " clusters written, " << sorted.large << " of them above 255 members sorted apart\n";
+            // pair k is record order[k], of both files; every pair is written
+            idx[0] = idx[1] = order.p; flags = all_kept.p;
+            buffers.record_keep = keep.p; buffers.records = n;
+        }
+        if (!fast.size_out) cluster_size.release();
+    }
+
+    // Stage 7: everything the writer needs is reserved HERE, while the run can still hand over: once an output exists it
+    // cannot.  With FQD_FAST_SORT=size pair k is record order[k] of both files and every pair is written — the labels of
+    // FQD_FAST_SIZEOUT are still found per record and brought into the order by the writer (survivor_writer.cpp), which has the
+    // sizes in written order once the plan is made.  A filter alone needs no index: the cleared flags go through the plan.
+    void plan()
+    {
         bool gz_out[2] = {false, false};
         for (int s = 0; s < S; ++s) gz_out[s] = has_gz_extension(out[s]);
-        FileOnDevice* files[2] = {&dev[0], &dev[1]};
-        if (size_out_) { buffers.cluster_size = cluster_size.p; buffers.size_in = size_in_; }
-        if (sort_by_size_) {
-            // pair k is record order[k], of both files; every pair is written
-            const uint32_t* idx[2] = {order.p, order.p};
-            buffers.record_keep = keep.p; buffers.records = n;
-            plan_survivors(eng->e, S, files, idx, all_kept.p, n_written, gz_out, memlimit_, buffers);
-            cluster_size.release();                               // (the writer has the sizes in written order)
-        } else {
-            const uint32_t* idx[2] = {nullptr, nullptr};
-            plan_survivors(eng->e, S, files, idx, keep.p, n, gz_out, memlimit_, buffers);
+        if (fast.size_out) { buffers.cluster_size = cluster_size.p; buffers.size_in = fast.size_in; }
+        if (!fast.sort_by_size) { flags = keep.p; upto = n; not_written = dups + dropped_clusters; }
+        plan_survivors(e, S, files, idx, flags, upto, gz_out, memlimit, buffers);
+        if (fast.sort_by_size) cluster_size.release();
+    }
+
+    // Stage 8: from here on the run is this one's: outputs are created, filled and closed — the survivors in the written
+    // order window by window (deflated on the device for `.gz` outputs), the cluster files and the level table beside them.
+    void write()
+    {
+        std::unique_ptr<OutputFile> sink[2];
+        for (int s = 0; s < S; ++s) sink[s] = std::make_unique<OutputFile>(out[s]);
+        OutputFile* sinks[2] = {sink[0].get(), sink[1].get()};
+        if (fast.clusters)
+            for (int s = 0; s < S; ++s) { write_cluster_lines(cluster_text[s], out[s] + ".clusters"); std::string().swap(cluster_text[s]); }
+        if (fast.levels) write_cluster_lines(duplevels_text(levels), out[0] + ".duplevels");
+        StageClock::Scope t("ordered/resident: survivors out of HBM");
+        write_survivors(e, stream, S, files, idx, flags, upto, not_written, sinks, format, memlimit, true, &buffers);
+    }
+};
+
+} // namespace
+
+// Everything about the eleven switches that their values and the command line decide, before any GPU call.
+void HashDupRemover::read_fast_modes(bool unordered)
+{
+    fast_ = FastModes::from_env();
+    fast_.check(unordered, tuning_.devices.size(), format_);
+    if (fast_.any() && tuning_.devices.size() == 1) { tuning_.device = tuning_.devices[0]; tuning_.devices.clear(); }
+}
+
+// An ordered run (single-end, or paired files read side by side) with a codec at either end — BGZF inputs, or `.gz`
+// outputs of plain regular inputs — or with a FQD_FAST_* switch set: every read (pair) is deduplicated where it lies in
+// HBM, and the survivors leave window by window.  false: not taken, returned BEFORE any output is touched, and the
+// streaming run (run_ordered), which reproduces the reference's behaviour for every irregular input, does the job.
+bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const std::string* out)
+{
+    bool nothing = false;
+    if (!resident_run_taken(fast_, S, in, out, nothing)) return false;                                       // stage 1
+    if (nothing) {
+        // no record, no cluster, nothing to choose: what the default run makes of empty files, and empty cluster files
+        // (the table of zeros is written whatever the default run makes of an empty file, behind its outputs)
+        struct LevelsOfNothing { bool on; const std::string& name; ~LevelsOfNothing() { if (on) write_cluster_lines(duplevels_text(fqd_size_levels{}), name + ".duplevels"); } }
+            levels_of_nothing{fast_.levels, out[0]};
+        run_ordered(S, in, out);                                  // (no cluster, no filter: the second `-v` line is not said either)
+        if (fast_.clusters) for (int s = 0; s < S; ++s) write_cluster_lines(std::string(), out[s] + ".clusters");
+        return true;
+    }
+    HIP_OK(hipSetDevice(tuning_.device));
+    OrderedResidentRun run(fast_, S, in, out, format_, memlimit_, tuning_.device);
+    const uint64_t& n = run.n;
+    try {
+        // (way None: not fetched, an exception included.  A BGZF file's packed bytes stay until the outputs are planned:
+        // gigabytes freed in mid-run are cleared by the driver while the process's next hipMalloc waits)
+        Fetched got[2];
+        if (!run.fetch_and_scan(fetch_bytes_for(block_bytes_for(tuning_, memlimit_), memlimit_), got)) return false;   // stage 2
+        StageClock::Scope t("ordered/resident: dedup on the GPU");
+        run.keep.reserve(n);
+        {
+            Clusters clusters;
+            {
+                Links links;
+                if (fast_.linked()) { links.link.reserve(n); links.owner.reserve(n); clusters.perm.reserve(n); clusters.head.reserve(n); }
+                {
+                    KeyedReads keyed;
+                    run.rewrite_keys(keyed, clusters);                                                       // stage 3
+                    if (!run.first_pass(keyed, links)) return false;                                         // stage 4
+                    if (fast_.umi_mismatch) run.merge_umi_neighbours(keyed, links, clusters);                // stage 5
+                }
+                if (std::getenv("FQD_TEST_FAIL_RESIDENT")) throw DeviceError("GPU engine: forced by FQD_TEST_FAIL_RESIDENT");      // tests: the hand-over is announced
+                run.count_and_group(links, clusters);                                                        // stage 6 ...
+            }
+            if (fast_.linked()) run.pick_size_filter_order(clusters);
         }
+        run.plan();                                                                                          // stage 7
     } catch (const FastModeRefusal&) {
         throw;                                                    // nothing has been written
     } catch (const DeviceOutOfMemory&) {
-        // (what the two size switches and the mismatch switch add, named only when one of them is set)
-        const bool sized = size_out_ || write_levels_ || sort_by_size_ || size_filter_;
-        const std::string sizes = (!sized ? std::string() :
-            std::string("; the cluster sizes of ") + (size_out_ ? "FQD_FAST_SIZEOUT" : write_levels_ ? "FQD_FAST_LEVELS" : sort_by_size_ ? "FQD_FAST_SORT" : "FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE") +
-            " take 4 bytes a record more" +
-            (size_out_ ? " and the labels' places and grown sizes 8 bytes a record and file" : "") +
-            (size_in_ ? std::string("; FQD_FAST_SIZEIN takes 4 bytes a record for the weights while the sizes are made") +
-                        (size_out_ ? " and 4 bytes a record and file for the annotations' lengths in the writer" : "") : std::string())) +
-            (!sort_by_size_ ? std::string() : std::string("; FQD_FAST_SORT=size takes 4 bytes a cluster for the written order, 1 byte a cluster for its flags and, while it sorts, "
-                                                          "24 bytes a cluster of scratch (the scratch of the grouping serves where it is as large)") +
-                                              (size_out_ ? ", and the labels' places and the sizes in written order 4 bytes a cluster and file and 4 bytes a cluster" : "")) +
-            (!umi_mismatch_ ? std::string() : std::string("; FQD_FAST_UMI_MISMATCH takes 12 bytes a record more (the owners by sequence, the exact counts, the merged owners) "
-                                                          "and, while it merges, 4 bytes a record and up to 66 bytes an exact cluster"));
-        if (umi_sep_)
-            return give_up(std::string("the text, the record arrays, the keyed bytes of FQD_FAST_UMI (mate 1's sequence bytes once more and the UMI bases of every record, 16 bytes a record)") +
-                           (both_strands_ ? ", the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record)" : "") +
-                           " and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory" + sizes);
-        return give_up((both_strands_ ? "the text, the record arrays, the canonical reads (the sequence bytes once more, 12 bytes a record and mate, 1 byte a record) and, with FQD_FAST_KEEP / FQD_FAST_CLUSTERS, up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory"
-                                     : "the text, the record arrays and up to 37 bytes a record for the links, the owners and their grouping do not fit in GPU memory") + sizes);   // the streaming run needs a few blocks of HBM only
+        return give_up(fast_, fast_.out_of_memory_note());        // (the streaming run needs a few blocks of HBM only)
     } catch (const DeviceError& e) {
-        if (modes) return give_up(e.what());
+        if (fast_.any()) return give_up(fast_, e.what());
         announce_handover("the GPU-resident ordered run", e);     // nothing has been written yet
         return false;
     } catch (const std::exception& e) {
-        if (modes) if (const DiagnosedError* d = dynamic_cast<const DiagnosedError*>(&e)) std::cerr << d->diag;   // what the host reader found, in full
-        return give_up(e.what());                                 // an input the host reader will report on in the reference's words
+        if (fast_.any()) if (const DiagnosedError* d = dynamic_cast<const DiagnosedError*>(&e)) std::cerr << d->diag;   // what the host reader found, in full
+        return give_up(fast_, e.what());                          // an input the host reader will report on in the reference's words
     }
-    // from here on the run is this one's: outputs are created, filled and closed
-    OutputFile sink0(out[0]);
-    std::unique_ptr<OutputFile> sink1;
-    if (S == 2) sink1 = std::make_unique<OutputFile>(out[1]);
-    OutputFile* sinks[2] = {&sink0, sink1.get()};
-    if (write_clusters_)
-        for (int s = 0; s < S; ++s) { write_cluster_lines(clusters[s], out[s] + ".clusters"); std::string().swap(clusters[s]); }
-    if (write_levels_) write_cluster_lines(duplevels_text(levels), out[0] + ".duplevels");
-    {
-        StageClock::Scope t("ordered/resident: survivors out of HBM");
-        FileOnDevice* files[2] = {&dev[0], &dev[1]};
-        const uint32_t* by_order[2] = {order.p, order.p};
-        const uint32_t* idx[2] = {nullptr, nullptr};
-        // (the count of pairs that are not written only sizes the windows)
-        if (sort_by_size_) write_survivors(eng->e, stream, S, files, by_order, all_kept.p, n_written, 0, sinks, format_, memlimit_, true, &buffers);
-        else write_survivors(eng->e, stream, S, files, idx, keep.p, n, dups + dropped_clusters, sinks, format_, memlimit_, true, &buffers);
-    }
+    run.write();                                                                                             // stage 8
     if (tuning_.leave_memory_to_exit) g_leave_memory_to_exit = true;
     StageClock::report();
-    summary_.total = n; summary_.duplicates = dups; summary_.unmatched = 0;
+    summary_.total = run.n; summary_.duplicates = run.dups; summary_.unmatched = 0;
     if (verbose_) print_summary(S, summary_.total, summary_.duplicates);
-    print_not_written(dropped_clusters, dropped_records);
+    // FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE: what `-v` says behind its first line
+    if (verbose_ && fast_.size_filter())
+        std::cout << run.dropped_clusters << " clusters holding " << run.dropped_records << (S == 1 ? " reads" : " read pairs") << " were not written (FQD_FAST_MINSIZE=" << fast_.min_size
+                  << ", FQD_FAST_MAXSIZE=" << (fast_.max_size ? std::to_string(fast_.max_size) : std::string("none")) << ").\n";
     return true;
 }
 
@@ -613,27 +443,9 @@ void HashDupRemover::run_unordered_resident(const std::string* in, const std::st
     HIP_OK(hipSetDevice(tuning_.device));
     StreamGuard stream_guard;
     const hipStream_t stream = stream_guard;
-    // the engine — key store and table sized from the files' sizes — is made on a helper thread under the reads of the
-    // inputs: its first use comes after them (guess_capacity)
     JoinedPairs jp;                                           // (before `eng`: the helper thread makes room in it, and eng's destructor joins that thread first)
-    struct LazyEngine {
-        std::unique_ptr<EngineHandle> holder; std::thread maker; std::exception_ptr error;
-        ~LazyEngine() { if (maker.joinable()) maker.join(); }
-        fqd_engine* get() { if (maker.joinable()) maker.join(); if (error) std::rethrow_exception(error); return holder->e; }
-    } eng;
-    {
-        uint64_t cap_reads = 0, cap_bases = 0;
-        guess_capacity(2, in, cap_reads, cap_bases);
-        eng.maker = std::thread([this, &eng, &jp, stream, cap_reads, cap_bases] {
-            try {
-                HIP_OK(hipSetDevice(tuning_.device));
-                StageClock::Scope t("  on the GPU: engine, key store, table, join arrays (under the read)");
-                eng.holder = std::make_unique<EngineHandle>(2, tuning_.device, stream, cap_reads, cap_bases);
-                if (cap_reads) jp.prepare(cap_reads);
-            }
-            catch (...) { eng.error = std::current_exception(); }
-        });
-    }
+    EngineUnderTheRead eng = engine_under_the_read(2, in, tuning_.device, stream, "  on the GPU: engine, key store, table, join arrays (under the read)",
+                                                   [&jp](uint64_t reads) { if (reads) jp.prepare(reads); });
     const size_t block_bytes = block_bytes_for(tuning_, memlimit_), fetch_bytes = fetch_bytes_for(block_bytes, memlimit_);
 
     FileOnDevice dev[2];
@@ -669,7 +481,7 @@ void HashDupRemover::run_unordered_resident(const std::string* in, const std::st
         for (int s = 0; s < 2; ++s) {
             if (got[s].way == Fetched::None) continue;
             StageClock::Scope t2("unordered/resident: inflate + record scan on the GPU");
-            if (!cut_records(eng.get(), stream, format_, got[s], dev[s])) {             // read it again the host way: that one reports
+            if (!cut_records(eng.get()->e, stream, format_, got[s], dev[s])) {             // read it again the host way: that one reports
                 dev[s].forget();
                 got[s].packed = CompressedOnDevice();
                 load(s);
@@ -682,7 +494,7 @@ void HashDupRemover::run_unordered_resident(const std::string* in, const std::st
         for (int s = 0; s < 2; ++s) {
             FileOnDevice& f = dev[s];
             f.tag_off.reserve(f.n); f.tag_len.reserve(f.n);
-            engine_ok(eng.get(), fqd_extract_tags(eng.get(), reinterpret_cast<const uint8_t*>(f.text.p), f.start.p, f.id_len.p, f.n, f.tag_off.p, f.tag_len.p));
+            engine_ok(eng.get()->e, fqd_extract_tags(eng.get()->e, reinterpret_cast<const uint8_t*>(f.text.p), f.start.p, f.id_len.p, f.n, f.tag_off.p, f.tag_len.p));
         }
     }
 
@@ -696,7 +508,7 @@ void HashDupRemover::run_unordered_resident(const std::string* in, const std::st
     // them (DeviceOutOfMemory) still hands the job to the two-pass run.  On disk nothing differs from the reference's
     // order — outputs opened after the sort phase, then the merge (hpp:265-266) — a bad base found by the dedup cuts the
     // output at the same pair either way.
-    fqd_engine* engine_now = eng.get();                        // (joins the helper thread: jp is ours from here on)
+    fqd_engine* engine_now = eng.get()->e;                        // (joins the helper thread: jp is ours from here on)
     join_and_dedup(engine_now, stream, side, tuning_.reference_tail_rule, jp);
     const uint64_t n_proc = jp.n_proc, upto = std::min<uint64_t>(n_proc, jp.written_below);
     uint64_t dups = 0;
@@ -711,7 +523,7 @@ void HashDupRemover::run_unordered_resident(const std::string* in, const std::st
     SurvivorBuffers buffers;
     {
         const bool gz_out[2] = {has_gz_extension(out[0]), has_gz_extension(out[1])};
-        plan_survivors(eng.get(), 2, files, idx, jp.keep.p, upto, gz_out, memlimit_, buffers);
+        plan_survivors(eng.get()->e, 2, files, idx, jp.keep.p, upto, gz_out, memlimit_, buffers);
     }
 
     OutputFile sink0(out[0]), sink1(out[1]);
@@ -720,7 +532,7 @@ void HashDupRemover::run_unordered_resident(const std::string* in, const std::st
     // ---- outputs: the device assembles windows of survivors in output order, the host writes them -----
     {
         StageClock::Scope t("unordered/resident: survivors out of HBM");
-        write_survivors(eng.get(), stream, 2, files, idx, jp.keep.p, upto, dups, sinks, format_, memlimit_, true, &buffers);
+        write_survivors(eng.get()->e, stream, 2, files, idx, jp.keep.p, upto, dups, sinks, format_, memlimit_, true, &buffers);
     }
     if (tuning_.leave_memory_to_exit) g_leave_memory_to_exit = true;
     StageClock::report();
