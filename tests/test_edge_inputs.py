@@ -1,9 +1,11 @@
-"""The inputs of tests/test_gpu_scan_edges.py, test_gpu_plan_edges.py and test_gpu_hamming_walk.py held to their own claims
-on the host: those tests are only as good as the places their newlines, sums and clusters fall on.  No GPU."""
+"""The inputs of tests/test_gpu_scan_edges.py, test_gpu_plan_edges.py, test_gpu_hamming_walk.py and test_gpu_join_edges.py
+held to their own claims on the host: those tests are only as good as the places their newlines, sums, clusters, key
+fields and runs fall on.  No GPU."""
 import numpy as np
 import pytest
 
 import hamming_walk_cases as hw
+import join_edge_cases as jc
 import plan_edge_cases as pc
 import scan_edge_cases as sc
 import seq_reference as ref
@@ -255,3 +257,199 @@ def test_hamming_large_distances_leave_one_cluster_per_length(d):
         lens = [tuple(len(m) for m in r) for r in recs]
         assert want == [1] + [int(a != b) for a, b in zip(lens, lens[1:])]
     assert sum(hw.flags(dict(hw.large_distance_lists(d))["main"])) == 1
+
+
+# ---- join --------------------------------------------------------------------------------------------------------------
+SORT_CASES = list(jc.sort_cases())
+JOIN_CASES = list(jc.join_cases())
+
+
+def hold_to_claims(name, tags, claims):
+    table = jc.code_table(tags)
+    for what in ("min_len", "max_len", "B"):
+        if what in claims:
+            assert getattr(table, what) == claims[what], (name, what)
+    for p, w in claims.get("widths", {}).items():
+        assert table.width[p] == w, (name, p)
+    assert table.B == sum(table.width) and (not table.width or table.lsb[-1] == 0)
+    if "n_min_len" in claims:
+        assert sum(len(t) == table.min_len for t in tags) == claims["n_min_len"], name
+    if "crosses" in claims:
+        p, bit = claims["crosses"]
+        assert table.lsb[p] < bit < table.lsb[p] + table.width[p], name               # bits of the field on either side
+        assert jc.deciders(tags, table, p, bit) >= claims["decided_by"], name
+    return table
+
+
+@pytest.mark.parametrize("name,tags,claims", SORT_CASES, ids=[c[0] for c in SORT_CASES])
+def test_join_sort_case_keeps_its_claims_and_keys_order_as_bytes(name, tags, claims):
+    table = hold_to_claims(name, tags, claims)
+    order = jc.reference_sort(tags)
+    assert sorted(range(len(tags)), key=lambda i: jc.key_of(tags[i], table)) == order
+    keys = {}
+    for t in tags:
+        assert keys.setdefault(jc.key_of(t, table), t) == t                             # distinct tags, distinct keys
+    assert all(k < 2 ** table.B for k in keys) and len(tags) <= 3000
+
+
+def test_join_width_cases_reach_every_width_with_and_without_end():
+    got = {(claims["widths"][1], kind) for kind, make, ks in (("fixed", jc.width_fixed, jc.FIXED_KS), ("ragged", jc.width_ragged, jc.RAGGED_KS))
+           for k in ks for _, claims in [make(k)]}
+    assert {(w, "fixed") for w in range(1, 9)} | {(w, "ragged") for w in range(1, 10)} == got
+    assert jc.FIXED_KS == [2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 64, 65, 128, 129, 256]
+    for k in jc.FIXED_KS:
+        tags, _ = jc.width_fixed(k)
+        assert {0, 255} <= {t[1] for t in tags} and len({t[1] for t in tags}) == k
+    for k in jc.RAGGED_KS:                                       # 2^w - 1 values: END fits; 2^w: END costs a bit
+        assert jc.width_ragged(k)[1]["widths"][1] == (k.bit_length() if k & (k + 1) == 0 else (k - 1).bit_length() + (k & (k - 1) == 0))
+    for k in jc.MINLEN_KS:
+        below, at = jc.width_at_min_len(k, False)[1]["widths"], jc.width_at_min_len(k, True)[1]["widths"]
+        assert (below[2], at[3]) == ((k - 1).bit_length(), k.bit_length())
+    assert jc.width_at_min_len(256, True)[1]["widths"][3] == 9 == jc.width_ragged(256)[1]["widths"][1]
+
+
+def test_join_key_word_cases_cover_the_asked_places():
+    for bit in (64, 128):
+        for w in range(2, 9):
+            ts = {t for ww, t, b in jc.CROSSINGS if (ww, b) == (w, bit)}
+            assert {bit - w + 1, bit - 1} <= ts and (w not in (2, 5, 8) or ts == set(range(bit - w + 1, bit)))
+    assert {63, 64, 65, 127, 128, 129, 130} == set(jc.KEY_BITS)
+    table = jc.code_table(jc.one_bit_fields(130)[0])
+    assert [sum(1 for l in table.lsb if 64 * word <= l < 64 * word + 64) for word in range(3)] == [64, 64, 2]
+
+
+def test_join_census_cases_straddle_the_lds_rows():
+    assert {jc.CENSUS_LDS - 1, jc.CENSUS_LDS, jc.CENSUS_LDS + 1} <= {n - 1 for n in jc.CENSUS_LENGTHS}
+    for length in jc.CENSUS_LENGTHS:
+        tags, _ = jc.census_last(length)
+        assert len({t[:-1] for t in tags}) == 1 and len({t[-1] for t in tags}) == 200
+    tags, _ = jc.census_four()
+    table = jc.code_table(tags)
+    assert [p for p, w in enumerate(table.width) if w] == [158, 159, 160, 161]
+    order = jc.reference_sort(tags)
+    assert any(tags[x][:159] == tags[y][:159] and tags[x][159] != tags[y][159] for x, y in zip(order, order[1:]))
+
+
+@pytest.mark.parametrize("length", jc.HEAD_LENGTHS)
+def test_join_head_cases_differ_where_they_say(length):
+    a, b = jc.head_groups(length)
+    table = jc.code_table(a + b)
+    assert table.B > 64 and all(len({t[j] for t in a + b}) == 256 for j in range(8))
+    top_bits = table.B - 64 * ((table.B - 1) // 64)
+    u = [t for t, _, _ in jc.sorted_union(a, b)]
+    kinds = set()
+    for x, y in zip(u, u[1:]):
+        if x[:8] == y[:8]:
+            assert jc.key_of(x, table) >> (table.B - top_bits) == jc.key_of(y, table) >> (table.B - top_bits)   # equal top key word
+            differ = [p for p in range(length) if x[p] != y[p]]
+            kinds.add("same" if not differ else {length - 1: "last", length - 9: "ninth_last"}[differ[0]])
+            assert len(differ) <= 1
+    assert kinds == {"same", "last", "ninth_last"}
+    a, b = jc.head_lengths_differ()
+    u = [t for t, _, _ in jc.sorted_union(a, b)]
+    assert any(len(x) + 1 == len(y) and y[:len(x)] == x for x, y in zip(u, u[1:]))
+
+
+def test_join_stability_lists():
+    assert {1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 8191, 8192, 8193, 12289} == set(jc.STABLE_NS)
+    assert {jc.SORT_TILE - 1, jc.SORT_TILE, jc.SORT_TILE + 1, 3 * jc.SORT_TILE + 1} <= set(jc.STABLE_NS)
+    for n in jc.STABLE_NS:
+        for kind in jc.STABLE_KINDS:
+            tags = jc.stable_tags(n, kind)
+            assert len(tags) == n
+            table = jc.code_table(tags)
+            assert table.B == jc.stable_claims(n, kind).get("B", table.B), (n, kind)
+            if n >= 512:
+                assert len(set(tags)) < n                        # equal tags: the permutation is a matter of stability
+            if kind == "bytes_256" and n >= 256:
+                counts = np.bincount([t[0] for t in tags], minlength=256)
+                assert counts.min() == n // 256 and counts.max() <= n // 256 + 1
+            assert sorted(range(n), key=lambda i: jc.key_of(tags[i], table)) == jc.reference_sort(tags)
+
+
+@pytest.mark.parametrize("style", jc.RUN_STYLES)
+def test_join_runs_lie_where_they_say(style):
+    starts, b_starts = set(), set()
+    for which, (s, runs) in enumerate(jc.RUN_LAYOUTS):
+        a, b, claims = jc.run_case(which, style)
+        u = jc.sorted_union(a, b)
+        hot, at = claims["hot"], claims["run_start"]
+        assert u[at][0] == hot and (at == 0 or u[at - 1][0] != hot), (which, style)
+        assert len(set(t for t, _, _ in u[:at])) == at                               # singletons below
+        if claims["b_start"] is not None:
+            p = claims["b_start"]
+            assert u[p][:2] == (hot, 1) and (p == at or u[p - 1][:2] == (hot, 0)), (which, style)
+            b_starts.add(p)
+        starts.add(at)
+        assert (a.count(hot), b.count(hot)) == runs[0]
+        W = (jc.code_table(a + b).B + 63) // 64
+        assert (W == 1) if style == "short" else (W >= 2)
+    T = jc.JOIN_TILE
+    assert {T - 1, T, T + 1, 7, 8, 9, 511, 512, 513} <= starts and {T, 2 * T, 8, 512} <= b_starts
+    whole = [(s + ra, s + ra + rb) for s, runs in jc.RUN_LAYOUTS for ra, rb in runs[:1] if rb >= T]
+    assert any(lo % T == 0 and hi - lo >= T for lo, hi in whole) and any(lo % T == 0 and hi - lo >= 2 * T for lo, hi in whole)
+    firsts = [runs[0] for _, runs in jc.RUN_LAYOUTS]
+    assert any(ra > rb > 0 for ra, rb in firsts) and any(rb > ra > 0 for ra, rb in firsts)
+    pairs_of_runs = [(x, y) for _, runs in jc.RUN_LAYOUTS for x, y in zip(runs, runs[1:])]
+    assert any(x[1] == 0 and y[0] == 0 for x, y in pairs_of_runs) and any(x[0] == 0 and y[1] == 0 for x, y in pairs_of_runs)
+
+
+def test_join_pair_patterns():
+    T = jc.PAIR_TILE
+    assert {T - 1, T, T + 1, 2 * T + 1} == set(jc.PAIR_NS)
+    for n_a in jc.PAIR_NS:
+        for pattern in jc.PAIR_PATTERNS:
+            a, b, claims = jc.pair_case(n_a, pattern)
+            j = jc.reference_join(a, b)
+            assert [k for k, m in enumerate(j["match_a"]) if m != jc.NONE] == claims["matched"], (n_a, pattern)
+            assert len(a) == n_a and len(j["pairs"]) == len(claims["matched"]) and j["match_b"].count(jc.NONE) > 100
+        assert jc.pair_matched(n_a, "last_of_tile")[0] == min(T, n_a) - 1
+        assert jc.pair_matched(n_a, "first_of_next_tile")[0] == (T if n_a > T else 0)
+
+
+NUL_FREE_JOINS = [c for c in JOIN_CASES if not any(0 in t for t in c[1] + c[2])]
+
+
+@pytest.mark.parametrize("name,a,b,claims", NUL_FREE_JOINS, ids=[c[0] for c in NUL_FREE_JOINS])
+def test_join_reference_is_the_oracles_join(oracle, name, a, b, claims):
+    j = jc.reference_join(a, b)
+    i1, i2, unpaired = oracle.join_tags(*jc.tag_arrays(a), *jc.tag_arrays(b), tail_rule=False)
+    assert list(zip(i1.tolist(), i2.tolist())) == j["pairs"]
+    assert unpaired == len(a) + len(b) - 2 * len(j["pairs"])
+    assert sorted(j["perm_a"]) == list(range(len(a))) and sorted(j["perm_b"]) == list(range(len(b)))
+    assert all(j["match_b"][y] == x for x, y in enumerate(j["match_a"]) if y != jc.NONE)
+
+
+def test_join_cases_with_nul_bytes_are_the_head_cases():
+    assert len(NUL_FREE_JOINS) == len(JOIN_CASES) - len(jc.HEAD_LENGTHS) - 1 == 2 * len(jc.RUN_LAYOUTS) + len(jc.PAIR_NS) * len(jc.PAIR_PATTERNS)
+
+
+def test_join_limit_rows_are_in_order_and_hold_every_value():
+    rows = jc.all_values_everywhere(4096)
+    assert len(rows) == 256 and {len(r) for r in rows} == {4096} and rows == sorted(rows)
+    cols = np.frombuffer(b"".join(rows), np.uint8).reshape(256, 4096)
+    assert (np.sort(cols, axis=0) == np.arange(256, dtype=np.uint8)[:, None]).all()     # 256 codes at each position: 8 bits
+    assert 8 * 4096 == 32768 and jc.code_table(jc.all_values_everywhere(16)).B == 128
+
+
+def test_join_extract_lines():
+    lines = jc.extract_lines()
+    text, starts, lens, exp_off, exp_len = jc.extract_text()
+    assert len(starts) == 8 * len(lines) and len(text) < 8 << 20
+    assert {(n, s % 8) for n, s in zip(lens, starts)} >= {(n, r) for n in range(1, 27) for r in range(8)}
+    assert all(text[s + n - 1] == 10 and text[s:s + n].count(b"\n") == 1 for s, n in zip(starts, lens))
+    for n in range(2, 27):
+        mine = [l for l in lines if len(l) == n]
+        inner = set(range(1, n - 1))
+        assert {l.find(b".") for l in mine} == inner | {-1} and {l.find(b" ") for l in mine} == inner | {-1}
+        assert any(b"." not in l and b" " not in l for l in mine)                    # near-misses only
+        for hit in b". ":
+            around = {(l[l.index(hit) - 1], l[l.index(hit) + 1]) for l in mine if hit in l and 1 < l.index(hit) < n - 2}
+            assert n < 6 or ({x for x, _ in around} >= set(jc.NEAR) and {y for _, y in around} >= set(jc.NEAR))
+        if n > 2:
+            assert any(l[-2:] == b".\n" for l in mine)
+    assert all(set(l[1:-1]) <= set(jc.NEAR + b". ") for l in lines)
+    for n in (64, 65, 66):
+        assert {l.find(b".") for l in lines if len(l) == n} == set(range(56, n - 1))
+    assert {64} <= {l.find(b".") for l in lines if len(l) == 66}
+    assert any(n == 0 for n in exp_len) and any(o + n == m for o, n, m in zip(exp_off, exp_len, lens))
