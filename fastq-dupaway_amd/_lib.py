@@ -76,7 +76,18 @@ class WeightsInfo(C.Structure):                              # fqd_weights_info
     _fields_ = [("over_record", C.c_uint64), ("over_sum", C.c_uint64)]
 
 
+class PlacesInfo(C.Structure):                               # fqd_places_info
+    _fields_ = [("bad_record", C.c_uint64), ("bad_reason", C.c_uint32), ("reserved", C.c_uint32), ("other_surface", C.c_uint64)]
+
+
+class OpticalInfo(C.Structure):                              # fqd_optical_info
+    _fields_ = [("clusters_in", C.c_uint64), ("clusters_out", C.c_uint64), ("split", C.c_uint64), ("largest", C.c_uint32), ("sweeps", C.c_uint32),
+                ("max_cluster", C.c_uint32), ("over_limit_members", C.c_uint32), ("over_limit_first", C.c_uint64), ("stage_ms", C.c_float * 4)]
+
+
 UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
+PLACE_OK, PLACE_FEW_FIELDS, PLACE_EMPTY_FIELD, PLACE_NOT_DIGIT, PLACE_TOO_LONG, PLACE_BAD_END = range(6)
+PLACE_SAME_SURFACE = 0x80000000
 UMI_OK, UMI_NO_SEPARATOR, UMI_EMPTY, UMI_TOO_LONG, UMI_BAD_BYTE, UMI_NO_BASE, UMI_SHAPE_DIFFERS = range(7)
 
 
@@ -179,6 +190,8 @@ def load_library():
     L.fqd_umi_reads.argtypes = [vp, vp, vp, vp, C.POINTER(UmiInfo), C.POINTER(ReadsDesc), u64, vp, u64, vp, vp]
     L.fqd_umi_merge.argtypes = [vp, vp, vp, vp, C.POINTER(UmiInfo), vp, vp, vp, u64, u32, vp, C.POINTER(UmiMergeInfo)]
     L.fqd_owners_to_keep.argtypes = [vp, vp, u64, vp]
+    L.fqd_read_places.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(PlacesInfo)]
+    L.fqd_optical_split.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, vp, C.POINTER(OpticalInfo)]
     L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
     L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_copy_labelled.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]

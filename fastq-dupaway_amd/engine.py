@@ -364,6 +364,28 @@ class Engine:
         """keep[i] = (owner[i] == i)."""
         self._check(self._L.fqd_owners_to_keep(self._h, self._p(owner), n, self._p(keep)))
 
+    # -- FQD_FAST_OPTICAL (csrc/fqd_optical.hip) ------------------------------------------------------------
+    def read_places(self, text, id_start, id_len, n: int, tile, x, y, surface, info=True):
+        """Per record (device memory, n uint32 each): tile, x and y off the first word of its ID line
+        (instrument:run:flowcell:lane:tile:x:y[:UMI]) and surface = the length of fields 1 .. 4 with their colons, with
+        _lib.PLACE_SAME_SURFACE set where those bytes are record 0's.  Returns the call's fqd_places_info (_lib.PlacesInfo):
+        the lowest refused record with its reason, and the records on another surface than record 0.  info=None hands the
+        library a null pointer, which it refuses."""
+        got = _lib.PlacesInfo() if info else None
+        self._check(self._L.fqd_read_places(self._h, self._p(text), self._p(id_start), self._p(id_len), n, self._p(tile), self._p(x), self._p(y),
+                                            self._p(surface), C.byref(got) if info else None))
+        return got
+
+    def optical_split(self, perm, head, text, id_start, tile, x, y, surface, n: int, distance: int, owner_out, out=True):
+        """owner_out[i] (n uint32, device) = the first record of record i's optical group: the members of its cluster in
+        (perm, head) (group_owners') that hang together through pairs on one surface and tile within `distance` pixels in x
+        and in y.  tile .. surface: what read_places wrote.  Returns the call's fqd_optical_info (_lib.OpticalInfo); out=None
+        hands the library a null pointer, which it refuses."""
+        got = _lib.OpticalInfo() if out else None
+        self._check(self._L.fqd_optical_split(self._h, self._p(perm), self._p(head), self._p(text), self._p(id_start), self._p(tile), self._p(x),
+                                              self._p(y), self._p(surface), n, distance, self._p(owner_out), C.byref(got) if out else None))
+        return got
+
     # -- FQD_FAST_SIZEOUT / FQD_FAST_LEVELS (csrc/fqd_size.hip) --------------------------------------------
     def cluster_sizes(self, perm, head, n: int, size, levels: bool = True):
         """size[perm[k]] (n uint32, device) = the length of the run of (perm, head) that starts at place k where head[k], 0 at

@@ -38,6 +38,16 @@ uint32_t size_bound(const char* name, uint32_t unset)
     return uint32_t(x);
 }
 
+// FQD_FAST_OPTICAL: size_bound's values, and 0 (like unset) for off.
+uint32_t pixel_distance(const char* name)
+{
+    const char* v = std::getenv(name);
+    if (!v) return 0;
+    bool zero = *v != 0;
+    for (const char* p = v; *p && zero; ++p) zero = *p == '0' && p - v < 10;
+    return zero ? 0 : size_bound(name, 0);
+}
+
 } // namespace
 
 FastModes FastModes::from_env()
@@ -57,6 +67,7 @@ FastModes FastModes::from_env()
     m.size_out = is_on("FQD_FAST_SIZEOUT");
     m.levels = is_on("FQD_FAST_LEVELS");
     m.size_in = is_on("FQD_FAST_SIZEIN");
+    m.optical = pixel_distance("FQD_FAST_OPTICAL");
     return m;
 }
 
@@ -65,6 +76,7 @@ std::string FastModes::names() const
     // (min_size 1 and max_size 0 are the two bounds that take nothing out: not named)
     const std::pair<bool, std::string> all[] = {
         {keep_best, "FQD_FAST_KEEP=best"}, {clusters, "FQD_FAST_CLUSTERS=1"}, {both_strands, "FQD_FAST_STRAND=both"}, {umi != 0, umi_name()}, {umi_mismatch != 0, mismatch_name()},
+        {optical != 0, optical_name()},
         {size_out, "FQD_FAST_SIZEOUT=1"}, {levels, "FQD_FAST_LEVELS=1"}, {sort_by_size, "FQD_FAST_SORT=size"}, {size_in, "FQD_FAST_SIZEIN=1"},
         {min_size > 1, "FQD_FAST_MINSIZE=" + std::to_string(min_size)}, {max_size != 0, "FQD_FAST_MAXSIZE=" + std::to_string(max_size)}};
     std::string s;
@@ -112,6 +124,9 @@ std::string FastModes::out_of_memory_note() const
     if (umi_mismatch)
         s += "; FQD_FAST_UMI_MISMATCH takes 12 bytes a record more (the owners by sequence, the exact counts, the merged owners) "
              "and, while it merges, 4 bytes a record and up to 66 bytes an exact cluster";
+    if (optical)
+        s += "; FQD_FAST_OPTICAL takes 16 bytes a record for the places (tile, x, y, surface) and 4 for the split owners and, while it splits, "
+             "up to 17 bytes a record of scratch (the scratch of the grouping serves where it is as large)";
     return s;
 }
 
@@ -127,6 +142,18 @@ std::string umi_reason(uint32_t reason, int sep)
     case FQD_UMI_SHAPE_DIFFERS: return "the shape of its UMI (its length and the places of '+', '-', '_') differs from record 0's: UMIs of varying length are not supported";
     }
     return "its UMI was refused";
+}
+
+std::string optical_reason(uint32_t reason)
+{
+    switch (reason) {
+    case FQD_PLACE_FEW_FIELDS: return "the first word of its ID line has fewer than 7 fields between ':' (instrument:run:flowcell:lane:tile:x:y is expected)";
+    case FQD_PLACE_EMPTY_FIELD: return "one of the first 7 fields of its ID line's first word is empty";
+    case FQD_PLACE_NOT_DIGIT: return "its tile or x (fields 5 and 6) holds a byte that is no digit, or its y (field 7) does not begin with one";
+    case FQD_PLACE_TOO_LONG: return "its tile, x or y has more than 9 digits";
+    case FQD_PLACE_BAD_END: return "the digits of its y (field 7) are followed by something other than ':', '_', '#', '/' or the end of the ID line's first word";
+    }
+    return "its place on the flow cell was refused";
 }
 
 std::string sizein_reason(uint32_t reason)

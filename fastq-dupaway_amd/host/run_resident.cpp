@@ -73,6 +73,12 @@ struct Links { Device<uint32_t> link, owner; };
 // The records grouped by owner: an order of the n records and a flag at the first place of every cluster; with
 // FQD_FAST_SIZEIN what every record stands for, while sizes are made.  Until the outputs are planned.
 struct Clusters { Device<uint32_t> perm; Device<uint8_t> head; Device<uint32_t> weight; uint64_t count = 0; };
+// FQD_FAST_OPTICAL: where on the flow cell every record was read (fqd_read_places over file 1's ID lines), until the clusters
+// are split.
+struct Places {
+    Device<uint32_t> tile, x, y, surface; uint64_t other_surface = 0;
+    void release() { tile.release(); x.release(); y.release(); surface.release(); }
+};
 
 // What lives from stage to stage, in the order it comes to be.  A stage that returns false has found the input one for the
 // streaming run (give_up) before any output exists.
@@ -84,6 +90,7 @@ struct OrderedResidentRun {
     uint64_t n = 0, dups = 0;
     Device<uint8_t> keep;
     uint64_t merged_clusters = 0;                                // FQD_FAST_UMI_MISMATCH: the clusters the merge leaves
+    Places places; uint64_t optical_more = 0;                    // FQD_FAST_OPTICAL: the places; the clusters the split adds
     std::string cluster_text[2];                                 // FQD_FAST_CLUSTERS
     Device<uint32_t> cluster_size; fqd_size_levels levels{};     // FQD_FAST_SIZEOUT / _LEVELS / _SORT / _MINSIZE / _MAXSIZE
     uint64_t dropped_clusters = 0, dropped_records = 0;          // FQD_FAST_MINSIZE / _MAXSIZE
@@ -135,7 +142,8 @@ struct OrderedResidentRun {
     // Stage 3, between the record scan and the submit loop.  FQD_FAST_STRAND=both: one fqd_canonical_reads over all n records.
     // FQD_FAST_UMI behind it: fqd_umi_find over file 1's ID lines, then fqd_umi_reads, which packs `UMI bases ‖ sequence` of
     // (the canonical) mate 1 for the submit loop's segment 0.  FQD_FAST_SIZEIN: fqd_size_annotations reads every record's weight
-    // off file 1's ID lines and holds file 2 against them.  A record that any of them refuses ends the run.
+    // off file 1's ID lines and holds file 2 against them.  FQD_FAST_OPTICAL: fqd_read_places reads every record's place off
+    // file 1's ID lines.  A record that any of them refuses ends the run.
     void rewrite_keys(KeyedReads& k, Clusters& clusters)
     {
         // no more than a file's sequence bytes — a FASTQ record is its sequence twice (bases, qualities) and at least six
@@ -188,6 +196,17 @@ struct OrderedResidentRun {
                 if (s == 0) info = found;
             }
             if (StageClock::on()) std::cerr << "fast: size annotations, " << info.annotated << " of " << n << " records annotated, total weight " << info.total_weight << "\n";
+        }
+        if (fast.optical) {
+            // the places, before anything else is spent on an input whose names hold none
+            StageClock::Scope t("fast: optical duplicates, places on the GPU");
+            places.tile.reserve(n); places.x.reserve(n); places.y.reserve(n); places.surface.reserve(n);
+            fqd_places_info found{};
+            engine_ok<DeviceError>(e, fqd_read_places(e, reinterpret_cast<const uint8_t*>(dev[0].text.p), dev[0].start.p, dev[0].id_len.p, n, places.tile.p, places.x.p,
+                                                      places.y.p, places.surface.p, &found));
+            if (found.bad_record != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal(fast.optical_name() + ": record " + std::to_string(found.bad_record) + " (counted from 0) of " + in[0] + ": " + optical_reason(found.bad_reason));
+            places.other_surface = found.other_surface;
         }
     }
 
@@ -268,7 +287,38 @@ struct OrderedResidentRun {
             if (!fast.umi_mismatch) engine_ok<DeviceError>(e, fqd_owners(e, keep.p, links.link.p, n, links.owner.p));
             engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
         }
+        if (fast.optical) { split_optical(links, clusters); dups = n - clusters.count; }
         if (clusters.count + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
+    }
+
+    // FQD_FAST_OPTICAL, behind the grouping (and the merge, where that runs): fqd_optical_split makes of every cluster its
+    // optical groups, each owned by its first member; the split owners are THE owners from here on, fqd_owners_to_keep makes
+    // the flags of them and fqd_group_owners groups the records once more.  The places leave with this stage.
+    void split_optical(Links& links, Clusters& clusters)
+    {
+        Device<uint32_t> split_owner;
+        split_owner.reserve(n);
+        fqd_optical_info split{};
+        {
+            StageClock::Scope t("fast: optical duplicates, clusters split on the GPU");
+            engine_ok<DeviceError>(e, fqd_optical_split(e, clusters.perm.p, clusters.head.p, reinterpret_cast<const uint8_t*>(dev[0].text.p), dev[0].start.p, places.tile.p,
+                                                        places.x.p, places.y.p, places.surface.p, n, fast.optical, split_owner.p, &split));
+            if (split.over_limit_first != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal(fast.optical_name() + ": the cluster of record " + std::to_string(split.over_limit_first) + " (counted from 0) of " + in[0] + " holds " +
+                                      std::to_string(split.over_limit_members) + " identical reads, a cluster of at most " + std::to_string(split.max_cluster) +
+                                      " is split (untrimmed poly-G and the like: trim the reads first)");
+            if (split.clusters_in != clusters.count) throw DeviceError("GPU engine: internal error (the split and the grouping count different clusters)");
+            links.owner.swap(split_owner);                           // (the owners by key leave with this stage)
+            engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
+            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
+        }
+        if (clusters.count != split.clusters_out) throw DeviceError("GPU engine: internal error (the split and the second grouping count different clusters)");
+        optical_more = split.clusters_out - split.clusters_in;
+        if (StageClock::on())
+            std::cerr << "fast: optical duplicates within " << fast.optical << " pixels, " << split.split << " of " << split.clusters_in << " clusters split, " << optical_more
+                      << " more written, largest cluster " << split.largest << ", " << split.sweeps << " sweeps, " << places.other_surface
+                      << " records on another surface than record 0\n";
+        places.release();
     }
 
     // fqd_cluster_sizes: the member count of every cluster at the record that is written, 4 bytes a record, and the level
@@ -362,7 +412,7 @@ struct OrderedResidentRun {
 
 } // namespace
 
-// Everything about the eleven switches that their values and the command line decide, before any GPU call.
+// Everything about the twelve switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     fast_ = FastModes::from_env();
@@ -431,7 +481,10 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     StageClock::report();
     summary_.total = run.n; summary_.duplicates = run.dups; summary_.unmatched = 0;
     if (verbose_) print_summary(S, summary_.total, summary_.duplicates);
-    // FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE: what `-v` says behind its first line
+    // FQD_FAST_OPTICAL: what `-v` says behind its first line, which counts the optical duplicates only
+    if (verbose_ && fast_.optical)
+        std::cout << run.optical_more << (S == 1 ? " reads" : " read pairs") << " that repeat an earlier sequence were written: not optical duplicates (" << fast_.optical_name() << ").\n";
+    // FQD_FAST_MINSIZE / FQD_FAST_MAXSIZE: what `-v` says behind these
     if (verbose_ && fast_.size_filter())
         std::cout << run.dropped_clusters << " clusters holding " << run.dropped_records << (S == 1 ? " reads" : " read pairs") << " were not written (FQD_FAST_MINSIZE=" << fast_.min_size
                   << ", FQD_FAST_MAXSIZE=" << (fast_.max_size ? std::to_string(fast_.max_size) : std::string("none")) << ").\n";

@@ -850,6 +850,74 @@ int  fqd_umi_merge(fqd_engine* e, const uint8_t* text, const uint64_t* id_start,
  * Only launches. */
 int  fqd_owners_to_keep(fqd_engine* e, const uint32_t* owner, uint64_t n, uint8_t* keep);
 
+/* ---- FQD_FAST_OPTICAL=D: only optical duplicates are duplicates — copies of a read that lie within D pixels of each other on
+ * one tile of the flow cell (added within ABI version 5: purely additive; no existing entry launches anything new).  Rule and
+ * proofs: csrc/fqd_optical_core.hpp.  W is the first word of an ID line as above, split at ':' into fields
+ * (instrument:run:flowcell:lane:tile:x:y[:UMI]).  The surface of a record is the bytes of fields 1 .. 4 with the colons between
+ * them; tile and x are fields 5 and 6, 1 .. 9 decimal digits each; y is the leading 1 .. 9 digits of field 7, followed by the
+ * field's end or one of ':' '_' '#' '/'.  Two records are neighbours when their surfaces are bytewise identical, their tiles
+ * equal and |xa - xb| <= D and |ya - yb| <= D; an optical group is a connected component of that relation among the records of
+ * one cluster, owned by its first member in input order.
+ *
+ * fqd_read_places: device memory only (info: host, not NULL), all arrays per record r < n.  Line r is the id_len[r] bytes at
+ * text + id_start[r].  tile, x, y (n uint32 each) as above; surface[r] (n uint32) = the surface's length in bytes, with
+ * FQD_PLACE_SAME_SURFACE set where the surface is record 0's (almost every run has one surface, and the split compares the
+ * bytes only of two records that both lack the bit).  *info: bad_record = the LOWEST record that is refused
+ * (FQD_UMI_NO_RECORD: none) and bad_reason why — the first of FQD_PLACE_FEW_FIELDS, FQD_PLACE_EMPTY_FIELD, then of tile's, x's
+ * and y's own reason in that order; other_surface = the records, of those not refused, whose surface is not record 0's.  A
+ * refused record makes the call return FQD_OK with info set; the arrays' contents are then unspecified.  n <= 2^32-2.  Sixteen
+ * lanes a record, one launch, no load outside an ID line; returns after the stream has drained (once).
+ *
+ * fqd_optical_split: device memory only (out: host, not NULL).  (perm, head) = fqd_group_owners' over the current owners: the
+ * members of a cluster in input order; tile, x, y, surface = fqd_read_places' over the same n records, text and id_start its
+ * inputs (the surface of record r is read at text + id_start[r] + 1).  distance = D, 1 .. 2^31-1.  owner_out[i] (n uint32) =
+ * the first record, in input order, of record i's optical group; fqd_group_owners and fqd_owners_to_keep take it.  owner_out
+ * must not overlap an input (FQD_ERR_ARG).  *out: clusters_in = the clusters of (perm, head); clusters_out = the optical
+ * groups; split = the clusters that fell apart into more than one; largest = the members of the largest cluster; sweeps = the
+ * most label sweeps any cluster took (a sweep = a min step that changed a label, and the pointer jump behind it);
+ * max_cluster = FQD_OPTICAL_MAX_CLUSTER.  A cluster of more members than that is refused: over_limit_first = the lowest first
+ * record of such a cluster (FQD_UMI_NO_RECORD: there is none), over_limit_members = that cluster's members; the call returns
+ * FQD_OK, owner_out is NOT written, clusters_out, split and sweeps are 0.  head[0] == 0, or an order that names a record outside
+ * 0 .. n-1, is FQD_ERR_ARG (counted on the device, nothing written).  n < 2^31.  Clusters go by size: one member — a store; up
+ * to 8 — eight lanes; up to 64 — a wave; up to 2048 — a workgroup, places and labels in LDS; beyond — a thread a member over
+ * many workgroups, two launches a sweep, the labels in scratch.  Scratch during the call: 4 bytes a cluster, about 5 bytes a
+ * record for the lists and, for inputs of more than 2048 records, 8 bytes a record for the large tier's labels.  Two results
+ * come back in between (the clusters, the lists' lengths) and one after every sweep of the large tier; returns after the
+ * stream has drained.  stage_ms is a diagnostic (tools/optical_probe.py): the wall time of the three parts the call's own
+ * waits cut it into, launches and waits included. */
+#define FQD_OPTICAL_MAX_CLUSTER 65536u
+#define FQD_PLACE_SAME_SURFACE 0x80000000u
+enum fqd_place_reason {
+    FQD_PLACE_OK = 0,
+    FQD_PLACE_FEW_FIELDS = 1,    /* W has fewer than seven fields */
+    FQD_PLACE_EMPTY_FIELD = 2,   /* one of the first seven fields is empty */
+    FQD_PLACE_NOT_DIGIT = 3,     /* tile or x holds a byte that is no digit, or y does not begin with one */
+    FQD_PLACE_TOO_LONG = 4,      /* tile or x has more than nine digits, or y begins with more than nine */
+    FQD_PLACE_BAD_END = 5        /* y's digits are followed by a byte other than ':' '_' '#' '/' */
+};
+typedef struct fqd_places_info {
+    uint64_t bad_record;
+    uint32_t bad_reason;        /* enum fqd_place_reason */
+    uint32_t reserved;
+    uint64_t other_surface;
+} fqd_places_info;
+typedef struct fqd_optical_info {
+    uint64_t clusters_in;
+    uint64_t clusters_out;
+    uint64_t split;
+    uint32_t largest;
+    uint32_t sweeps;
+    uint32_t max_cluster;
+    uint32_t over_limit_members;
+    uint64_t over_limit_first;
+    float    stage_ms[4];       /* host wall time between the call's own synchronisations: heads + classes, the tiers up to a workgroup, the large tier; 0 */
+} fqd_optical_info;
+int  fqd_read_places(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, const uint32_t* id_len, uint64_t n, uint32_t* tile, uint32_t* x,
+                     uint32_t* y, uint32_t* surface, fqd_places_info* info);
+int  fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head, const uint8_t* text, const uint64_t* id_start, const uint32_t* tile,
+                       const uint32_t* x, const uint32_t* y, const uint32_t* surface, uint64_t n, uint32_t distance, uint32_t* owner_out,
+                       fqd_optical_info* out);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
