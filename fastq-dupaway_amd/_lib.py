@@ -85,6 +85,13 @@ class OpticalInfo(C.Structure):                              # fqd_optical_info
                 ("max_cluster", C.c_uint32), ("over_limit_members", C.c_uint32), ("over_limit_first", C.c_uint64), ("stage_ms", C.c_float * 4)]
 
 
+class NearInfo(C.Structure):                                 # fqd_near_info
+    _fields_ = [(name, C.c_uint64) for name in ("nodes", "merged", "entries", "groups", "pairs", "edges", "largest_group", "sweeps", "over_limit_first",
+                                                "over_limit_nodes")] + [("max_group", C.c_uint32), ("reserved", C.c_uint32), ("stage_ms", C.c_float * 3)]
+
+
+NEAR_MAX_GROUP = 4096
+NEAR_WEAK_SEEDS = 1
 UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
 PLACE_OK, PLACE_FEW_FIELDS, PLACE_EMPTY_FIELD, PLACE_NOT_DIGIT, PLACE_TOO_LONG, PLACE_BAD_END = range(6)
 PLACE_SAME_SURFACE = 0x80000000
@@ -192,6 +199,7 @@ def load_library():
     L.fqd_owners_to_keep.argtypes = [vp, vp, u64, vp]
     L.fqd_read_places.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(PlacesInfo)]
     L.fqd_optical_split.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, vp, C.POINTER(OpticalInfo)]
+    L.fqd_near_merge.argtypes = [vp, C.POINTER(ReadsDesc), vp, u64, u32, u32, vp, C.POINTER(NearInfo)]
     L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
     L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_copy_labelled.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]

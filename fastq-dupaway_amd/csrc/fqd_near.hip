@@ -1,0 +1,443 @@
+// fqd_near.hip — FQD_FAST_HAMMING=D of the `--fast` mode (same library as fqd_engine.hip): the engine's exact clusters that
+// differ in at most D substituted bases a mate are merged, through a seed join instead of all pairs.  Rule and proofs:
+// fqd_near_core.hpp.  Nothing in here is called unless the switch is set.
+//
+//   seeds    count_nodes_kernel counts the nodes (owner[i] == i) and holds the owners against their own rule; the count comes
+//            back to size the rest.  seeds_kernel, a lane a record: a node takes D + 1 neighbouring places of the entry list —
+//            a wave adds to the list's end with one atomic — and writes (seed key, node) for every segment of its mate 1,
+//            sixteen bytes a load (fqdnear::seed_key).  In which order the nodes stand in the list depends on scheduling;
+//            nothing behind the sort does.
+//   sort     fqd_internal_radix_sort over the 64 key bits.  mark_kernel, a lane an entry: the first entry of a group finds
+//            the group's end (a gallop and a binary search over the sorted keys) and with it the size; the groups are counted
+//            and the largest is kept.  An entry with an equal key half the limit away on either side — every entry of a
+//            group beyond the limit has one — finds both ends, and where the group is beyond the limit offers
+//            (its node << 32 | size) to one 64-bit atomicMin: the lowest first record of such a group, and that group's size.
+//            An entry that has a later entry in its group — few have — goes on the work list, a wave adding to it with one
+//            atomic; the list lies in the sort's other key array, which nobody reads any more.
+//   verify   verify_kernel, EIGHT LANES AN ENTRY OF THE WORK LIST: the later entries of its group are its candidates, one
+//            after another.  An entry of the same node is skipped; the shapes are compared as numbers; then the lanes count the differing bytes
+//            of mate 1, sixteen bytes a lane and round (fqdnear::chunk_mismatches), sum across the eight behind every round
+//            and stop once the sum is above D; mate 2 likewise.  A pair that passes is appended to the edge list by the
+//            group's first lane.  The list has a capacity: the kernel counts every edge and stores those that fit, and where
+//            the count is above the capacity the host makes room for the count and runs the kernel once more (the count does
+//            not depend on scheduling, so the second run fits).  Every loop's condition is a wave-wide vote, so the eight
+//            lanes of a group are together at every cross-lane sum.
+//   sweeps   the labels, a word a record, in scratch; owner_out serves as the array the min step writes.  A sweep:
+//            copy labels -> next, edge_min_kernel (a lane an edge, atomicMin into next), the host asks whether an edge had two
+//            labels, jump_kernel (labels[v] = next[next[v]]).  finish_kernel: owner_out[i] = labels[owner[i]].
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstdlib>
+
+#include "fqd_internal.hpp"
+#include "fqd_near_core.hpp"
+
+namespace {
+
+using namespace fqdnear;
+
+constexpr int kBlock = 256;
+constexpr unsigned long long kNoOver = ~0ull;
+
+static_assert(64 % kLanes == 0 && kLanes == 8, "the verify kernel's groups tile a wave");
+
+struct Counters {
+    unsigned long long nodes, bad, cursor, groups, largest, work, pairs, edges, merged, over;
+    uint32_t changed, pad;
+};
+
+// One mate's reads as the kernels see them (fqd_reads).
+struct Mate {
+    const uint8_t* bases; const uint64_t* off; const uint32_t* len; uint32_t ulen, ustride;
+    __device__ __forceinline__ const uint8_t* at(uint32_t r) const { return off ? bases + off[r] : bases + uint64_t(r) * ustride; }
+    __device__ __forceinline__ uint32_t length(uint32_t r) const { return len ? len[r] : ulen; }
+};
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;                                                // (lane 0's is the wave's)
+}
+
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(v, d, 64); v = o > v ? o : v; }
+    return v;
+}
+
+__device__ __forceinline__ uint32_t group_sum(uint32_t v)
+{
+#pragma unroll
+    for (int d = int(kLanes) / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, int(kLanes));
+    return v;
+}
+
+// ---- seeds -------------------------------------------------------------------------------------------------------------------
+
+// bad: an owner above its record (that covers one outside 0 .. n-1), or one that is not its own owner.
+__global__ __launch_bounds__(kBlock)
+void count_nodes_kernel(const uint32_t* __restrict__ owner, uint64_t n, Counters* counters)
+{
+    unsigned long long nodes = 0, bad = 0;
+    for (uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kBlock) {
+        const uint32_t o = owner[i];
+        if (o > i) { ++bad; continue; }
+        nodes += o == i;
+        bad += o != i && owner[o] != o;
+    }
+    nodes = wave_sum(nodes); bad = wave_sum(bad);
+    if ((threadIdx.x & 63) == 0) {
+        if (nodes) atomicAdd(&counters->nodes, nodes);
+        if (bad) atomicAdd(&counters->bad, bad);
+    }
+}
+
+// A lane a record, no stride: every lane of a wave reaches the ballot.  room = the entries the lists hold.
+__global__ __launch_bounds__(kBlock)
+void seeds_kernel(Mate m1, Mate m2, bool paired, const uint32_t* __restrict__ owner, uint64_t n, uint32_t D, bool weak, uint64_t* __restrict__ keys,
+                  uint32_t* __restrict__ vals, uint64_t room, Counters* counters)
+{
+    const uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool node = i < n && owner[i] == uint32_t(i);
+    const unsigned long long nodes = __ballot(node);
+    if (!nodes) return;                                      // (the whole wave)
+    const int leader = __ffsll(nodes) - 1;
+    unsigned long long at = 0;
+    if (int(lane) == leader) at = atomicAdd(&counters->cursor, static_cast<unsigned long long>(__popcll(nodes)) * (D + 1u));
+    at = __shfl(at, leader, 64) + static_cast<unsigned long long>(__popcll(nodes & ((1ull << lane) - 1ull))) * (D + 1u);
+    if (!node) return;
+    const uint32_t r = uint32_t(i), len1 = m1.length(r), len2 = paired ? m2.length(r) : 0u;
+    const uint8_t* p = m1.at(r);
+    for (uint32_t j = 0; j <= D; ++j)
+        if (at + j < room) { keys[at + j] = node_seed(p, len1, len2, D, j, weak); vals[at + j] = r; }
+}
+
+// ---- groups ------------------------------------------------------------------------------------------------------------------
+
+// The first place behind e whose key is not keys[e] (N where there is none): a gallop, then a binary search.
+__device__ __forceinline__ uint64_t group_end(const uint64_t* __restrict__ keys, uint64_t N, uint64_t e)
+{
+    const uint64_t key = keys[e];
+    uint64_t lo = e, step = 1;                               // keys[lo] == key
+    while (lo + step < N && keys[lo + step] == key) { lo += step; step <<= 1; }
+    uint64_t hi = lo + step < N ? lo + step : N;             // keys[hi] != key, or hi == N
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] == key) lo = mid; else hi = mid;
+    }
+    return hi;
+}
+
+// The first place of e's group.
+__device__ __forceinline__ uint64_t group_start(const uint64_t* __restrict__ keys, uint64_t e)
+{
+    const uint64_t key = keys[e];
+    uint64_t hi = e, step = 1;                               // keys[hi] == key
+    while (hi >= step && keys[hi - step] == key) { hi -= step; step <<= 1; }
+    uint64_t lo = hi >= step ? hi - step : 0;                // keys[lo] != key, or lo == 0
+    if (keys[lo] == key) return lo;                          // (lo == 0)
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (keys[mid] == key) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+
+// A lane an entry, no stride (the wave's sums).  work: room for N places — the entries that have a later entry in their group.
+__global__ __launch_bounds__(kBlock)
+void mark_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t N, uint64_t* __restrict__ work, Counters* counters)
+{
+    const uint64_t e = blockIdx.x * uint64_t(kBlock) + threadIdx.x;
+    const bool live = e < N;
+    uint64_t key = 0;
+    if (live) key = keys[e];
+    const bool first = live && (e == 0 || keys[e - 1] != key);
+    unsigned long long size = 0;
+    if (first) size = group_end(keys, N, e) - e;
+    constexpr uint64_t half = kMaxGroup / 2;
+    if (live && ((e >= half && keys[e - half] == key) || (e + half < N && keys[e + half] == key))) {
+        const unsigned long long all = group_end(keys, N, e) - group_start(keys, e);
+        if (all > kMaxGroup) atomicMin(&counters->over, (static_cast<unsigned long long>(vals[e]) << 32) | (all > 0xFFFFFFFFull ? 0xFFFFFFFFull : all));
+    }
+    const unsigned long long groups = static_cast<unsigned long long>(__popcll(__ballot(first)));
+    const unsigned long long largest = wave_max(size);
+    const unsigned long long followed = __ballot(live && e + 1 < N && keys[e + 1] == key);
+    if (followed) {                                          // (the same for every lane)
+        const uint32_t lane = threadIdx.x & 63u;
+        const int leader = __ffsll(followed) - 1;
+        unsigned long long at = 0;
+        if (int(lane) == leader) at = atomicAdd(&counters->work, static_cast<unsigned long long>(__popcll(followed)));
+        at = __shfl(at, leader, 64) + static_cast<unsigned long long>(__popcll(followed & ((1ull << lane) - 1ull)));
+        if (((followed >> lane) & 1ull) && at < N) work[at] = e;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (groups) atomicAdd(&counters->groups, groups);
+        if (largest) atomicMax(&counters->largest, largest);
+    }
+}
+
+// ---- verify ------------------------------------------------------------------------------------------------------------------
+
+// The differing bytes of a and b (n each), counted by the group's lanes until the sum is above D; all eight lanes return the
+// sum.  on: the group has a pair to compare (the loop's condition is the wave's, see the head of the file).
+__device__ __forceinline__ uint32_t lanes_count(bool on, const uint8_t* a, const uint8_t* b, uint32_t n, uint32_t D, uint32_t gl)
+{
+    uint32_t d = 0;
+    for (uint32_t c0 = 0; __any(on && uint64_t(c0) * kChunk < n && d <= D); c0 += kLanes) {
+        const bool go = on && uint64_t(c0) * kChunk < n && d <= D;
+        d += group_sum(go ? chunk_mismatches(a, b, n, c0 + gl) : 0u);
+    }
+    return d;
+}
+
+// Eight lanes an entry of the work list (W places of entries below N), no stride.  edges: room pairs (a, b).
+__global__ __launch_bounds__(kBlock)
+void verify_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t N, const uint64_t* __restrict__ work, uint64_t W, Mate m1,
+                   Mate m2, bool paired, uint32_t D, uint2* __restrict__ edges, unsigned long long room, Counters* counters)
+{
+    const uint32_t lane = threadIdx.x & 63u, gl = lane % kLanes;
+    const uint64_t w = (blockIdx.x * uint64_t(kBlock) + threadIdx.x) / kLanes;
+    uint64_t e = 0, end = 0;
+    uint32_t a = 0, len1 = 0, len2 = 0;
+    const uint8_t *a1 = m1.bases, *a2 = m1.bases;
+    if (w < W) e = work[w];
+    if (w < W && e < N) {
+        end = group_end(keys, N, e);
+        a = vals[e]; len1 = m1.length(a); a1 = m1.at(a);
+        if (paired) { len2 = m2.length(a); a2 = m2.at(a); }
+    }
+    unsigned long long pairs = 0;
+    for (uint64_t c = e + 1; __any(c < end); ++c) {
+        bool on = c < end;
+        uint32_t b = 0;
+        const uint8_t *b1 = a1, *b2 = a2;
+        if (on) b = vals[c];
+        on = on && b != a;                                   // an entry of the same node (its own keys collided)
+        pairs += on && gl == 0u;
+        if (on) on = m1.length(b) == len1 && (!paired || m2.length(b) == len2);
+        if (on) { b1 = m1.at(b); if (paired) b2 = m2.at(b); }
+        const uint32_t d1 = lanes_count(on, a1, b1, len1, D, gl);   // (called by every lane: its loops vote)
+        on = on && d1 <= D;
+        if (paired) { const uint32_t d2 = lanes_count(on, a2, b2, len2, D, gl); on = on && d2 <= D; }
+        if (on && gl == 0u) {
+            const unsigned long long at = atomicAdd(&counters->edges, 1ull);
+            if (at < room) edges[at] = make_uint2(a, b);
+        }
+    }
+    pairs = wave_sum(pairs);
+    if (lane == 0 && pairs) atomicAdd(&counters->pairs, pairs);
+}
+
+// ---- sweeps ------------------------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kBlock)
+void start_labels_kernel(uint32_t* __restrict__ labels, uint64_t n)
+{
+    for (uint64_t v = blockIdx.x * uint64_t(kBlock) + threadIdx.x; v < n; v += uint64_t(gridDim.x) * kBlock) labels[v] = uint32_t(v);
+}
+
+// The min step; next is a copy of labels when the launch begins.  Every edge's ends are nodes below n (verify wrote them
+// from the entry list, which holds records below n).
+__global__ __launch_bounds__(kBlock)
+void edge_min_kernel(const uint2* __restrict__ edges, uint64_t m, const uint32_t* __restrict__ labels, uint32_t* __restrict__ next, uint32_t* changed)
+{
+    bool any = false;
+    for (uint64_t k = blockIdx.x * uint64_t(kBlock) + threadIdx.x; k < m; k += uint64_t(gridDim.x) * kBlock) {
+        const uint2 ed = edges[k];
+        uint32_t to, low;
+        if (!edge_min(labels, ed.x, ed.y, &to, &low)) continue;
+        atomicMin(&next[to], low);
+        any = true;
+    }
+    if (any) *changed = 1u;                                   // (every writer writes the same value)
+}
+
+__global__ __launch_bounds__(kBlock)
+void jump_kernel(const uint32_t* __restrict__ next, uint32_t* __restrict__ labels, uint64_t n)
+{
+    for (uint64_t v = blockIdx.x * uint64_t(kBlock) + threadIdx.x; v < n; v += uint64_t(gridDim.x) * kBlock) labels[v] = next[next[v]];
+}
+
+__global__ __launch_bounds__(kBlock)
+void finish_kernel(const uint32_t* __restrict__ owner, const uint32_t* __restrict__ labels, uint64_t n, uint32_t* __restrict__ owner_out, Counters* counters)
+{
+    unsigned long long merged = 0;
+    for (uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kBlock) {
+        const uint32_t o = owner[i], l = labels[o];
+        owner_out[i] = l;
+        merged += o == i && l == o;
+    }
+    merged = wave_sum(merged);
+    if ((threadIdx.x & 63) == 0 && merged) atomicAdd(&counters->merged, merged);
+}
+
+bool on_device(const void* p)
+{
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
+    return b && pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+struct Buffers { uint64_t* keys[2]; uint32_t* vals[2]; uint32_t *counts, *tot, *labels; };
+
+size_t carve(uint64_t n, uint64_t N, char* base, Buffers& b)
+{
+    Carver c{base};
+    for (int k = 0; k < 2; ++k) { b.keys[k] = c.take<uint64_t>(N); b.vals[k] = c.take<uint32_t>(N); }
+    b.counts = c.take<uint32_t>(fqd_internal_radix_counts(N)); b.tot = c.take<uint32_t>(256);
+    b.labels = c.take<uint32_t>(n);
+    return c.used + 256;
+}
+
+// Counters in front, the edges behind them.
+constexpr size_t kEdgesAt = 256;
+static_assert(sizeof(Counters) <= kEdgesAt, "the counters fit in front of the edges");
+
+// FQD_NEAR_EDGE_ROOM=K (tests): the edge list starts with room for K edges, so that a small input goes through the regrowth.
+unsigned long long first_edge_room(uint64_t N)
+{
+    if (const char* v = std::getenv("FQD_NEAR_EDGE_ROOM")) { const long long k = std::atoll(v); if (k > 0) return static_cast<unsigned long long>(k); }
+    return std::max<unsigned long long>(N, 1024);
+}
+
+} // namespace
+
+extern "C" {
+
+int fqd_near_merge(fqd_engine* e, const fqd_reads* reads, const uint32_t* owner, uint64_t n, uint32_t distance, uint32_t flags, uint32_t* owner_out,
+                   fqd_near_info* out)
+{
+    if (!e) return FQD_ERR_ARG;
+    if (out) { *out = fqd_near_info{}; out->over_limit_first = FQD_UMI_NO_RECORD; out->max_group = FQD_NEAR_MAX_GROUP; }
+    const int S = fqd_internal_segments(e);
+    bool fine = out && distance >= 1 && distance <= kMaxDistance && n < 0x80000000ull && !(flags & ~FQD_NEAR_WEAK_SEEDS) && (n == 0 || (reads && owner && owner_out));
+    for (int s = 0; fine && n && s < S; ++s)
+        fine = reads[s].bases && (reads[s].offsets == nullptr) == (reads[s].lengths == nullptr) && (reads[s].offsets || reads[s].uniform_stride >= reads[s].uniform_len);
+    if (!fine)
+        return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_near_merge: bad arguments (the info, a distance of 1 .. 3, no flag but FQD_NEAR_WEAK_SEEDS, the engine's segments as fqd_reads — offsets and lengths both or neither — the owners and room for the merged owners of at most 2^31-1 records)");
+    if (n == 0) return FQD_OK;
+    FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
+    bool device = on_device(owner) && on_device(owner_out);
+    for (int s = 0; s < S; ++s) device = device && on_device(reads[s].bases) && (!reads[s].offsets || (on_device(reads[s].offsets) && on_device(reads[s].lengths)));
+    if (!device) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_near_merge: the reads and every array are device memory");
+    const size_t words = size_t(n) * sizeof(uint32_t);
+    bool overlaps = overlap(owner_out, words, owner, words);
+    for (int s = 0; s < S; ++s)
+        overlaps = overlaps || overlap(owner_out, words, reads[s].offsets, 2 * words) || overlap(owner_out, words, reads[s].lengths, words) ||
+                   (!reads[s].offsets && overlap(owner_out, words, reads[s].bases, size_t(n - 1) * reads[s].uniform_stride + reads[s].uniform_len));
+    if (overlaps) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_near_merge: owner_out overlaps an input");
+    hipStream_t stream = fqd_internal_stream(e);
+    auto clock = std::chrono::steady_clock::now();
+    auto stage = [&](int k) {                                   // (behind a wait of the call's own: what the stage cost, seen from the host)
+        const auto now = std::chrono::steady_clock::now();
+        out->stage_ms[k] = std::chrono::duration<float, std::milli>(now - clock).count();
+        clock = now;
+    };
+    const uint32_t D = distance;
+    const bool paired = S == 2, weak = (flags & FQD_NEAR_WEAK_SEEDS) != 0;
+    const Mate m1{reads[0].bases, reads[0].offsets, reads[0].lengths, reads[0].uniform_len, reads[0].uniform_stride};
+    const Mate m2 = paired ? Mate{reads[1].bases, reads[1].offsets, reads[1].lengths, reads[1].uniform_len, reads[1].uniform_stride} : m1;
+
+    // ---- seeds ----
+    void* small = nullptr;
+    int rc = fqd_internal_scratch(e, 1, kEdgesAt, &small);
+    if (rc) return rc;
+    Counters* counters = static_cast<Counters*>(small);
+    Counters got{};
+    auto fetch = [&]() -> hipError_t {
+        hipError_t err = hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream);
+        return err != hipSuccess ? err : hipStreamSynchronize(stream);
+    };
+    FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
+    FQD_TRY(e, hipMemsetAsync(&counters->over, 0xFF, sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(count_nodes_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, owner, n, counters);
+    FQD_TRY(e, hipGetLastError());
+    FQD_TRY(e, fetch());
+    if (got.bad || got.nodes == 0 || got.nodes > n)
+        return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_near_merge: an owner lies above its record or is not its own owner (is owner that of fqd_owners over these records? nothing was written)");
+    const uint64_t nodes = got.nodes, N = nodes * (D + 1u);
+    out->nodes = nodes; out->entries = N;
+    Buffers b{};
+    void* base = nullptr;
+    if ((rc = fqd_internal_scratch(e, 0, carve(n, N, nullptr, b), &base))) return rc;
+    (void)carve(n, N, static_cast<char*>(base), b);
+    hipLaunchKernelGGL(seeds_kernel, dim3(uint32_t((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, m1, m2, paired, owner, n, D, weak, b.keys[0], b.vals[0],
+                       N, counters);
+    FQD_TRY(e, hipGetLastError());
+
+    // ---- sort, groups ----
+    int cur = 0;
+    if ((rc = fqd_internal_radix_sort(e, stream, b.keys, b.vals, b.counts, b.tot, N, 64u, &cur))) return rc;
+    const uint64_t* keys = b.keys[cur];
+    const uint32_t* vals = b.vals[cur];
+    uint64_t* work = b.keys[cur ^ 1];                         // (the sort's other key array is free from here on)
+    hipLaunchKernelGGL(mark_kernel, dim3(uint32_t((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, keys, vals, N, work, counters);
+    FQD_TRY(e, hipGetLastError());
+    FQD_TRY(e, fetch());
+    if (got.cursor != N) return fqd_internal_fail(e, FQD_ERR_HIP, "fqd_near_merge: internal error (the nodes counted and the nodes listed differ)");
+    out->groups = got.groups; out->largest_group = got.largest;
+    const uint64_t W = got.work;
+    if (W > N) return fqd_internal_fail(e, FQD_ERR_HIP, "fqd_near_merge: internal error (more entries with a successor than entries)");
+    stage(0);
+    if (got.over != kNoOver) {                                // refused: owner_out stays unspecified
+        out->over_limit_first = got.over >> 32;
+        out->over_limit_nodes = got.over & 0xFFFFFFFFull;
+        return FQD_OK;
+    }
+
+    // ---- verify ----
+    unsigned long long room = first_edge_room(N);
+    uint2* edges = nullptr;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        if ((rc = fqd_internal_scratch(e, 1, kEdgesAt + size_t(room) * sizeof(uint2), &small))) return rc;
+        counters = static_cast<Counters*>(small);               // (a larger block is a new one: the counters verify adds to start at 0 either way)
+        edges = reinterpret_cast<uint2*>(static_cast<char*>(small) + kEdgesAt);
+        FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
+        if (W)
+            hipLaunchKernelGGL(verify_kernel, dim3(uint32_t((W * kLanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, keys, vals, N,
+                               static_cast<const uint64_t*>(work), W, m1, m2, paired, D, edges, room, counters);
+        FQD_TRY(e, hipGetLastError());
+        FQD_TRY(e, fetch());
+        if (got.edges <= room) break;
+        if (attempt) return fqd_internal_fail(e, FQD_ERR_HIP, "fqd_near_merge: internal error (two runs of the verification count different edges)");
+        room = got.edges;
+    }
+    const uint64_t m = got.edges;
+    out->pairs = got.pairs; out->edges = m;
+    stage(1);
+
+    // ---- sweeps ----
+    uint32_t* next = owner_out;
+    hipLaunchKernelGGL(start_labels_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, b.labels, n);
+    uint64_t sweeps = 0;
+    for (; m && sweeps < nodes; ++sweeps) {
+        FQD_TRY(e, hipMemsetAsync(&counters->changed, 0, sizeof(uint32_t), stream));
+        FQD_TRY(e, hipMemcpyAsync(next, b.labels, words, hipMemcpyDeviceToDevice, stream));
+        hipLaunchKernelGGL(edge_min_kernel, dim3(grid_for(m, kBlock, 8192)), dim3(kBlock), 0, stream, static_cast<const uint2*>(edges), m,
+                           static_cast<const uint32_t*>(b.labels), next, &counters->changed);
+        FQD_TRY(e, hipGetLastError());
+        uint32_t changed = 0;
+        FQD_TRY(e, hipMemcpyAsync(&changed, &counters->changed, sizeof changed, hipMemcpyDeviceToHost, stream));
+        FQD_TRY(e, hipStreamSynchronize(stream));
+        if (!changed) break;
+        hipLaunchKernelGGL(jump_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(next), b.labels, n);
+    }
+    hipLaunchKernelGGL(finish_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, owner, static_cast<const uint32_t*>(b.labels), n, owner_out, counters);
+    FQD_TRY(e, hipGetLastError());
+    FQD_TRY(e, fetch());
+    out->merged = got.merged; out->sweeps = sweeps;
+    stage(2);
+    return FQD_OK;
+}
+
+} // extern "C"

@@ -386,6 +386,19 @@ class Engine:
                                               self._p(y), self._p(surface), n, distance, self._p(owner_out), C.byref(got) if out else None))
         return got
 
+    # -- FQD_FAST_HAMMING (csrc/fqd_near.hip) ----------------------------------------------------------------
+    def near_merge(self, segs: Sequence[Reads], owner, n: int, distance: int, owner_out, flags: int = 0, out=True):
+        """owner_out[i] (n uint32, device) = the first record of record i's merged cluster: the exact clusters of `owner`
+        (owners' over the same n records of segs, device memory) that hang together through pairs of equal shape whose mates
+        differ in at most `distance` bytes each.  flags: 0 or _lib.NEAR_WEAK_SEEDS.  Returns the call's fqd_near_info
+        (_lib.NearInfo); out=None hands the library a null pointer, which it refuses."""
+        if segs is not None and len(segs) != self.segments:
+            raise ValueError(f"engine has {self.segments} mate(s) per record, got {len(segs)}")
+        got = _lib.NearInfo() if out else None
+        self._check(self._L.fqd_near_merge(self._h, self._desc(segs) if segs is not None else None, self._p(owner), n, distance, flags, self._p(owner_out),
+                                           C.byref(got) if out else None))
+        return got
+
     # -- FQD_FAST_SIZEOUT / FQD_FAST_LEVELS (csrc/fqd_size.hip) --------------------------------------------
     def cluster_sizes(self, perm, head, n: int, size, levels: bool = True):
         """size[perm[k]] (n uint32, device) = the length of the run of (perm, head) that starts at place k where head[k], 0 at

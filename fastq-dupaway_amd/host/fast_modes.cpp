@@ -68,6 +68,7 @@ FastModes FastModes::from_env()
     m.levels = is_on("FQD_FAST_LEVELS");
     m.size_in = is_on("FQD_FAST_SIZEIN");
     m.optical = pixel_distance("FQD_FAST_OPTICAL");
+    m.hamming = uint32_t(choice("FQD_FAST_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
     return m;
 }
 
@@ -76,6 +77,7 @@ std::string FastModes::names() const
     // (min_size 1 and max_size 0 are the two bounds that take nothing out: not named)
     const std::pair<bool, std::string> all[] = {
         {keep_best, "FQD_FAST_KEEP=best"}, {clusters, "FQD_FAST_CLUSTERS=1"}, {both_strands, "FQD_FAST_STRAND=both"}, {umi != 0, umi_name()}, {umi_mismatch != 0, mismatch_name()},
+        {hamming != 0, hamming_name()},
         {optical != 0, optical_name()},
         {size_out, "FQD_FAST_SIZEOUT=1"}, {levels, "FQD_FAST_LEVELS=1"}, {sort_by_size, "FQD_FAST_SORT=size"}, {size_in, "FQD_FAST_SIZEIN=1"},
         {min_size > 1, "FQD_FAST_MINSIZE=" + std::to_string(min_size)}, {max_size != 0, "FQD_FAST_MAXSIZE=" + std::to_string(max_size)}};
@@ -92,6 +94,12 @@ void FastModes::check(bool unordered, size_t n_devices, Format format) const
     if (!any()) return;
     if (umi_mismatch && !umi)
         throw FastModeRefusal(mismatch_name() + " merges the UMIs that FQD_FAST_UMI finds: set FQD_FAST_UMI=colon or FQD_FAST_UMI=underscore as well");
+    if (hamming && both_strands)
+        throw FastModeRefusal(hamming_name() + " with FQD_FAST_STRAND=both: a substituted base can change which orientation of a read is the canonical one, so copies with errors "
+                              "may be keyed in opposite orientations and never be compared");
+    if (hamming && umi)
+        throw FastModeRefusal(hamming_name() + " with " + umi_name() + (umi_mismatch ? " and " + mismatch_name() : std::string()) +
+                              ": which sequences under one UMI are copies of one molecule is a rule of its own, and this switch merges by sequence alone");
     if (unordered)
         throw FastModeRefusal(names() + " with --unordered: these modes run on ordered inputs only");
     if (n_devices > 1)
@@ -124,6 +132,11 @@ std::string FastModes::out_of_memory_note() const
     if (umi_mismatch)
         s += "; FQD_FAST_UMI_MISMATCH takes 12 bytes a record more (the owners by sequence, the exact counts, the merged owners) "
              "and, while it merges, 4 bytes a record and up to 66 bytes an exact cluster";
+    if (hamming)
+        s += "; FQD_FAST_HAMMING takes 4 bytes a record for the merged owners and, while it merges, " + std::to_string(24 * (hamming + 1)) +
+             " bytes an exact cluster for the seeds and their sort (12 bytes a seed, " + std::to_string(hamming + 1) +
+             " seeds a cluster, twice over), 4 bytes a record for the labels and 8 bytes for every pair of clusters found near, with room for " +
+             std::to_string(hamming + 1) + " such pairs a cluster from the start";
     if (optical)
         s += "; FQD_FAST_OPTICAL takes 16 bytes a record for the places (tile, x, y, surface) and 4 for the split owners and, while it splits, "
              "up to 17 bytes a record of scratch (the scratch of the grouping serves where it is as large)";

@@ -90,6 +90,7 @@ struct OrderedResidentRun {
     uint64_t n = 0, dups = 0;
     Device<uint8_t> keep;
     uint64_t merged_clusters = 0;                                // FQD_FAST_UMI_MISMATCH: the clusters the merge leaves
+    uint64_t near_taken = 0;                                     // FQD_FAST_HAMMING: the exact clusters that went into another
     Places places; uint64_t optical_more = 0;                    // FQD_FAST_OPTICAL: the places; the clusters the split adds
     std::string cluster_text[2];                                 // FQD_FAST_CLUSTERS
     Device<uint32_t> cluster_size; fqd_size_levels levels{};     // FQD_FAST_SIZEOUT / _LEVELS / _SORT / _MINSIZE / _MAXSIZE
@@ -287,11 +288,42 @@ struct OrderedResidentRun {
             if (!fast.umi_mismatch) engine_ok<DeviceError>(e, fqd_owners(e, keep.p, links.link.p, n, links.owner.p));
             engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
         }
+        if (fast.hamming) { merge_near(links, clusters); dups = n - clusters.count; }
         if (fast.optical) { split_optical(links, clusters); dups = n - clusters.count; }
         if (clusters.count + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
     }
 
-    // FQD_FAST_OPTICAL, behind the grouping (and the merge, where that runs): fqd_optical_split makes of every cluster its
+    // FQD_FAST_HAMMING, behind the grouping: fqd_near_merge makes of the exact clusters — the reads as they lie in the files, the
+    // owners by key — the merged ones, each owned by its first record; the merged owners are THE owners from here on,
+    // fqd_owners_to_keep makes the flags of them and fqd_group_owners groups the records once more.
+    void merge_near(Links& links, Clusters& clusters)
+    {
+        Device<uint32_t> merged_owner;
+        merged_owner.reserve(n);
+        fqd_reads reads[2] = {};
+        for (int s = 0; s < S; ++s) reads[s] = fqd_reads{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].seq_off.p, dev[s].seq_len.p, 0, 0};
+        fqd_near_info merged{};
+        {
+            StageClock::Scope t("fast: substitutions, exact clusters merged on the GPU");
+            engine_ok<DeviceError>(e, fqd_near_merge(e, reads, links.owner.p, n, fast.hamming, 0, merged_owner.p, &merged));
+            if (merged.over_limit_first != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal(fast.hamming_name() + ": " + std::to_string(merged.over_limit_nodes) + " different sequences, the one of record " +
+                                      std::to_string(merged.over_limit_first) + " (counted from 0) of " + in[0] + " the first among them, share one of the " +
+                                      std::to_string(fast.hamming + 1) + " segments their first mate is cut into; a group of at most " + std::to_string(merged.max_group) +
+                                      " is compared (adapter dimers, amplicons: trim the reads or dereplicate them exactly first)");
+            if (merged.nodes != clusters.count) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
+            links.owner.swap(merged_owner);                          // (the owners by key leave with this stage)
+            engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
+            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
+        }
+        if (clusters.count != merged.merged) throw DeviceError("GPU engine: internal error (the merge and the second grouping count different clusters)");
+        near_taken = merged.nodes - merged.merged;
+        if (StageClock::on())
+            std::cerr << "fast: substitutions <= " << fast.hamming << ", " << near_taken << " of " << merged.nodes << " exact clusters merged into others, " << merged.pairs
+                      << " pairs compared, " << merged.edges << " near, largest seed group " << merged.largest_group << ", " << merged.sweeps << " sweeps\n";
+    }
+
+    // FQD_FAST_OPTICAL, behind the grouping (and the merges, where they run): fqd_optical_split makes of every cluster its
     // optical groups, each owned by its first member; the split owners are THE owners from here on, fqd_owners_to_keep makes
     // the flags of them and fqd_group_owners groups the records once more.  The places leave with this stage.
     void split_optical(Links& links, Clusters& clusters)
@@ -412,7 +444,7 @@ struct OrderedResidentRun {
 
 } // namespace
 
-// Everything about the twelve switches that their values and the command line decide, before any GPU call.
+// Everything about the thirteen switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     fast_ = FastModes::from_env();
@@ -481,6 +513,10 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     StageClock::report();
     summary_.total = run.n; summary_.duplicates = run.dups; summary_.unmatched = 0;
     if (verbose_) print_summary(S, summary_.total, summary_.duplicates);
+    // FQD_FAST_HAMMING: what `-v` says behind its first line, which counts every record that was not written
+    if (verbose_ && fast_.hamming)
+        std::cout << run.near_taken << (S == 1 ? " distinct sequences" : " distinct sequence pairs") << " were taken for copies of another that differs in at most " << fast_.hamming
+                  << (S == 1 ? " bases (" : " bases a mate (") << fast_.hamming_name() << ").\n";
     // FQD_FAST_OPTICAL: what `-v` says behind its first line, which counts the optical duplicates only
     if (verbose_ && fast_.optical)
         std::cout << run.optical_more << (S == 1 ? " reads" : " read pairs") << " that repeat an earlier sequence were written: not optical duplicates (" << fast_.optical_name() << ").\n";

@@ -918,6 +918,45 @@ int  fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head,
                        const uint32_t* x, const uint32_t* y, const uint32_t* surface, uint64_t n, uint32_t distance, uint32_t* owner_out,
                        fqd_optical_info* out);
 
+/* ---- FQD_FAST_HAMMING=D: exact clusters within D substituted bases of one another are one cluster (added within ABI version 5:
+ * purely additive; no existing entry launches anything new).  Rule and proofs: csrc/fqd_near_core.hpp.  A node is one exact
+ * cluster (a record with owner[i] == i) with the shape (len1) or (len1, len2).  Two nodes are near when their shapes are equal,
+ * their mates 1 differ in at most D byte positions and, for pairs, their mates 2 differ in at most D positions as well; 'N' is a
+ * letter like any other.  A merged cluster is a connected component of that relation, owned by its first record in input order.
+ *
+ * fqd_near_merge: device memory only (out: host, not NULL).  reads = the engine's segments (1 or 2), ragged or uniform, over
+ * n < 2^31 records; owner = fqd_owners' over the same records.  distance = D, 1 .. 3 (anything else: FQD_ERR_ARG); flags = 0 or
+ * FQD_NEAR_WEAK_SEEDS.  owner_out[i] (n uint32) = the first record of record i's merged cluster; fqd_group_owners and
+ * fqd_owners_to_keep take it.  owner_out must not overlap owner, a segment's offsets or lengths, or the bases of a uniform
+ * segment (FQD_ERR_ARG).  An owner above its record, or one that is not its own owner, is FQD_ERR_ARG (counted on the device,
+ * nothing written).  Mate 1 of every node is cut into D + 1 segments at floor(j * len / (D + 1)); a node's entry for segment j is
+ * (a 64-bit hash of shape, j and the segment's bytes; the node), and two near nodes share a key.  The entries are sorted by key
+ * (the radix passes of the ID join); within a group of equal keys every pair of entries of two different nodes is compared byte
+ * for byte over both mates, eight lanes a pair and sixteen bytes a lane, and a pair that is near is an edge; min-label sweeps
+ * with pointer jumping over the edge list give the components.  *out: nodes; merged = the merged clusters (nodes - merged exact
+ * clusters went into another); entries = nodes * (D + 1); groups = the seed groups; pairs = the pairs compared; edges = the
+ * pairs found near (a pair that shares several seeds is counted once for each); largest_group = the entries of the largest
+ * group; sweeps = the label sweeps (a sweep = a min step that changed a label, and the pointer jump behind it); max_group =
+ * FQD_NEAR_MAX_GROUP.  A group of more entries than that is refused: over_limit_first = the lowest first record among the nodes
+ * of such a group (FQD_UMI_NO_RECORD: there is none), over_limit_nodes = that group's entries; the call returns FQD_OK,
+ * owner_out is unspecified, and merged, pairs, edges and sweeps are 0.  FQD_NEAR_WEAK_SEEDS (tests) cuts every key to its low 4
+ * bits: nodes that agree on nothing meet in one group, a node's own entries among them, and the result is the same.  Scratch
+ * during the call: 24 bytes an entry for the sort, 4 bytes a record for the labels (owner_out holds the second label array) and
+ * 8 bytes an edge; the edge list starts with room for `entries` edges (FQD_NEAR_EDGE_ROOM=K in the environment: for K) and, where
+ * the verification counts more, is made as large as the count and the verification runs once more.  Results come back after the
+ * node count, the groups, each verification and every sweep; returns after the stream has drained.  stage_ms is a diagnostic
+ * (tools/near_probe.py): the wall time of seeds + sort + groups, of the verification and of the sweeps, launches and waits
+ * included. */
+#define FQD_NEAR_MAX_GROUP 4096u
+#define FQD_NEAR_WEAK_SEEDS 1u    /* test hook: seed keys cut to their low 4 bits */
+typedef struct fqd_near_info {
+    uint64_t nodes, merged, entries, groups, pairs, edges, largest_group, sweeps, over_limit_first, over_limit_nodes;
+    uint32_t max_group, reserved;
+    float    stage_ms[3];
+} fqd_near_info;
+int  fqd_near_merge(fqd_engine* e, const fqd_reads* reads, const uint32_t* owner, uint64_t n, uint32_t distance, uint32_t flags,
+                    uint32_t* owner_out, fqd_near_info* out);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
