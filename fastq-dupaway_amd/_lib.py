@@ -90,8 +90,13 @@ class NearInfo(C.Structure):                                 # fqd_near_info
                                                 "over_limit_nodes")] + [("max_group", C.c_uint32), ("reserved", C.c_uint32), ("stage_ms", C.c_float * 3)]
 
 
+class ConsensusInfo(C.Structure):                            # fqd_consensus_info
+    _fields_ = [(name, C.c_uint64) for name in ("clusters", "members", "bases_changed", "reads_changed", "largest")]
+
+
 NEAR_MAX_GROUP = 4096
 NEAR_WEAK_SEEDS = 1
+CONSENSUS_SMALL_TIERS = 1
 UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
 PLACE_OK, PLACE_FEW_FIELDS, PLACE_EMPTY_FIELD, PLACE_NOT_DIGIT, PLACE_TOO_LONG, PLACE_BAD_END = range(6)
 PLACE_SAME_SURFACE = 0x80000000
@@ -200,6 +205,7 @@ def load_library():
     L.fqd_read_places.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(PlacesInfo)]
     L.fqd_optical_split.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, vp, C.POINTER(OpticalInfo)]
     L.fqd_near_merge.argtypes = [vp, C.POINTER(ReadsDesc), vp, u64, u32, u32, vp, C.POINTER(NearInfo)]
+    L.fqd_consensus.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, u32, vp, C.POINTER(ConsensusInfo)]
     L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
     L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_copy_labelled.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]

@@ -399,6 +399,19 @@ class Engine:
                                            C.byref(got) if out else None))
         return got
 
+    # -- FQD_FAST_CONSENSUS (csrc/fqd_consensus.hip) -----------------------------------------------------------
+    def consensus(self, perm, head, n: int, text, start, size, seq_off, seq_len, flags: int = 0, changed=None, info=True):
+        """One file's text (device bytes, changed in place): the sequence and quality lines of the written member perm[head
+        place] of every cluster of two or more members of (perm, head) (group_owners') become the cluster's column-wise
+        consensus.  start, size, seq_off, seq_len: scan_records' arrays of the file.  flags: 0 or _lib.CONSENSUS_SMALL_TIERS.
+        changed (n bytes by record, or None): set for every written record with a changed base; reads_changed counts only
+        those it was not set for before, so a pair is counted once over the two files' calls.  Returns the call's
+        fqd_consensus_info (_lib.ConsensusInfo); info=None hands the library a null pointer, which it refuses."""
+        got = _lib.ConsensusInfo() if info else None
+        self._check(self._L.fqd_consensus(self._h, self._p(perm), self._p(head), n, self._p(text), self._p(start), self._p(size), self._p(seq_off),
+                                          self._p(seq_len), flags, self._p(changed), C.byref(got) if info else None))
+        return got
+
     # -- FQD_FAST_SIZEOUT / FQD_FAST_LEVELS (csrc/fqd_size.hip) --------------------------------------------
     def cluster_sizes(self, perm, head, n: int, size, levels: bool = True):
         """size[perm[k]] (n uint32, device) = the length of the run of (perm, head) that starts at place k where head[k], 0 at

@@ -69,6 +69,7 @@ FastModes FastModes::from_env()
     m.size_in = is_on("FQD_FAST_SIZEIN");
     m.optical = pixel_distance("FQD_FAST_OPTICAL");
     m.hamming = uint32_t(choice("FQD_FAST_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
+    m.consensus = is_on("FQD_FAST_CONSENSUS");
     return m;
 }
 
@@ -79,6 +80,7 @@ std::string FastModes::names() const
         {keep_best, "FQD_FAST_KEEP=best"}, {clusters, "FQD_FAST_CLUSTERS=1"}, {both_strands, "FQD_FAST_STRAND=both"}, {umi != 0, umi_name()}, {umi_mismatch != 0, mismatch_name()},
         {hamming != 0, hamming_name()},
         {optical != 0, optical_name()},
+        {consensus, "FQD_FAST_CONSENSUS=1"},
         {size_out, "FQD_FAST_SIZEOUT=1"}, {levels, "FQD_FAST_LEVELS=1"}, {sort_by_size, "FQD_FAST_SORT=size"}, {size_in, "FQD_FAST_SIZEIN=1"},
         {min_size > 1, "FQD_FAST_MINSIZE=" + std::to_string(min_size)}, {max_size != 0, "FQD_FAST_MAXSIZE=" + std::to_string(max_size)}};
     std::string s;
@@ -100,12 +102,20 @@ void FastModes::check(bool unordered, size_t n_devices, Format format) const
     if (hamming && umi)
         throw FastModeRefusal(hamming_name() + " with " + umi_name() + (umi_mismatch ? " and " + mismatch_name() : std::string()) +
                               ": which sequences under one UMI are copies of one molecule is a rule of its own, and this switch merges by sequence alone");
+    if (consensus && both_strands)
+        throw FastModeRefusal("FQD_FAST_CONSENSUS=1 with FQD_FAST_STRAND=both: the members of a cluster may be keyed in opposite orientations, and a column-wise vote "
+                              "needs them in one; turning reads for the vote is not done");
+    if (consensus && size_in)
+        throw FastModeRefusal("FQD_FAST_CONSENSUS=1 with FQD_FAST_SIZEIN=1: a record that stands for several reads has lost the quality lines of the reads it stands "
+                              "for, and the vote weighs every base by its quality");
     if (unordered)
         throw FastModeRefusal(names() + " with --unordered: these modes run on ordered inputs only");
     if (n_devices > 1)
         throw FastModeRefusal(names() + " runs on one GPU: FQD_DEVICES may name one device only");
     if (keep_best && format == Format::Fasta)
         throw FastModeRefusal("FQD_FAST_KEEP=best needs the quality lines of FASTQ records: --format fasta has none");
+    if (consensus && format == Format::Fasta)
+        throw FastModeRefusal("FQD_FAST_CONSENSUS=1 with --format fasta: the vote weighs every base by its quality, and FASTA records have no quality lines");
 }
 
 std::string FastModes::out_of_memory_note() const
@@ -140,6 +150,9 @@ std::string FastModes::out_of_memory_note() const
     if (optical)
         s += "; FQD_FAST_OPTICAL takes 16 bytes a record for the places (tile, x, y, surface) and 4 for the split owners and, while it splits, "
              "up to 17 bytes a record of scratch (the scratch of the grouping serves where it is as large)";
+    if (consensus)
+        s += "; FQD_FAST_CONSENSUS takes, for paired files, 1 byte a record for the pairs it changed and, while it votes, 4 bytes a cluster and up to 5 bytes a "
+             "record of scratch (the scratch of the grouping serves where it is as large)";
     return s;
 }
 

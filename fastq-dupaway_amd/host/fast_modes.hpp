@@ -1,4 +1,4 @@
-// fast_modes.hpp — the thirteen FQD_FAST_* switches of the `--fast` mode as one value: read from the environment in one place
+// fast_modes.hpp — the fourteen FQD_FAST_* switches of the `--fast` mode as one value: read from the environment in one place
 // (FastModes::from_env), checked against the command line before any GPU call (check), and asked by the run
 // (run_resident.cpp) through the predicates below.  Also the words of every refusal the switches can cause.
 // Plain C++: no HIP, nothing of run_common.hpp.
@@ -31,19 +31,20 @@ struct FastModes {
     bool size_in = false;        // FQD_FAST_SIZEIN=1: a `;size=N` an ID line already carries is the record's weight, a cluster's size the sum of its members' weights (csrc/fqd_sizein_core.hpp)
     uint32_t optical = 0;        // FQD_FAST_OPTICAL=D in 1 .. 2^31-1 (unset and 0: off): only the copies of a read within D pixels of each other on one tile of the flow cell, by the place in file 1's ID line, are duplicates (csrc/fqd_optical_core.hpp)
     uint32_t hamming = 0;        // FQD_FAST_HAMMING=D in 1 .. 3 (unset and 0: off): exact clusters of one shape whose sequences differ in at most D substituted bases a mate are one cluster, by single linkage; its first record is written (csrc/fqd_near_core.hpp)
+    bool consensus = false;      // FQD_FAST_CONSENSUS=1: the sequence and quality lines of every cluster's written member are replaced by the cluster's column-wise consensus (csrc/fqd_consensus_core.hpp)
 
-    // Reads the thirteen variables.  Throws std::runtime_error on a value that is none of the above, and FastModeRefusal for
+    // Reads the fourteen variables.  Throws std::runtime_error on a value that is none of the above, and FastModeRefusal for
     // a MAXSIZE below MINSIZE, in the order KEEP, SORT, MINSIZE, MAXSIZE, MAXSIZE below MINSIZE, STRAND, UMI, UMI_MISMATCH,
     // OPTICAL, HAMMING.
     static FastModes from_env();
     // What the values and the command line decide, before any GPU call; throws FastModeRefusal.  In this order: SIZEIN with
-    // nothing that reads sizes, UMI_MISMATCH without UMI, HAMMING with STRAND=both, HAMMING with UMI, `--unordered`, several devices, KEEP=best
-    // with FASTA.
+    // nothing that reads sizes, UMI_MISMATCH without UMI, HAMMING with STRAND=both, HAMMING with UMI, CONSENSUS with STRAND=both, CONSENSUS with SIZEIN,
+    // `--unordered`, several devices, KEEP=best with FASTA, CONSENSUS with FASTA.
     void check(bool unordered, size_t n_devices, Format format) const;
 
     bool size_filter() const { return min_size > 1 || max_size != 0; }                 // a bound that can take a cluster out
     bool sized() const { return size_out || levels || sort_by_size || size_filter(); } // something reads the cluster sizes
-    bool linked() const { return keep_best || clusters || umi_mismatch || optical || hamming || sized(); }   // the duplicates must be linked to their clusters
+    bool linked() const { return keep_best || clusters || umi_mismatch || optical || hamming || consensus || sized(); }   // the duplicates must be linked to their clusters
     bool any() const { return linked() || both_strands || umi; }                       // only the GPU-resident ordered run will do
 
     // The switches that are set, as the messages name them: "FQD_FAST_KEEP=best and FQD_FAST_UMI=colon"; "" for none.

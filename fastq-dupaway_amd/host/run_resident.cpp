@@ -92,6 +92,7 @@ struct OrderedResidentRun {
     uint64_t merged_clusters = 0;                                // FQD_FAST_UMI_MISMATCH: the clusters the merge leaves
     uint64_t near_taken = 0;                                     // FQD_FAST_HAMMING: the exact clusters that went into another
     Places places; uint64_t optical_more = 0;                    // FQD_FAST_OPTICAL: the places; the clusters the split adds
+    uint64_t consensus_bases = 0, consensus_reads = 0;           // FQD_FAST_CONSENSUS: the bases replaced, and the records (pairs) that hold them
     std::string cluster_text[2];                                 // FQD_FAST_CLUSTERS
     Device<uint32_t> cluster_size; fqd_size_levels levels{};     // FQD_FAST_SIZEOUT / _LEVELS / _SORT / _MINSIZE / _MAXSIZE
     uint64_t dropped_clusters = 0, dropped_records = 0;          // FQD_FAST_MINSIZE / _MAXSIZE
@@ -365,8 +366,29 @@ struct OrderedResidentRun {
                                   std::to_string(over.over_sum) + ": at most 2147483647");
     }
 
+    // FQD_FAST_CONSENSUS, directly behind the pick: fqd_consensus per file over the text where it lies in HBM — the written member
+    // of every cluster of two or more gets the cluster's consensus as its sequence and quality lines, of the same lengths, so
+    // that the plan, the writer, the labels and the deflate see a text like any other.  A pair is counted once through `changed`.
+    void vote_consensus(const Clusters& c)
+    {
+        StageClock::Scope t("fast: consensus of the clusters on the GPU");
+        Device<uint8_t> changed;
+        if (S == 2) { changed.reserve(n); HIP_OK(hipMemsetAsync(changed.p, 0, n, stream)); }
+        fqd_consensus_info voted{};
+        for (int s = 0; s < S; ++s) {
+            fqd_consensus_info one{};
+            engine_ok<DeviceError>(e, fqd_consensus(e, c.perm.p, c.head.p, n, reinterpret_cast<uint8_t*>(dev[s].text.p), dev[s].start.p, dev[s].size.p, dev[s].seq_off.p,
+                                                    dev[s].seq_len.p, 0, S == 2 ? changed.p : nullptr, &one));
+            voted = one;
+            consensus_bases += one.bases_changed; consensus_reads += one.reads_changed;
+        }
+        if (StageClock::on())
+            std::cerr << "fast: consensus, " << voted.clusters << " clusters of " << voted.members << " records voted, largest " << voted.largest << ", " << consensus_bases
+                      << " bases in " << consensus_reads << (S == 1 ? " reads" : " read pairs") << " replaced\n";
+    }
+
     // ... then, while perm and head exist: FQD_FAST_KEEP=best moves the keep flag of every cluster to its best member
-    // (pick_best_members, fqd_heads_to_keep); FQD_FAST_CLUSTERS takes the clusters' ID lines; the sizes are made for whatever
+    // (pick_best_members, fqd_heads_to_keep); FQD_FAST_CONSENSUS votes (vote_consensus); FQD_FAST_CLUSTERS takes the clusters' ID lines; the sizes are made for whatever
     // reads them (FastModes::sized), and the weights released behind them; fqd_size_filter clears the flags of the clusters
     // outside the bounds — behind the cluster files and the level table, which hold all clusters; fqd_size_order writes the
     // records that stay in order of decreasing cluster size.  The sizes stay for the writer with FQD_FAST_SIZEOUT only.
@@ -377,6 +399,7 @@ struct OrderedResidentRun {
             engine_ok<DeviceError>(e, fqd_heads_to_keep(e, c.perm.p, c.head.p, n, keep.p));
             if (StageClock::on()) std::cerr << "fast: best-quality pick, " << moved << " of " << c.count << " clusters changed\n";
         }
+        if (fast.consensus) vote_consensus(c);
         if (fast.clusters) {
             StageClock::Scope t("fast: ID lines of the clusters out of HBM");
             for (int s = 0; s < S; ++s) cluster_text[s] = cluster_lines(e, stream, dev[s], c.perm.p, c.head.p, n);
@@ -444,7 +467,7 @@ struct OrderedResidentRun {
 
 } // namespace
 
-// Everything about the thirteen switches that their values and the command line decide, before any GPU call.
+// Everything about the fourteen switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     fast_ = FastModes::from_env();
@@ -524,6 +547,9 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     if (verbose_ && fast_.size_filter())
         std::cout << run.dropped_clusters << " clusters holding " << run.dropped_records << (S == 1 ? " reads" : " read pairs") << " were not written (FQD_FAST_MINSIZE=" << fast_.min_size
                   << ", FQD_FAST_MAXSIZE=" << (fast_.max_size ? std::to_string(fast_.max_size) : std::string("none")) << ").\n";
+    // FQD_FAST_CONSENSUS: what `-v` says behind those
+    if (verbose_ && fast_.consensus)
+        std::cout << run.consensus_bases << " bases in " << run.consensus_reads << (S == 1 ? " reads" : " read pairs") << " were replaced by their cluster's consensus (FQD_FAST_CONSENSUS=1).\n";
     return true;
 }
 

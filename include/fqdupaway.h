@@ -957,6 +957,51 @@ typedef struct fqd_near_info {
 int  fqd_near_merge(fqd_engine* e, const fqd_reads* reads, const uint32_t* owner, uint64_t n, uint32_t distance, uint32_t flags,
                     uint32_t* owner_out, fqd_near_info* out);
 
+/* ---- FQD_FAST_CONSENSUS=1: the written member of every cluster carries the cluster's consensus (added within ABI version 5:
+ * purely additive; no existing entry launches anything new).  Rule and proofs: csrc/fqd_consensus_core.hpp.  A cluster is a run
+ * of (perm, head); its written member is perm[head place].  In every column p of a cluster of two or more members each member
+ * votes for its base with the weight of its quality byte (q - 33 for q >= 33, else 0; 0 for a base that is none of A, C, G, T,
+ * which stands for N).  The present letter with the largest sum wins — among tied letters the written member's own, else the
+ * first of A, C, G, T, N — and its quality is the winner's sum minus all other sums, clamped to 0 .. 93, written as 33 + Q.
+ *
+ * fqd_consensus: device memory only (info: host, not NULL), called once per file (mate) over that file's text and record arrays
+ * (fqd_scan_records': record r is the size[r] bytes at text + start[r], its sequence line the seq_len[r] bytes at text +
+ * seq_off[r], its quality line the seq_len[r] bytes at text + start[r] + size[r] - 1 - seq_len[r]).  (perm, head) =
+ * fqd_group_owners' over the current owners, after fqd_seq_pick's exchange where the best member is written.  The seq_len
+ * sequence bytes and seq_len quality bytes of the written member of every cluster of two or more are replaced where they
+ * lie: a sequence byte only where the winner is not the member's own letter, every quality byte.  No other byte of the text
+ * is stored to: ID lines, '+' lines, newlines, the other members and clusters of one stay as they are.  The result does not
+ * depend on how the members are dealt to lanes and workgroups, nor on the order of atomics: two calls on equal inputs give
+ * equal bytes.  *info: clusters = the clusters of two or more members; members = the records read for them; bases_changed =
+ * the columns whose winner is not the written member's own letter; reads_changed = the written records with at least one
+ * such column; largest = the members of the largest cluster (of one, too).
+ * changed (device, n bytes by record, or NULL): how a paired run counts its pairs once.  The call sets changed[r] = 1 for
+ * every written record r it counts in bases_changed, and counts in reads_changed only those whose byte was 0 before.  The host
+ * zeroes the array, hands it to the calls over file 1 and file 2, and adds the two calls' reads_changed (the pairs changed in
+ * either mate) and bases_changed.  NULL: reads_changed counts every written record of this call with a changed column.
+ * FQD_ERR_ARG, with NOTHING stored to the text: n >= 2^31; flags other than 0 or FQD_CONSENSUS_SMALL_TIERS; head[0] == 0 or an
+ * order that names a record outside 0 .. n-1; a record (any, of a cluster of one as well) whose quality line does not lie
+ * behind its sequence line inside the record (size < seq_len + 1, seq_off < start, or seq_off + seq_len not below the quality
+ * line's start: the records of a FASTA file); members of one cluster with different seq_len.  All of it is counted on the
+ * device in the first launch.
+ * Clusters go by size: up to 64 members — sixteen lanes, four columns a lane and load, the members one after the other; up to
+ * 2^20 - 1 — a workgroup whose four waves take every fourth member and combine their columns' states in LDS; from 2^20 on —
+ * up to 2048 workgroups a cluster add 64-bit sums and presence masks with atomics to 48 bytes a column of scratch, and a second
+ * launch stores the result, one such cluster after the other.  FQD_CONSENSUS_SMALL_TIERS (tests) lowers the two bounds to 8
+ * and 64 members and a workgroup's share of a larger cluster from 4096 members to 16.  Sums are 32-bit where the tier bounds
+ * the members to 2^20 (222 * 2^20 < 2^28), 64-bit beyond.  No load leaves a line (a line's last, partial four bytes go byte by
+ * byte), and every store to the written member's row comes after the last read of it (csrc/fqd_consensus.hip).  Scratch during
+ * the call: 4 bytes a cluster, about 4.2 bytes a record for the lists, 48 bytes a column of the longest read where n >= 2^20.
+ * Two results come back in between (the clusters and checks, the lists' lengths); returns after the stream has drained. */
+#define FQD_CONSENSUS_SMALL_TIERS 1u    /* test hook: tier bounds of 8 and 64 members, 16 members a workgroup beyond */
+typedef struct fqd_consensus_info { uint64_t clusters;      /* clusters of >= 2 members */
+                                    uint64_t members;       /* records read for them */
+                                    uint64_t bases_changed; /* columns whose winner is not the written member's own letter */
+                                    uint64_t reads_changed; /* written records with at least one such column */
+                                    uint64_t largest; } fqd_consensus_info;
+int  fqd_consensus(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint64_t n, uint8_t* text, const uint64_t* start, const uint32_t* size,
+                   const uint64_t* seq_off, const uint32_t* seq_len, uint32_t flags, uint8_t* changed, fqd_consensus_info* info);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
