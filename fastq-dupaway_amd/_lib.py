@@ -90,6 +90,10 @@ class NearInfo(C.Structure):                                 # fqd_near_info
                                                 "over_limit_nodes")] + [("max_group", C.c_uint32), ("reserved", C.c_uint32), ("stage_ms", C.c_float * 3)]
 
 
+class NearUmiInfo(C.Structure):                              # fqd_near_umi_info
+    _fields_ = [("near", NearInfo), ("links", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 class ConsensusInfo(C.Structure):                            # fqd_consensus_info
     _fields_ = [(name, C.c_uint64) for name in ("clusters", "members", "bases_changed", "reads_changed", "largest")]
 
@@ -205,6 +209,7 @@ def load_library():
     L.fqd_read_places.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(PlacesInfo)]
     L.fqd_optical_split.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, vp, C.POINTER(OpticalInfo)]
     L.fqd_near_merge.argtypes = [vp, C.POINTER(ReadsDesc), vp, u64, u32, u32, vp, C.POINTER(NearInfo)]
+    L.fqd_near_merge_umi.argtypes = [vp, C.POINTER(ReadsDesc), vp, vp, u64, u32, u32, vp, vp, vp, C.POINTER(UmiInfo), vp, C.POINTER(NearUmiInfo)]
     L.fqd_consensus.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, u32, vp, C.POINTER(ConsensusInfo)]
     L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
     L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]

@@ -399,6 +399,21 @@ class Engine:
                                            C.byref(got) if out else None))
         return got
 
+    def near_merge_umi(self, segs: Sequence[Reads], owner, link, n: int, distance: int, text, id_start, umi_off, info, owner_out, flags: int = 0, out=True):
+        """owner_out[i] (n uint32, device) = the first record of record i's molecule: the exact clusters of `owner` (owners' of
+        the run keyed UMI ‖ sequence, over the same n records of segs — the sequences as they lie in the files) that hang
+        together through pairs under ONE UMI, of equal shape, whose mates differ in at most `distance` bytes each, and through
+        link (umi_merge's owner_out, or None for no links).  text, id_start, umi_off, info: umi_find's over file 1.  flags: 0 or
+        _lib.NEAR_WEAK_SEEDS.  Returns the call's fqd_near_umi_info (_lib.NearUmiInfo: .near, .links); out=None hands the library
+        a null pointer, which it refuses."""
+        if segs is not None and len(segs) != self.segments:
+            raise ValueError(f"engine has {self.segments} mate(s) per record, got {len(segs)}")
+        got = _lib.NearUmiInfo() if out else None
+        self._check(self._L.fqd_near_merge_umi(self._h, self._desc(segs) if segs is not None else None, self._p(owner), self._p(link), n, distance, flags,
+                                               self._p(text), self._p(id_start), self._p(umi_off), C.byref(info) if info is not None else None,
+                                               self._p(owner_out), C.byref(got) if out else None))
+        return got
+
     # -- FQD_FAST_CONSENSUS (csrc/fqd_consensus.hip) -----------------------------------------------------------
     def consensus(self, perm, head, n: int, text, start, size, seq_off, seq_len, flags: int = 0, changed=None, info=True):
         """One file's text (device bytes, changed in place): the sequence and quality lines of the written member perm[head

@@ -69,6 +69,7 @@ FastModes FastModes::from_env()
     m.size_in = is_on("FQD_FAST_SIZEIN");
     m.optical = pixel_distance("FQD_FAST_OPTICAL");
     m.hamming = uint32_t(choice("FQD_FAST_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
+    m.umi_hamming = uint32_t(choice("FQD_FAST_UMI_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
     m.consensus = is_on("FQD_FAST_CONSENSUS");
     return m;
 }
@@ -78,6 +79,7 @@ std::string FastModes::names() const
     // (min_size 1 and max_size 0 are the two bounds that take nothing out: not named)
     const std::pair<bool, std::string> all[] = {
         {keep_best, "FQD_FAST_KEEP=best"}, {clusters, "FQD_FAST_CLUSTERS=1"}, {both_strands, "FQD_FAST_STRAND=both"}, {umi != 0, umi_name()}, {umi_mismatch != 0, mismatch_name()},
+        {umi_hamming != 0, umi_hamming_name()},
         {hamming != 0, hamming_name()},
         {optical != 0, optical_name()},
         {consensus, "FQD_FAST_CONSENSUS=1"},
@@ -102,6 +104,11 @@ void FastModes::check(bool unordered, size_t n_devices, Format format) const
     if (hamming && umi)
         throw FastModeRefusal(hamming_name() + " with " + umi_name() + (umi_mismatch ? " and " + mismatch_name() : std::string()) +
                               ": which sequences under one UMI are copies of one molecule is a rule of its own, and this switch merges by sequence alone");
+    if (umi_hamming && !umi)
+        throw FastModeRefusal(umi_hamming_name() + " merges the sequences under one of the UMIs that FQD_FAST_UMI finds: set FQD_FAST_UMI=colon or FQD_FAST_UMI=underscore as well");
+    if (umi_hamming && both_strands)
+        throw FastModeRefusal(umi_hamming_name() + " with FQD_FAST_STRAND=both: a substituted base can change which orientation of a read is the canonical one, so copies with errors "
+                              "may be keyed in opposite orientations and never be compared");
     if (consensus && both_strands)
         throw FastModeRefusal("FQD_FAST_CONSENSUS=1 with FQD_FAST_STRAND=both: the members of a cluster may be keyed in opposite orientations, and a column-wise vote "
                               "needs them in one; turning reads for the vote is not done");
@@ -147,6 +154,10 @@ std::string FastModes::out_of_memory_note() const
              " bytes an exact cluster for the seeds and their sort (12 bytes a seed, " + std::to_string(hamming + 1) +
              " seeds a cluster, twice over), 4 bytes a record for the labels and 8 bytes for every pair of clusters found near, with room for " +
              std::to_string(hamming + 1) + " such pairs a cluster from the start";
+    if (umi_hamming)
+        s += "; FQD_FAST_UMI_HAMMING takes 4 bytes a record for the molecules' owners" + std::string(umi_mismatch ? ", 4 bytes a record more for the exact owners kept beside the merged ones" : "") +
+             " and, while it merges, " + std::to_string(24 * (umi_hamming + 1)) + " bytes an exact cluster for the seeds and their sort, 4 bytes a record for the labels and 8 bytes for every "
+             "pair of clusters found near" + (umi_mismatch ? " and every link" : "") + ", with room for " + std::to_string(umi_hamming + 1) + " of them a cluster from the start";
     if (optical)
         s += "; FQD_FAST_OPTICAL takes 16 bytes a record for the places (tile, x, y, surface) and 4 for the split owners and, while it splits, "
              "up to 17 bytes a record of scratch (the scratch of the grouping serves where it is as large)";

@@ -69,7 +69,9 @@ struct KeyedReads {
     fqd_reads reads[2] = {}, umi_mate{};                         // what is submitted: the given or the canonical reads; mate 1 as `UMI bases ‖ sequence`
 };
 // Every duplicate's link to an earlier record of its key and the first record of the key, until the records are grouped.
-struct Links { Device<uint32_t> link, owner; };
+// FQD_FAST_UMI_HAMMING: where every record's UMI field lies and the run's shape, taken over from KeyedReads when that leaves, and
+// with FQD_FAST_UMI_MISMATCH the merged owners, which are the molecules' links while `owner` stays the exact owners.
+struct Links { Device<uint32_t> link, owner; Device<uint32_t> umi_off, umi_link; fqd_umi_info umi_info{}; };
 // The records grouped by owner: an order of the n records and a flag at the first place of every cluster; with
 // FQD_FAST_SIZEIN what every record stands for, while sizes are made.  Until the outputs are planned.
 struct Clusters { Device<uint32_t> perm; Device<uint8_t> head; Device<uint32_t> weight; uint64_t count = 0; };
@@ -91,6 +93,7 @@ struct OrderedResidentRun {
     Device<uint8_t> keep;
     uint64_t merged_clusters = 0;                                // FQD_FAST_UMI_MISMATCH: the clusters the merge leaves
     uint64_t near_taken = 0;                                     // FQD_FAST_HAMMING: the exact clusters that went into another
+    uint64_t umi_near_taken = 0;                                 // FQD_FAST_UMI_HAMMING: the clusters in front of the stage that went into another
     Places places; uint64_t optical_more = 0;                    // FQD_FAST_OPTICAL: the places; the clusters the split adds
     uint64_t consensus_bases = 0, consensus_reads = 0;           // FQD_FAST_CONSENSUS: the bases replaced, and the records (pairs) that hold them
     std::string cluster_text[2];                                 // FQD_FAST_CLUSTERS
@@ -241,7 +244,8 @@ struct OrderedResidentRun {
     // sequence`, gives the exact owners and, through fqd_group_owners and the sizes, every exact cluster's count; after
     // fqd_engine_reset the same batches go in again keyed by the sequences alone, into the same flags and links — those of the
     // first pass are used up by fqd_owners — which gives every record's sequence group.  fqd_umi_merge makes the merged owners
-    // of the three, fqd_owners_to_keep the flags; the merged owners are THE owners from here on.
+    // of the three, fqd_owners_to_keep the flags; the merged owners are THE owners from here on.  With FQD_FAST_UMI_HAMMING the
+    // exact owners stay THE owners — the nodes of merge_near_umi — and the merged ones are kept beside them as its links.
     void merge_umi_neighbours(const KeyedReads& k, Links& links, Clusters& clusters)
     {
         Device<uint32_t> owner_seq, exact_size, merged_owner;
@@ -273,7 +277,8 @@ struct OrderedResidentRun {
             std::cerr << "fast: UMI mismatches <= " << fast.umi_mismatch << ", " << merged.merged << " of " << merged.nodes << " exact clusters merged into others, largest network "
                       << merged.largest << ", " << merged.sweeps << " sweeps\n";
         merged_clusters = merged.nodes - merged.merged;
-        links.owner.swap(merged_owner);                              // (the exact owners leave with this stage)
+        if (fast.umi_hamming) links.umi_link.swap(merged_owner);     // (4 bytes a record more: the exact owners stay)
+        else links.owner.swap(merged_owner);                         // (the exact owners leave with this stage)
     }
 
     // Stage 6: the duplicates are counted and, for the `linked` switches, the links resolved to the first record of every key
@@ -290,6 +295,7 @@ struct OrderedResidentRun {
             engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
         }
         if (fast.hamming) { merge_near(links, clusters); dups = n - clusters.count; }
+        if (fast.umi_hamming) { merge_near_umi(links, clusters); dups = n - clusters.count; }
         if (fast.optical) { split_optical(links, clusters); dups = n - clusters.count; }
         if (clusters.count + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
     }
@@ -322,6 +328,44 @@ struct OrderedResidentRun {
         if (StageClock::on())
             std::cerr << "fast: substitutions <= " << fast.hamming << ", " << near_taken << " of " << merged.nodes << " exact clusters merged into others, " << merged.pairs
                       << " pairs compared, " << merged.edges << " near, largest seed group " << merged.largest_group << ", " << merged.sweeps << " sweeps\n";
+    }
+
+    // FQD_FAST_UMI_HAMMING, behind the grouping, where merge_near stands (the two never run together): fqd_near_merge_umi makes of
+    // the exact clusters of the run keyed `UMI bases ‖ sequence` — the reads as they lie in the files, the exact owners, every
+    // record's UMI field and, with FQD_FAST_UMI_MISMATCH, the merged owners as links — the molecules, each owned by its first
+    // record; their owners are THE owners from here on, fqd_owners_to_keep makes the flags of them and fqd_group_owners groups
+    // the records once more.  The clusters in front of the stage are the exact ones, or the merge's where it ran.
+    void merge_near_umi(Links& links, Clusters& clusters)
+    {
+        Device<uint32_t> merged_owner;
+        merged_owner.reserve(n);
+        fqd_reads reads[2] = {};
+        for (int s = 0; s < S; ++s) reads[s] = fqd_reads{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].seq_off.p, dev[s].seq_len.p, 0, 0};
+        const uint64_t before = fast.umi_mismatch ? merged_clusters : clusters.count;
+        fqd_near_umi_info merged{};
+        {
+            StageClock::Scope t("fast: UMI substitutions, exact clusters merged on the GPU");
+            engine_ok<DeviceError>(e, fqd_near_merge_umi(e, reads, links.owner.p, fast.umi_mismatch ? links.umi_link.p : nullptr, n, fast.umi_hamming, 0,
+                                                         reinterpret_cast<const uint8_t*>(dev[0].text.p), dev[0].start.p, links.umi_off.p, &links.umi_info, merged_owner.p,
+                                                         &merged));
+            if (merged.near.over_limit_first != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal(fast.umi_hamming_name() + ": " + std::to_string(merged.near.over_limit_nodes) + " different sequences under one UMI, the one of record " +
+                                      std::to_string(merged.near.over_limit_first) + " (counted from 0) of " + in[0] + " the first among them, share one of the " +
+                                      std::to_string(fast.umi_hamming + 1) + " segments their first mate is cut into; a group of at most " +
+                                      std::to_string(merged.near.max_group) + " is compared (adapter dimers, amplicons: trim the reads, or run without the switch)");
+            if (merged.near.nodes != clusters.count) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
+            if (merged.near.nodes - merged.links != before) throw DeviceError("GPU engine: internal error (the links and the merged UMI clusters differ in number)");
+            links.owner.swap(merged_owner);                          // (the exact owners leave with this stage)
+            links.umi_link.release(); links.umi_off.release();
+            engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
+            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
+        }
+        if (clusters.count != merged.near.merged) throw DeviceError("GPU engine: internal error (the merge and the second grouping count different clusters)");
+        umi_near_taken = before - merged.near.merged;
+        if (StageClock::on())
+            std::cerr << "fast: UMI substitutions <= " << fast.umi_hamming << ", " << umi_near_taken << " of " << before << " clusters merged into others, " << merged.near.pairs
+                      << " pairs compared, " << merged.near.edges << " near, " << merged.links << " links, largest seed group " << merged.near.largest_group << ", "
+                      << merged.near.sweeps << " sweeps\n";
     }
 
     // FQD_FAST_OPTICAL, behind the grouping (and the merges, where they run): fqd_optical_split makes of every cluster its
@@ -467,7 +511,7 @@ struct OrderedResidentRun {
 
 } // namespace
 
-// Everything about the fourteen switches that their values and the command line decide, before any GPU call.
+// Everything about the fifteen switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     fast_ = FastModes::from_env();
@@ -512,6 +556,7 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
                     run.rewrite_keys(keyed, clusters);                                                       // stage 3
                     if (!run.first_pass(keyed, links)) return false;                                         // stage 4
                     if (fast_.umi_mismatch) run.merge_umi_neighbours(keyed, links, clusters);                // stage 5
+                    if (fast_.umi_hamming) { links.umi_off.swap(keyed.umi_off); links.umi_info = keyed.umi_info; }   // (merge_near_umi reads them in stage 6)
                 }
                 if (std::getenv("FQD_TEST_FAIL_RESIDENT")) throw DeviceError("GPU engine: forced by FQD_TEST_FAIL_RESIDENT");      // tests: the hand-over is announced
                 run.count_and_group(links, clusters);                                                        // stage 6 ...
@@ -540,6 +585,10 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     if (verbose_ && fast_.hamming)
         std::cout << run.near_taken << (S == 1 ? " distinct sequences" : " distinct sequence pairs") << " were taken for copies of another that differs in at most " << fast_.hamming
                   << (S == 1 ? " bases (" : " bases a mate (") << fast_.hamming_name() << ").\n";
+    // FQD_FAST_UMI_HAMMING: what `-v` says behind its first line, which counts every record that was not written
+    if (verbose_ && fast_.umi_hamming)
+        std::cout << run.umi_near_taken << (S == 1 ? " distinct sequences" : " distinct sequence pairs") << " under one UMI were taken for copies of another that differs in at most "
+                  << fast_.umi_hamming << (S == 1 ? " bases (" : " bases a mate (") << fast_.umi_hamming_name() << ").\n";
     // FQD_FAST_OPTICAL: what `-v` says behind its first line, which counts the optical duplicates only
     if (verbose_ && fast_.optical)
         std::cout << run.optical_more << (S == 1 ? " reads" : " read pairs") << " that repeat an earlier sequence were written: not optical duplicates (" << fast_.optical_name() << ").\n";

@@ -957,6 +957,33 @@ typedef struct fqd_near_info {
 int  fqd_near_merge(fqd_engine* e, const fqd_reads* reads, const uint32_t* owner, uint64_t n, uint32_t distance, uint32_t flags,
                     uint32_t* owner_out, fqd_near_info* out);
 
+/* ---- FQD_FAST_UMI_HAMMING=D: exact clusters under ONE UMI within D substituted bases of one another are one molecule (added
+ * within ABI version 5: purely additive; no existing entry launches anything new, fqd_near_merge among them).  Rule and proofs:
+ * csrc/fqd_near_umi_core.hpp.  A node is one exact cluster of the run keyed B(U) ‖ mate 1, mate 2 (owner[i] == i).  Its tag T(U)
+ * is the umi_len bytes of its first record's UMI field with every joiner place set to 0; with the run's one shape, equal tags
+ * are equal B(U).  Two nodes are near when their tags are equal and they are near by fqd_near_merge's rule (equal shapes, at most
+ * D differing byte positions a mate).  With link, every node v is also joined to link[v].  A molecule is a connected component of
+ * the two relations, owned by its first record in input order.
+ *
+ * fqd_near_merge_umi: device memory only (info, out: host, not NULL).  reads, owner, n, distance, flags and owner_out are
+ * fqd_near_merge's: reads = the sequences as they lie in the files, NOT the keyed `UMI bases ‖ sequence` bytes.  text, id_start,
+ * umi_off and info are fqd_umi_find's over file 1 and the same n records; an info that names a refused record, or a umi_len
+ * outside 1 .. 64, is FQD_ERR_ARG.  link (n uint32, or NULL for no links) = fqd_umi_merge's owner_out over the same owners: only
+ * its entries at nodes are read; a link[v] above v, or one that is no node, is FQD_ERR_ARG (counted on the device, nothing
+ * written).  owner_out must not overlap owner, link, id_start, umi_off or what fqd_near_merge names.  A node's seed keys are
+ * fqd_near_merge's with the ceil(umi_len / 8) little-endian words of its tag absorbed in front of the segment's bytes, so that
+ * one sequence under many UMIs is many groups of one; the verification compares the tags byte for byte, lane gl of a pair's
+ * eight lanes tag word gl, before shapes and mates.  No load leaves U.  (link[v], v) of every node with link[v] != v stands in
+ * the edge list in front of the near edges; the list's room and regrowth cover both.  *out: near = fqd_near_merge's counts, with
+ * merged = the molecules and edges = the near edges alone; links = the nodes with link[v] != v.  A seed group beyond
+ * FQD_NEAR_MAX_GROUP is refused as in fqd_near_merge.  Scratch and the results that come back are fqd_near_merge's, and one
+ * result more (the links) where link is given. */
+typedef struct fqd_near_umi_info { fqd_near_info near; uint64_t links; uint64_t reserved; } fqd_near_umi_info;
+int  fqd_near_merge_umi(fqd_engine* e, const fqd_reads* reads, const uint32_t* owner, const uint32_t* link /* may be NULL */,
+                        uint64_t n, uint32_t distance, uint32_t flags,
+                        const uint8_t* text, const uint64_t* id_start, const uint32_t* umi_off, const fqd_umi_info* info,
+                        uint32_t* owner_out, fqd_near_umi_info* out);
+
 /* ---- FQD_FAST_CONSENSUS=1: the written member of every cluster carries the cluster's consensus (added within ABI version 5:
  * purely additive; no existing entry launches anything new).  Rule and proofs: csrc/fqd_consensus_core.hpp.  A cluster is a run
  * of (perm, head); its written member is perm[head place].  In every column p of a cluster of two or more members each member
