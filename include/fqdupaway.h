@@ -15,6 +15,16 @@
  * engine is available from fqd_last_error().  `device` pointers are HIP
  * device pointers, `stream` is a hipStream_t passed as void*.
  *
+ * Buffers: no entry point reads or writes a caller's buffer outside the extent stated at its declaration (n entries,
+ * the bytes a span or an offset array names, a capacity), and a `const` input comes back bit for bit; what lies before
+ * or behind a buffer, and where it lies — offsets into a text may exceed 2^32 — changes no result.  (Byte buffers are
+ * loaded in aligned words of up to 16 bytes, so a load may cover the rest of the aligned 16 bytes that hold a buffer's
+ * first or last byte; such a word never crosses a page, and none of those bytes reaches a result.  Stores are exact.)
+ * A pointer needs the natural alignment of its element type (uint32_t: 4, uint64_t: 8, bytes: none) and no more,
+ * unless its declaration says otherwise.  The one exception written down: fqd_gunzip / fqd_gunzip_arriving want 32
+ * readable bytes behind the last byte of the packed input.  (tests/test_gpu_buffer_extents.py holds every entry point
+ * to this.)
+ *
  * Contract: record i of an engine's input
  * order is KEPT iff no record j < i has the identical sequence (for paired
  * engines: identical mate-1 AND mate-2 sequences, lengths included) over the

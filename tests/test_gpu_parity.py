@@ -225,7 +225,7 @@ def test_reference_fixture_paired_fast(golden_dir):
 def test_synthetic_1m_matches_oracle_and_closed_form(oracle, torch_cuda):
     torch = torch_cuda
     n, L = 1_000_000, 150
-    bases = torch.empty(n * L + 16, dtype=torch.uint8, device="cuda")
+    bases = torch.empty(n * L, dtype=torch.uint8, device="cuda")
     expect = torch.empty(n, dtype=torch.uint8, device="cuda")
     keep = torch.empty(n, dtype=torch.uint8, device="cuda")
     with Engine(segments=1, capacity_reads=n, capacity_bases=n * L) as e:
@@ -252,7 +252,7 @@ def test_table_grows_between_bulk_batches(torch_cuda, paired):
     S = 2 if paired else 1
     sizes = [1_200_000, 1_300_000, 2_900_000, 1_100_000, 6_000_000, 5_000_000]
     n, L = sum(sizes), 150
-    bases = [torch.empty(n * L + 16, dtype=torch.uint8, device="cuda") for _ in range(S)]
+    bases = [torch.empty(n * L, dtype=torch.uint8, device="cuda") for _ in range(S)]
     expect = torch.empty(n, dtype=torch.uint8, device="cuda")
     keep = torch.zeros(n, dtype=torch.uint8, device="cuda")
     with Engine(segments=S) as e:
@@ -273,7 +273,7 @@ def test_table_grows_between_bulk_batches(torch_cuda, paired):
 def test_synthetic_pairs_match_oracle(oracle, torch_cuda):
     torch = torch_cuda
     n, L = 400_000, 150
-    b1 = torch.empty(n * L + 16, dtype=torch.uint8, device="cuda"); b2 = torch.empty_like(b1)
+    b1 = torch.empty(n * L, dtype=torch.uint8, device="cuda"); b2 = torch.empty_like(b1)
     expect = torch.empty(n, dtype=torch.uint8, device="cuda"); keep = torch.empty_like(expect)
     with Engine(segments=2, capacity_reads=n) as e:
         e.synth_reads(99, 0, n, L, 200, 0, b1, None)
@@ -292,7 +292,7 @@ def test_full_size_100m_se_properties(torch_cuda):
     """BASELINE.json configs[1]: 100 M x 150 bp, ~20 % duplicates, one MI355X."""
     torch = torch_cuda
     n, L = 100_000_000, 150
-    bases = torch.empty(n * L + 16, dtype=torch.uint8, device="cuda")
+    bases = torch.empty(n * L, dtype=torch.uint8, device="cuda")
     expect = torch.empty(n, dtype=torch.uint8, device="cuda")
     keep = torch.empty(n, dtype=torch.uint8, device="cuda")
     with Engine(segments=1, capacity_reads=n, capacity_bases=n * L) as e:
@@ -322,7 +322,7 @@ def test_full_size_100m_pe_properties(oracle, torch_cuda):
     a prefix is self-contained because copies only ever point at earlier pairs."""
     torch = torch_cuda
     n, L = 100_000_000, 150
-    b1 = torch.empty(n * L + 16, dtype=torch.uint8, device="cuda"); b2 = torch.empty_like(b1)
+    b1 = torch.empty(n * L, dtype=torch.uint8, device="cuda"); b2 = torch.empty_like(b1)
     expect = torch.empty(n, dtype=torch.uint8, device="cuda"); keep = torch.empty_like(expect)
     with Engine(segments=2, capacity_reads=n, capacity_bases=2 * n * L) as e:
         e.synth_reads(7, 0, n, L, 200, 0, b1, None)
@@ -512,7 +512,7 @@ def test_engine_orders_itself_after_the_callers_stream(torch_cuda):
     dev = torch.device("cuda", 0)
     n, LL = 4_000_000, 150
     with Engine(segments=1) as e:
-        bases = torch.empty(n * LL + 16, dtype=torch.uint8, device=dev)
+        bases = torch.empty(n * LL, dtype=torch.uint8, device=dev)
         expect = torch.empty(n, dtype=torch.uint8, device=dev)
         e.synth_reads(5, 0, n, LL, 200, 0, bases, expect)
         e.sync()
@@ -557,7 +557,7 @@ def test_last_batch_declared_gives_the_same_flags(monkeypatch, torch_cuda, paire
     S = 2 if paired else 1
     sizes = [3_000_000, 1_500_000, 2_500_000]
     n, L = sum(sizes), 150
-    bases = [torch.empty(n * L + 16, dtype=torch.uint8, device="cuda") for _ in range(S)]
+    bases = [torch.empty(n * L, dtype=torch.uint8, device="cuda") for _ in range(S)]
     expect = torch.empty(n, dtype=torch.uint8, device="cuda")
     keep = torch.empty(n, dtype=torch.uint8, device="cuda")
     with Engine(segments=S, capacity_reads=n) as e:
