@@ -2,7 +2,7 @@
 // of every cluster's written member replaced, where they lie in the text, by the cluster's column-wise consensus.  Rule and
 // proofs: fqd_consensus_core.hpp.  Nothing in here is called unless the switch is set.
 //
-//   heads    check_heads_kernel + u64_scan_kernel + head_write_kernel (the three launches of fqd_record_scan.hpp's scan): the
+//   heads    check_heads_kernel + scan_tiles_kernel + head_write_kernel (the three launches of fqd_record_scan.hpp's scan): the
 //            head places of (perm, head) compacted in order, so that a cluster's size is the next head place minus its own.
 //            The first of them also holds every record's lines against lines_fit, every member's sequence length against the
 //            member in front of it, and finds the longest sequence.  The counts come back; a bad one ends the call here,
@@ -56,7 +56,10 @@ static_assert((1ull << 31) / kMaxGroups <= kMax32, "a workgroup's share of a clu
 static_assert(kWaves == kChunk, "thread (w, lane) decides column kChunk * lane + w of a round: as many waves as columns a lane");
 static_assert(kWaves * kWords * kRound * sizeof(uint32_t) <= 64 * 1024, "the four waves' states of a round fit a workgroup's LDS");
 
-using fqdscan::u64_scan_kernel;
+using fqdscan::head_write_kernel;
+using fqdscan::scan_tiles_kernel;
+using fqdwave::wave_max;
+using fqdwave::wave_sum;
 
 // The text and the record arrays of one file, and the order.
 struct Rows { uint8_t* text; const uint32_t* perm; const uint64_t* start; const uint32_t* size; const uint64_t* seq_off; const uint32_t* seq_len; };
@@ -70,27 +73,6 @@ struct Counters {
     uint32_t listed[3];                                      // clusters on the lanes', the workgroup's and the many-workgroups list
     uint32_t largest, longest;                               // members of the largest cluster; the longest sequence line
 };
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                // (lane 0's is the wave's)
-}
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const uint32_t o = __shfl_down(v, d, 64); v = o > v ? o : v; }
-    return v;
-}
 
 // ---- heads -------------------------------------------------------------------------------------------------------------------
 
@@ -115,41 +97,14 @@ void check_heads_kernel(Rows R, const uint8_t* __restrict__ head, uint64_t n, un
         if (!h) { const uint32_t before = R.perm[k - 1]; bad_len += before < n && R.seq_len[before] != L; }
     }
     bad_place = wave_sum(bad_place); bad_lines = wave_sum(bad_lines); bad_len = wave_sum(bad_len); longest = wave_max(longest);
-    s = wave_sum64(s);
     if ((threadIdx.x & 63) == 0) {
-        ws[threadIdx.x >> 6] = s;
         if (bad_place) atomicAdd(&counters->bad_place, static_cast<unsigned long long>(bad_place));
         if (bad_lines) atomicAdd(&counters->bad_lines, static_cast<unsigned long long>(bad_lines));
         if (bad_len) atomicAdd(&counters->bad_len, static_cast<unsigned long long>(bad_len));
         if (longest) atomicMax(&counters->longest, longest);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-__global__ __launch_bounds__(kBlock)
-void head_write_kernel(const uint8_t* __restrict__ head, uint64_t n, uint64_t m, const unsigned long long* __restrict__ tile_start,
-                       uint32_t* __restrict__ head_place)
-{
-    __shared__ uint32_t ws[kWaves];
-    const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
-    bool is_head[8];
-    uint32_t s = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); is_head[e] = k < n && head[k] != 0; s += is_head[e]; }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long at = tile_start[blockIdx.x] + inc - s;
-    for (uint32_t w = 0; w < wave; ++w) at += ws[w];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if (is_head[e] && at < m) head_place[at] = uint32_t(base + uint32_t(e));
-        at += is_head[e];
-    }
+    s = fqdwave::block_total<kWaves>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 // ---- classes -----------------------------------------------------------------------------------------------------------------
@@ -175,17 +130,9 @@ void classify_kernel(const uint32_t* __restrict__ head_place, Rows R, uint64_t m
     const uint32_t cls = s < 2u ? 3u : s <= tiers.small ? 0u : s <= tiers.block ? 1u : 2u;
     uint32_t at = 0;                                         // the cluster's place among the block's of its class
 #pragma unroll
-    for (uint32_t t = 0; t < 3u; ++t) {
-        const unsigned long long mine = __ballot(cls == t);
-        if (!mine) continue;                                 // (the same for every lane)
-        const int leader = __ffsll(mine) - 1;
-        uint32_t first = 0;
-        if (int(lane) == leader) first = atomicAdd(&count[t], uint32_t(__popcll(mine)));
-        first = __shfl(first, leader, 64) + uint32_t(__popcll(mine & ((1ull << lane) - 1ull)));
-        if (cls == t) at = first;
-    }
+    for (uint32_t t = 0; t < 3u; ++t) at += fqdwave::ballot_append(cls == t, &count[t]);
     const uint32_t clusters = uint32_t(__popcll(__ballot(cls != 3u)));
-    const unsigned long long members = wave_sum64(cls != 3u ? s : 0u);
+    const unsigned long long members = wave_sum<unsigned long long>(cls != 3u ? s : 0u);
     const uint32_t largest = wave_max(s);
     if (lane == 0) {
         if (clusters) { atomicAdd(&clusters_b, clusters); atomicAdd(&members_b, members); }
@@ -287,9 +234,7 @@ void vote_lanes_kernel(const unsigned long long* __restrict__ list, uint32_t n_i
         for (uint32_t e = 0; e < kChunk; ++e)
             if (e < width) n_changed += store_column(decide(st[e], own[e]), R.text + own_seq + col + e, R.text + own_qual + col + e);
     }
-    uint32_t any = n_changed;
-#pragma unroll
-    for (int d = int(kGroup) / 2; d > 0; d >>= 1) any |= __shfl_xor(any, d, int(kGroup));
+    const uint32_t any = fqdwave::group_or<int(kGroup)>(n_changed);
     if (m && gl == 0u && any) mark_read(written, changed, counters);
     n_changed = wave_sum(n_changed);
     if (lane == 0 && n_changed) atomicAdd(&counters->bases_changed, static_cast<unsigned long long>(n_changed));
@@ -449,7 +394,7 @@ int fqd_consensus(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint
     Counters* counters = reinterpret_cast<Counters*>(static_cast<char*>(small) + (((size_t(tiles) + 1) * sizeof(unsigned long long) + 255) & ~size_t(255)));
     FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
     hipLaunchKernelGGL(check_heads_kernel, dim3(tiles), dim3(kBlock), 0, stream, R, head, n, tile_sum, counters);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile_sum, tiles, d_total);
+    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile_sum, tiles, d_total);
     FQD_TRY(e, hipGetLastError());
     unsigned long long m = 0;
     Counters got{};

@@ -32,12 +32,20 @@
 #include <cstring>
 
 #include "fqd_internal.hpp"
+#include "fqd_record_scan.hpp"
 
 namespace {
 
 constexpr int kBlock = 256;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kFileB = 0x80000000u;             // payload of a record of file 2: kFileB | index
+
+using fqdscan::scan_tiles_kernel;                    // the one-block scan over tile sums (fqd_record_scan.hpp)
+using fqdwave::block_exclusive;                      // and what a block does around it (fqd_wave.hpp)
+using fqdwave::block_total;
+using fqdwave::wave_max;
+using fqdwave::wave_min;
+using fqdwave::wave_sum;
 
 // ---------------------------------------------------------------------------------------------
 // 1. tag extraction (fastqview.cpp:190-204; fastaview.cpp:153-167 is the same rule): the tag
@@ -103,8 +111,7 @@ void len_range_kernel(Union u, unsigned int* __restrict__ min_max)
         const uint32_t L = i < u.n_a ? u.len_a[i] : u.len_b[i - u.n_a];
         lo = min(lo, L); hi = max(hi, L);
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { lo = min(lo, __shfl_down(lo, d, 64)); hi = max(hi, __shfl_down(hi, d, 64)); }
+    lo = wave_min(lo); hi = wave_max(hi);
     if ((threadIdx.x & 63) == 0) { atomicMin(&min_max[0], lo); atomicMax(&min_max[1], hi); }
 }
 
@@ -261,27 +268,8 @@ void radix_hist_kernel(const uint64_t* __restrict__ keys, uint64_t N, uint32_t s
 __global__ __launch_bounds__(1024)
 void radix_rowscan_kernel(uint32_t* __restrict__ counts, uint32_t n_tiles, uint32_t* __restrict__ tot)
 {
-    __shared__ uint32_t wave_tot[16];
-    __shared__ uint32_t carry_s;
-    uint32_t* row = counts + uint64_t(blockIdx.x) * n_tiles;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t c0 = 0; c0 < n_tiles; c0 += 1024u) {
-        const uint32_t i = c0 + threadIdx.x;
-        const uint32_t v = i < n_tiles ? row[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(threadIdx.x & 63u) >= d) inc += up; }
-        if ((threadIdx.x & 63u) == 63u) wave_tot[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        uint32_t before = carry_s;
-        for (uint32_t w = 0; w < (threadIdx.x >> 6); ++w) before += wave_tot[w];
-        if (i < n_tiles) row[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry_s = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) tot[blockIdx.x] = carry_s;
+    const uint32_t sum = fqdscan::scan_in_place(counts + uint64_t(blockIdx.x) * n_tiles, n_tiles);   // (a block a digit's row)
+    if (threadIdx.x == 0) tot[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -295,15 +283,8 @@ void radix_scatter_kernel(const uint64_t* __restrict__ keys, const uint32_t* __r
     const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
     // digit bases: exclusive scan of tot[0..255] (every block repeats it: 256 values)
     {
-        const uint32_t v = tot[t];
-        uint32_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-        if (lane == 63u) wsum[wave] = inc;
-        __syncthreads();
-        uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
-        dbase[t] = before + inc - v;
+        uint32_t total;
+        dbase[t] = block_exclusive<4>(tot[t], wsum, total);
     }
     __syncthreads();
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -416,8 +397,7 @@ void join_summary_kernel(const uint32_t* __restrict__ vals, const uint8_t* __res
             prev_a = !b;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { na += __shfl_down(na, d, 64); h1 = max(h1, __shfl_down(h1, d, 64)); b1 = max(b1, __shfl_down(b1, d, 64)); }
+    na = wave_sum(na); h1 = wave_max(h1); b1 = wave_max(b1);
     if ((threadIdx.x & 63) == 0) { s_a[threadIdx.x >> 6] = na; s_h[threadIdx.x >> 6] = h1; s_b[threadIdx.x >> 6] = b1; }
     __syncthreads();
     if (threadIdx.x == 0)
@@ -425,7 +405,8 @@ void join_summary_kernel(const uint32_t* __restrict__ vals, const uint8_t* __res
                                      max(max(s_b[0], s_b[1]), max(s_b[2], s_b[3])), 0u};
 }
 
-// One block: sums[t] <- (sum, max, max) over tiles before t.
+// One block: sums[t] <- (sum, max, max) over tiles before t.  (This scan and join_emit_kernel's carry two running maxima
+// beside the sum in one ladder: they stay as they are, fqd_wave.hpp's scans are sums only.)
 __global__ __launch_bounds__(1024)
 void join_carry_scan_kernel(JoinCarry* __restrict__ sums, uint32_t n_tiles)
 {
@@ -536,38 +517,8 @@ void pair_count_kernel(const uint32_t* __restrict__ match_a, uint64_t n_a, uint3
     uint32_t c = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const uint64_t i = base + uint32_t(e) * kBlock + threadIdx.x; c += (i < n_a && match_a[i] != kNone) ? 1u : 0u; }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// One block: exclusive scan of tile_count in place; the total goes to *total (u64).
-__global__ __launch_bounds__(1024)
-void u32_scan_kernel(uint32_t* __restrict__ data, uint32_t n, unsigned long long* __restrict__ total)
-{
-    __shared__ uint32_t wt[16];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t t0 = 0; t0 < n; t0 += 1024u) {
-        const uint32_t i = t0 + threadIdx.x;
-        const uint32_t v = i < n ? data[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-        if (lane == 63u) wt[wave] = inc;
-        __syncthreads();
-        uint32_t before = carry;
-        for (uint32_t w = 0; w < wave; ++w) before += wt[w];
-        if (i < n) data[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
+    c = block_total<4>(c, ws);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -576,22 +527,14 @@ void pair_emit_kernel(const uint32_t* __restrict__ match_a, const uint32_t* __re
 {
     __shared__ uint32_t ws[4];
     const uint64_t base = uint64_t(blockIdx.x) * kPairTile;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t at = tile_start[blockIdx.x];
     for (int e = 0; e < 8; ++e) {                      // element order inside the tile: round e, then thread
         const uint64_t i = base + uint32_t(e) * kBlock + threadIdx.x;
         const uint32_t m = i < n_a ? match_a[i] : kNone;
-        const unsigned long long vote = __ballot(m != kNone);
-        if (lane == 0) ws[wave] = uint32_t(__popcll(vote));
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < 4u; ++w) { const uint32_t c = ws[w]; before += w < wave ? c : 0u; total += c; }
-        if (m != kNone) {
-            const uint32_t k = at + before + uint32_t(__popcll(vote & ((1ull << lane) - 1ull)));
-            pair_a[k] = perm_a[i]; pair_b[k] = perm_b[m];
-        }
+        uint32_t total;
+        const uint32_t k = at + block_exclusive<4>(m != kNone ? 1u : 0u, ws, total);
+        if (m != kNone) { pair_a[k] = perm_a[i]; pair_b[k] = perm_b[m]; }
         at += total;
-        __syncthreads();
     }
 }
 
@@ -654,8 +597,7 @@ void count_le_kernel(fqd_tags t, const uint8_t* __restrict__ probe, uint32_t pro
         const bool le = k < m ? a[k] < probe[k] : L <= probe_len;
         c += le ? 1u : 0u;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, static_cast<unsigned long long>(c));
 }
 
@@ -696,8 +638,7 @@ void range_keep_kernel(const uint32_t* __restrict__ range, uint64_t n, uint32_t 
         keep[i] = k ? 1 : 0;
         c += k ? 1u : 0u;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) c += __shfl_down(c, d, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, static_cast<unsigned long long>(c));
 }
 
@@ -719,8 +660,7 @@ void max_u32_kernel(const uint32_t* __restrict__ v, uint64_t n, uint32_t* __rest
 {
     uint32_t m = 0;
     for (uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kBlock) m = v[i] > m ? v[i] : m;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const uint32_t o = __shfl_down(m, d, 64); m = o > m ? o : m; }
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
 
@@ -737,37 +677,8 @@ void out_sizes_kernel(const uint8_t* __restrict__ keep, const uint32_t* __restri
     unsigned long long s = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); if (k < n && keep[k]) s += sizes[idx[k]]; }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-__global__ __launch_bounds__(1024)
-void u64_scan_kernel(unsigned long long* __restrict__ data, uint32_t n, unsigned long long* __restrict__ total)
-{
-    __shared__ unsigned long long wt[16];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t t0 = 0; t0 < n; t0 += 1024u) {
-        const uint32_t i = t0 + threadIdx.x;
-        const unsigned long long v = i < n ? data[i] : 0ull;
-        unsigned long long inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-        if (lane == 63u) wt[wave] = inc;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (uint32_t w = 0; w < wave; ++w) before += wt[w];
-        if (i < n) data[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
+    s = block_total<4>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -784,14 +695,8 @@ void out_offsets_kernel(const uint8_t* __restrict__ keep, const uint32_t* __rest
         sz[e] = 0; rec[e] = 0;
         if (k < n && keep[k]) { rec[e] = idx[k]; sz[e] = sizes[rec[e]]; s += sz[e]; }
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned long long inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long at = tile_start[blockIdx.x] + inc - s;
-    for (uint32_t w = 0; w < wave; ++w) at += ws[w];
+    unsigned long long total;
+    unsigned long long at = tile_start[blockIdx.x] + block_exclusive<4>(s, ws, total);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const uint64_t k = base + uint32_t(e);
@@ -819,11 +724,8 @@ void plan_gather_kernel(const uint8_t* __restrict__ keep, const uint32_t* __rest
             src_out[k] = starts[r]; len_out[k] = L; s += L;
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    s = block_total<4>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -836,14 +738,8 @@ void plan_offsets_kernel(const uint32_t* __restrict__ len, uint64_t n, const uns
     unsigned long long s = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); L[e] = k < n ? len[k] : 0u; s += L[e]; }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned long long inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long at = tile_start[blockIdx.x] + inc - s;
-    for (uint32_t w = 0; w < wave; ++w) at += ws[w];
+    unsigned long long total;
+    unsigned long long at = tile_start[blockIdx.x] + block_exclusive<4>(s, ws, total);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); if (k < n) { dst_out[k] = at; at += L[e]; } }
 }
@@ -978,7 +874,7 @@ int run_join(fqd_engine* e, const fqd_tags* a, const fqd_tags* b, const fqd_join
     FQD_TRY(e, hipMemsetAsync(sb.n_pairs, 0, sizeof(unsigned long long), stream));
     if (p_tiles) {
         hipLaunchKernelGGL(pair_count_kernel, dim3(p_tiles), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(out->match_a), u.n_a, sb.pair_tiles);
-        hipLaunchKernelGGL(u32_scan_kernel, dim3(1), dim3(1024), 0, stream, sb.pair_tiles, p_tiles, sb.n_pairs);
+        hipLaunchKernelGGL(scan_tiles_kernel<uint32_t>, dim3(1), dim3(1024), 0, stream, sb.pair_tiles, p_tiles, sb.n_pairs);
         hipLaunchKernelGGL(pair_emit_kernel, dim3(p_tiles), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(out->match_a),
                            static_cast<const uint32_t*>(out->perm_a), static_cast<const uint32_t*>(out->perm_b), u.n_a,
                            static_cast<const uint32_t*>(sb.pair_tiles), out->pair_a, out->pair_b);
@@ -1110,7 +1006,7 @@ int fqd_output_offsets(fqd_engine* e, const uint8_t* keep, const uint32_t* idx, 
     unsigned long long* tile = static_cast<unsigned long long*>(base);
     unsigned long long* d_total = tile + tiles;
     hipLaunchKernelGGL(out_sizes_kernel, dim3(tiles), dim3(kBlock), 0, stream, keep, idx, n, sizes, tile);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
+    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
     hipLaunchKernelGGL(out_offsets_kernel, dim3(tiles), dim3(kBlock), 0, stream, keep, idx, n, sizes,
                        static_cast<const unsigned long long*>(tile), reinterpret_cast<unsigned long long*>(dest));
     FQD_TRY(e, hipGetLastError());
@@ -1138,7 +1034,7 @@ int fqd_output_plan(fqd_engine* e, const uint8_t* keep, const uint32_t* idx, uin
     unsigned long long* tile = static_cast<unsigned long long*>(base);
     unsigned long long* d_total = tile + tiles;
     hipLaunchKernelGGL(plan_gather_kernel, dim3(tiles), dim3(kBlock), 0, stream, keep, idx, n, starts, sizes, src_off, len, tile);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
+    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
     hipLaunchKernelGGL(plan_offsets_kernel, dim3(tiles), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(len), n,
                        static_cast<const unsigned long long*>(tile), reinterpret_cast<unsigned long long*>(dst_off));
     FQD_TRY(e, hipGetLastError());

@@ -38,6 +38,7 @@
 #include "fqd_internal.hpp"
 #include "fqd_near_core.hpp"
 #include "fqd_near_umi_core.hpp"
+#include "fqd_wave.hpp"
 
 namespace {
 
@@ -67,26 +68,8 @@ struct Tags {
     __device__ __forceinline__ const uint8_t* at(uint32_t r) const { return text + id_start[r] + umi_off[r]; }
 };
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                // (lane 0's is the wave's)
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(v, d, 64); v = o > v ? o : v; }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t group_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = int(kLanes) / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, int(kLanes));
-    return v;
-}
+using fqdwave::wave_max;
+using fqdwave::wave_sum;
 
 // ---- seeds -------------------------------------------------------------------------------------------------------------------
 
@@ -115,14 +98,8 @@ __device__ __forceinline__ void seeds_body(const Mate& m1, const Mate& m2, bool 
                                            uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint64_t room, Counters* counters, const Tags& tags)
 {
     const uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
     const bool node = i < n && owner[i] == uint32_t(i);
-    const unsigned long long nodes = __ballot(node);
-    if (!nodes) return;                                      // (the whole wave)
-    const int leader = __ffsll(nodes) - 1;
-    unsigned long long at = 0;
-    if (int(lane) == leader) at = atomicAdd(&counters->cursor, static_cast<unsigned long long>(__popcll(nodes)) * (D + 1u));
-    at = __shfl(at, leader, 64) + static_cast<unsigned long long>(__popcll(nodes & ((1ull << lane) - 1ull))) * (D + 1u);
+    const unsigned long long at = fqdwave::ballot_append(node, &counters->cursor, static_cast<unsigned long long>(D + 1u));
     if (!node) return;
     const uint32_t r = uint32_t(i), len1 = m1.length(r), len2 = paired ? m2.length(r) : 0u;
     const uint8_t* p = m1.at(r);
@@ -180,16 +157,10 @@ void links_kernel(const uint32_t* __restrict__ owner, const uint32_t* __restrict
                   Counters* counters)
 {
     const uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
     uint32_t l = 0;
     bool has = i < n && owner[i] == uint32_t(i);
     if (has) { l = link[i]; has = l != uint32_t(i); }
-    const unsigned long long all = __ballot(has);
-    if (!all) return;                                        // (the whole wave)
-    const int leader = __ffsll(all) - 1;
-    unsigned long long at = 0;
-    if (int(lane) == leader) at = atomicAdd(&counters->edges, static_cast<unsigned long long>(__popcll(all)));
-    at = __shfl(at, leader, 64) + static_cast<unsigned long long>(__popcll(all & ((1ull << lane) - 1ull)));
+    const unsigned long long at = fqdwave::ballot_append(has, &counters->edges);
     if (has && at < room) edges[at] = make_uint2(l, uint32_t(i));
 }
 
@@ -242,15 +213,9 @@ void mark_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__
     }
     const unsigned long long groups = static_cast<unsigned long long>(__popcll(__ballot(first)));
     const unsigned long long largest = wave_max(size);
-    const unsigned long long followed = __ballot(live && e + 1 < N && keys[e + 1] == key);
-    if (followed) {                                          // (the same for every lane)
-        const uint32_t lane = threadIdx.x & 63u;
-        const int leader = __ffsll(followed) - 1;
-        unsigned long long at = 0;
-        if (int(lane) == leader) at = atomicAdd(&counters->work, static_cast<unsigned long long>(__popcll(followed)));
-        at = __shfl(at, leader, 64) + static_cast<unsigned long long>(__popcll(followed & ((1ull << lane) - 1ull)));
-        if (((followed >> lane) & 1ull) && at < N) work[at] = e;
-    }
+    const bool followed = live && e + 1 < N && keys[e + 1] == key;
+    const unsigned long long at = fqdwave::ballot_append(followed, &counters->work);
+    if (followed && at < N) work[at] = e;
     if ((threadIdx.x & 63) == 0) {
         if (groups) atomicAdd(&counters->groups, groups);
         if (largest) atomicMax(&counters->largest, largest);
@@ -266,7 +231,7 @@ __device__ __forceinline__ uint32_t lanes_count(bool on, const uint8_t* a, const
     uint32_t d = 0;
     for (uint32_t c0 = 0; __any(on && uint64_t(c0) * kChunk < n && d <= D); c0 += kLanes) {
         const bool go = on && uint64_t(c0) * kChunk < n && d <= D;
-        d += group_sum(go ? chunk_mismatches(a, b, n, c0 + gl) : 0u);
+        d += fqdwave::group_sum<kLanes>(go ? chunk_mismatches(a, b, n, c0 + gl) : 0u);
     }
     return d;
 }
@@ -303,7 +268,7 @@ __device__ __forceinline__ void verify_body(const uint64_t* __restrict__ keys, c
         if constexpr (kTagged) {
             uint32_t differs = 0;
             if (on) differs = fqdnearumi::tag_word(tags.at(b), tags.umi_len, tags.joiners, gl) != tag_a;
-            on = on && group_sum(differs) == 0u;             // (called by every lane)
+            on = on && fqdwave::group_sum<kLanes>(differs) == 0u;             // (called by every lane)
         }
         if (on) on = m1.length(b) == len1 && (!paired || m2.length(b) == len2);
         if (on) { b1 = m1.at(b); if (paired) b2 = m2.at(b); }

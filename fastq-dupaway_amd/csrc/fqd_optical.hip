@@ -9,7 +9,7 @@
 //            group takes the places of the 4th .. 7th.  Lanes 0, 1 and 2 read tile, x and y; all sixteen hold the surface
 //            against record 0's, a byte a lane.  The lowest refused record and its reason come back through one 64-bit
 //            atomicMin a wave of (record << 3 | reason).  No load leaves the ID line.
-//   heads    head_count_kernel + u64_scan_kernel + head_write_kernel (the three launches of fqd_record_scan.hpp's scan):
+//   heads    head_count_kernel + scan_tiles_kernel + head_write_kernel (the three launches of fqd_record_scan.hpp's scan):
 //            the head places of (perm, head) compacted in order, so that a cluster's size is the next head place minus its
 //            own.  The count comes back to size the rest.
 //   classes  classify_kernel, a lane a cluster: a cluster of ONE member — most of them — is only counted; a longer one goes
@@ -49,35 +49,10 @@ static_assert(kPerThread * kSplitBlock == int(kBlockLimit), "a block's threads s
 static_assert(kWave == 64 && 64 % kSmall == 0 && kGroup == 16, "the lane kernels' groups tile a wave");
 static_assert(6 * kBlockLimit * sizeof(uint32_t) <= 64 * 1024, "places, records and labels of a cluster fit a workgroup's LDS");
 
-using fqdscan::u64_scan_kernel;
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                // (lane 0's is the wave's)
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const uint32_t o = __shfl_down(v, d, 64); v = o > v ? o : v; }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t group_min(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) { const uint32_t o = __shfl_xor(v, d, int(kGroup)); v = o < v ? o : v; }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t group_or(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) v |= __shfl_xor(v, d, int(kGroup));
-    return v;
-}
+using fqdscan::head_write_kernel;
+using fqdscan::scan_tiles_kernel;
+using fqdwave::wave_max;
+using fqdwave::wave_sum;
 
 // ---- places ----------------------------------------------------------------------------------------------------------------
 
@@ -110,16 +85,14 @@ void read_places_kernel(const uint8_t* __restrict__ text, const uint64_t* __rest
             const bool live = end == fqdumi::kNone && c0 < chunks;
             fqdumi::Look k{0u, 0u, 0u};
             if (live) k = fqdumi::lane_look(line, L, uint8_t(':'), c0, gl);
-            const uint32_t e = group_min(fqdumi::look_end(k));
+            const uint32_t e = fqdwave::group_min<kGroup>(fqdumi::look_end(k));
             const uint32_t own = live ? uint32_t(__builtin_popcount(colons_below(k, e))) : 0u;
-            uint32_t inc = own;
-#pragma unroll
-            for (int d = 1; d < int(kGroup); d <<= 1) { const uint32_t up = __shfl_up(inc, d, int(kGroup)); if (int(gl) >= d) inc += up; }
+            const uint32_t inc = fqdwave::wave_inclusive<uint32_t, kGroup>(own);
             Colons got{0u, {kNone, kNone, kNone, kNone}, false};
             if (live && own) got = lane_colons(line, k, e, colons + inc - own);
 #pragma unroll
-            for (int f = 0; f < 4; ++f) { const uint32_t at = group_min(got.at[f]); if (c[f] == kNone) c[f] = at; }
-            empty |= group_or(got.empty ? 1u : 0u);
+            for (int f = 0; f < 4; ++f) { const uint32_t at = fqdwave::group_min<kGroup>(got.at[f]); if (c[f] == kNone) c[f] = at; }
+            empty |= fqdwave::group_or<kGroup>(got.empty ? 1u : 0u);
             colons += __shfl(inc, int(kGroup) - 1, int(kGroup));
             if (live) end = e;
         }
@@ -137,7 +110,7 @@ void read_places_kernel(const uint8_t* __restrict__ text, const uint64_t* __rest
         uint32_t differs = 0;
         if (p.reason == kOk)
             for (uint32_t b = 1u + gl; b <= c[0]; b += kGroup) differs |= surface_byte_same(line0, len0, line, b) ? 0u : 1u;
-        if (p.reason == kOk && !group_or(differs)) p.surface |= kSameSurface;
+        if (p.reason == kOk && !fqdwave::group_or<kGroup>(differs)) p.surface |= kSameSurface;
 
         const int from = int((lane & 3u) * kGroup);
         const uint32_t got_tile = __shfl(p.tile, from, 64), got_x = __shfl(p.x, from, 64), got_y = __shfl(p.y, from, 64);
@@ -151,8 +124,7 @@ void read_places_kernel(const uint8_t* __restrict__ text, const uint64_t* __rest
         if (my.reason) word = (static_cast<unsigned long long>(mine) << 3) | my.reason;
         else other = my.surface & kSameSurface ? 0u : 1u;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(word, d, 64); word = o < word ? o : word; }
+    word = fqdwave::wave_min(word);
     other = wave_sum(other);
     if (lane == 0) {
         if (word != kNoBad) atomicMin(&found->bad, word);
@@ -189,36 +161,9 @@ void head_count_kernel(const uint32_t* __restrict__ perm, const uint8_t* __restr
         bad += perm[k] >= n || (k == 0 && !h);
     }
     bad = wave_sum(bad);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if ((threadIdx.x & 63) == 0) { ws[threadIdx.x >> 6] = s; if (bad) atomicAdd(&counters->bad, static_cast<unsigned long long>(bad)); }
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-__global__ __launch_bounds__(kBlock)
-void head_write_kernel(const uint8_t* __restrict__ head, uint64_t n, uint64_t m, const unsigned long long* __restrict__ tile_start,
-                       uint32_t* __restrict__ head_place)
-{
-    __shared__ uint32_t ws[4];
-    const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
-    bool is_head[8];
-    uint32_t s = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); is_head[e] = k < n && head[k] != 0; s += is_head[e]; }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long at = tile_start[blockIdx.x] + inc - s;
-    for (uint32_t w = 0; w < wave; ++w) at += ws[w];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if (is_head[e] && at < m) head_place[at] = uint32_t(base + uint32_t(e));
-        at += is_head[e];
-    }
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&counters->bad, static_cast<unsigned long long>(bad));
+    s = fqdwave::block_total<4>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 // ---- classes -----------------------------------------------------------------------------------------------------------------
@@ -242,12 +187,7 @@ void classify_kernel(const uint32_t* __restrict__ head_place, const uint32_t* __
     const uint32_t cls = s == 0u ? 6u : s == 1u ? 5u : s <= kSmall ? 0u : s <= kWave ? 1u : s <= kBlockLimit ? 2u : s <= kMaxCluster ? 3u : 4u;
 #pragma unroll
     for (uint32_t t = 0; t < 4u; ++t) {
-        const unsigned long long mine = __ballot(cls == t);
-        if (!mine) continue;                                 // (the same for every lane)
-        const int leader = __ffsll(mine) - 1;
-        uint32_t at = 0;
-        if (int(lane) == leader) at = atomicAdd(&counters->listed[t], uint32_t(__popcll(mine)));
-        at = __shfl(at, leader, 64) + uint32_t(__popcll(mine & ((1ull << lane) - 1ull)));
+        const uint32_t at = fqdwave::ballot_append(cls == t, &counters->listed[t]);
         if (cls == t) lists.of[t][at] = (static_cast<unsigned long long>(k0) << 32) | s;
     }
     if (cls == 4u) atomicMin(&counters->over, (static_cast<unsigned long long>(perm[k0]) << 32) | s);
@@ -556,7 +496,7 @@ int fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
     FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
     FQD_TRY(e, hipMemsetAsync(&counters->over, 0xFF, sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(head_count_kernel, dim3(tiles), dim3(kBlock), 0, stream, perm, head, n, tile_sum, counters);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile_sum, tiles, d_total);
+    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile_sum, tiles, d_total);
     FQD_TRY(e, hipGetLastError());
     unsigned long long m = 0;
     Counters got{};

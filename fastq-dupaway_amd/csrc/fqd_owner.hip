@@ -13,6 +13,7 @@
 
 #include "fqd_internal.hpp"
 #include "fqd_owner_core.hpp"
+#include "fqd_wave.hpp"
 
 namespace {
 
@@ -28,8 +29,7 @@ void owners_kernel(const uint8_t* __restrict__ keep, const uint32_t* __restrict_
         owner[i] = o;
         bad += o == fqdowner::kBrokenChain;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) bad += __shfl_down(bad, d, 64);
+    bad = fqdwave::wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(broken, static_cast<unsigned long long>(bad));
 }
 
@@ -53,8 +53,7 @@ void group_heads_kernel(const uint64_t* __restrict__ key, const uint32_t* __rest
         head[k] = starts ? 1 : 0;
         heads += starts;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) heads += __shfl_down(heads, d, 64);
+    heads = fqdwave::wave_sum(heads);
     if ((threadIdx.x & 63) == 0 && heads) atomicAdd(n_heads, static_cast<unsigned long long>(heads));
 }
 

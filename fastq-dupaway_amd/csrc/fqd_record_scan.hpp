@@ -1,12 +1,17 @@
-// fqd_record_scan.hpp — where every record's packed bytes start: the three-step scan over the descriptors of one or two
-// mates that fqd_strand.hip and fqd_umi.hip share (record_bytes_kernel + u64_scan_kernel + record_offsets_kernel: kOffTile
-// records a block, one block over the block sums, kOffTile records a block again — the scan of fqd_output_plan).  A
-// record's bytes are len0 (+ len1 for S = 2); a mate that adds one fixed length to every record is a uniform Mate.
+// fqd_record_scan.hpp — the three-launch scan of the HIP units: kOffTile elements a block for the tiles' sums, ONE block
+// over the tile sums (scan_tiles_kernel, the only one-block scan of the library), kOffTile elements a block again for every
+// element's start — the scan of fqd_output_plan.  Here with it: where every record's packed bytes start, over the
+// descriptors of one or two mates (record_bytes_kernel + scan_tiles_kernel + record_offsets_kernel, fqd_strand.hip and
+// fqd_umi.hip; a record's bytes are len0 (+ len1 for S = 2), and a mate that adds one fixed length to every record is a
+// uniform Mate), and the places of the set flags of a byte array (head_write_kernel, behind a unit's own count of them).
+// The reductions and placements inside a block are fqd_wave.hpp's block_total and block_exclusive.
 // Internal to the library's HIP units; every kernel has internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "fqd_wave.hpp"
 
 namespace fqdscan {
 namespace {
@@ -19,6 +24,13 @@ struct Mate { const uint8_t* bases; const uint64_t* offsets; const uint32_t* len
 __device__ __forceinline__ uint64_t mate_off(const Mate& m, uint64_t i) { return m.offsets ? m.offsets[i] : i * uint64_t(m.ustride); }
 __device__ __forceinline__ uint32_t mate_len(const Mate& m, uint64_t i) { return m.lengths ? m.lengths[i] : m.ulen; }
 
+// A record's bytes.
+template <int S>
+__device__ __forceinline__ uint64_t record_len(const Mate& m0, const Mate& m1, uint64_t k)
+{
+    return uint64_t(mate_len(m0, k)) + (S == 2 ? mate_len(m1, k) : 0u);
+}
+
 template <int S>
 __global__ __launch_bounds__(kBlock)
 void record_bytes_kernel(Mate m0, Mate m1, uint64_t n, unsigned long long* __restrict__ tile_sum)
@@ -27,42 +39,35 @@ void record_bytes_kernel(Mate m0, Mate m1, uint64_t n, unsigned long long* __res
     const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
     unsigned long long s = 0;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint64_t k = base + uint32_t(e);
-        if (k < n) s += uint64_t(mate_len(m0, k)) + (S == 2 ? mate_len(m1, k) : 0u);
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); if (k < n) s += record_len<S>(m0, m1, k); }
+    s = fqdwave::block_total<4>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
-// (the scan of fqd_output_plan: exclusive, in place, by one block; *total = the sum)
-__global__ __launch_bounds__(1024)
-void u64_scan_kernel(unsigned long long* __restrict__ data, uint32_t n, unsigned long long* __restrict__ total)
+// The exclusive scan of data[0 .. n) in place by ONE block of 1024; every thread gets the sum back.  It brings its own LDS
+// (16 words of T, a copy per kernel that calls it): scan_tiles_kernel and fqd_join.hip's radix_rowscan_kernel.
+template <typename T>
+__device__ __forceinline__ T scan_in_place(T* __restrict__ data, uint32_t n)
 {
-    __shared__ unsigned long long wt[16];
-    __shared__ unsigned long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    __shared__ T ws[16];
+    T carry = 0;                                             // (the same in every thread)
     for (uint32_t t0 = 0; t0 < n; t0 += 1024u) {
         const uint32_t i = t0 + threadIdx.x;
-        const unsigned long long v = i < n ? data[i] : 0ull;
-        unsigned long long inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-        if (lane == 63u) wt[wave] = inc;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (uint32_t w = 0; w < wave; ++w) before += wt[w];
-        if (i < n) data[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry = before + inc;
-        __syncthreads();
+        T total;
+        const T before = fqdwave::block_exclusive<16, T>(i < n ? data[i] : T(0), ws, total);
+        if (i < n) data[i] = carry + before;
+        carry += total;
     }
-    if (threadIdx.x == 0) *total = carry;
+    return carry;
+}
+
+// (the scan of fqd_output_plan: the tile sums, 32 or 64 bits wide, become the tiles' starts; *total = the sum)
+template <typename T>
+__global__ __launch_bounds__(1024)
+void scan_tiles_kernel(T* __restrict__ data, uint32_t n, unsigned long long* __restrict__ total)
+{
+    const T sum = scan_in_place(data, n);
+    if (threadIdx.x == 0) *total = sum;
 }
 
 template <int S>
@@ -73,23 +78,33 @@ void record_offsets_kernel(Mate m0, Mate m1, uint64_t n, const unsigned long lon
     __shared__ unsigned long long ws[4];
     const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
     uint64_t L[8];
-    unsigned long long s = 0;
+    unsigned long long s = 0, total;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint64_t k = base + uint32_t(e);
-        L[e] = k < n ? uint64_t(mate_len(m0, k)) + (S == 2 ? mate_len(m1, k) : 0u) : 0u;
-        s += L[e];
-    }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned long long inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long at = tile_start[blockIdx.x] + inc - s;
-    for (uint32_t w = 0; w < wave; ++w) at += ws[w];
+    for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); L[e] = k < n ? record_len<S>(m0, m1, k) : 0u; s += L[e]; }
+    unsigned long long at = tile_start[blockIdx.x] + fqdwave::block_exclusive<4>(s, ws, total);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); if (k < n) { rec_off[k] = at; at += L[e]; } }
+}
+
+// Compaction of byte flags by the same scan (a count of the flags a tile into tile_start, scan_tiles_kernel, then this):
+// head_place[j] = the place of the j-th set flag of head[0 .. n), for j < m.  Used by fqd_optical.hip and
+// fqd_consensus.hip; the other units that include this header do not launch it, hence [[maybe_unused]].
+[[maybe_unused]] __global__ __launch_bounds__(kBlock)
+void head_write_kernel(const uint8_t* __restrict__ head, uint64_t n, uint64_t m, const unsigned long long* __restrict__ tile_start,
+                       uint32_t* __restrict__ head_place)
+{
+    __shared__ uint32_t ws[4];
+    const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
+    bool is_head[8];
+    uint32_t s = 0, total;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); is_head[e] = k < n && head[k] != 0; s += is_head[e]; }
+    unsigned long long at = tile_start[blockIdx.x] + fqdwave::block_exclusive<4>(s, ws, total);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if (is_head[e] && at < m) head_place[at] = uint32_t(base + uint32_t(e));
+        at += is_head[e];
+    }
 }
 
 } // namespace

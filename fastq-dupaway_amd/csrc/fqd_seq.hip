@@ -30,12 +30,16 @@
 #include <cstring>
 
 #include "fqd_internal.hpp"
+#include "fqd_record_scan.hpp"
 #include "fqd_seq_core.hpp"
 #include "fqd_seq_range_core.hpp"
 
 namespace {
 
 using fqdseq::View;
+using fqdwave::block_exclusive;
+using fqdwave::wave_max;
+using fqdwave::wave_sum;
 
 constexpr int kBlock = 256;
 
@@ -84,8 +88,7 @@ void census_kernel(Mates m, uint64_t n, uint32_t* __restrict__ info)
         census_bytes(a, lb);
         if (m.b2) { const View b = m.m2(uint32_t(i)); mx2 = max(mx2, b.len); census_bytes(b, lb); }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { mx1 = max(mx1, __shfl_down(mx1, d, 64)); mx2 = max(mx2, __shfl_down(mx2, d, 64)); }
+    mx1 = wave_max(mx1); mx2 = wave_max(mx2);
     if ((threadIdx.x & 63) == 0) { atomicMax(&info[8], mx1); atomicMax(&info[9], mx2); }
     __syncthreads();
     if (threadIdx.x < 8 && lb[threadIdx.x]) atomicOr(&info[threadIdx.x], lb[threadIdx.x]);
@@ -140,24 +143,10 @@ void diff_kernel(Mates m, const uint32_t* __restrict__ q, const uint8_t* __restr
         diff[j] = !bnd[j] && !m.equal(q[j - 1], q[j]);
 }
 
-// Exclusive scan of byte flags: tile sums, one block over the tiles, then every element.
+// Exclusive scan of byte flags: tile sums, one block over the tiles (fqd_record_scan.hpp's scan_tiles_kernel), then every
+// element; inside a block, fqd_wave.hpp's block_exclusive.
 constexpr uint32_t kScanPer = 16;
 constexpr uint32_t kScanTile = kBlock * kScanPer;        // 4096
-
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* ws, uint32_t& total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t k = 0; k < wave; ++k) before += ws[k];
-    total = ws[0] + ws[1] + ws[2] + ws[3];
-    __syncthreads();
-    return before + inc - v;
-}
 
 __global__ __launch_bounds__(kBlock)
 void tile_sum_kernel(const uint8_t* __restrict__ f, uint64_t count, uint32_t* __restrict__ tile_sum)
@@ -166,34 +155,8 @@ void tile_sum_kernel(const uint8_t* __restrict__ f, uint64_t count, uint32_t* __
     const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
     uint32_t s = 0;
     for (uint32_t e = 0; e < kScanPer; ++e) s += base + e < count ? (f[base + e] ? 1u : 0u) : 0u;
-    uint32_t total = 0;
-    (void)block_exclusive(s, ws, total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024)
-void tile_scan_kernel(uint32_t* __restrict__ tile_sum, uint32_t tiles, uint32_t* __restrict__ total)
-{
-    __shared__ uint32_t wave_tot[16];
-    __shared__ uint32_t carry_s;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (uint32_t c0 = 0; c0 < tiles; c0 += 1024u) {
-        const uint32_t i = c0 + threadIdx.x;
-        const uint32_t v = i < tiles ? tile_sum[i] : 0u;
-        uint32_t inc = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(threadIdx.x & 63u) >= d) inc += up; }
-        if ((threadIdx.x & 63u) == 63u) wave_tot[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        uint32_t before = carry_s;
-        for (uint32_t k = 0; k < (threadIdx.x >> 6); ++k) before += wave_tot[k];
-        if (i < tiles) tile_sum[i] = before + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023u) carry_s = before + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry_s;
+    s = fqdwave::block_total<4>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -204,7 +167,7 @@ void tile_apply_kernel(const uint8_t* __restrict__ f, uint64_t count, const uint
     uint32_t s = 0;
     for (uint32_t e = 0; e < kScanPer; ++e) s += base + e < count ? (f[base + e] ? 1u : 0u) : 0u;
     uint32_t total = 0;
-    uint32_t at = tile_base[blockIdx.x] + block_exclusive(s, ws, total);
+    uint32_t at = tile_base[blockIdx.x] + block_exclusive<4>(s, ws, total);
     for (uint32_t e = 0; e < kScanPer; ++e)
         if (base + e < count) { excl[base + e] = at; at += f[base + e] ? 1u : 0u; }
 }
@@ -330,15 +293,15 @@ void count_kernel(const uint8_t* __restrict__ f, uint64_t n, unsigned long long*
 {
     unsigned long long s = 0;
     for (uint64_t k = blockIdx.x * uint64_t(kBlock) + threadIdx.x; k < n; k += uint64_t(gridDim.x) * kBlock) s += f[k] ? 1u : 0u;
-#pragma unroll
-    for (int dd = 32; dd > 0; dd >>= 1) s += __shfl_down(s, dd, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(total, s);
 }
 
 // ---------------------------------------------------------------------------------------------
 struct SortBuffers {
     uint64_t* keys[2]; uint32_t* vals[2]; uint32_t *counts, *tot;
-    uint32_t *q, *pos, *nq, *npos, *nrid, *bnd_excl, *keep_excl, *tiles, *total;
+    uint32_t *q, *pos, *nq, *npos, *nrid, *bnd_excl, *keep_excl, *tiles;
+    unsigned long long* total;
     uint8_t *bnd, *diff, *mixed, *keep, *rank;
     uint64_t* word;
 };
@@ -352,7 +315,7 @@ void carve(uint64_t n, SortBuffers& b, char* base, size_t* bytes)
     b.counts = c.take<uint32_t>(fqd_internal_radix_counts(n)); b.tot = c.take<uint32_t>(256);
     b.q = c.take<uint32_t>(n); b.pos = c.take<uint32_t>(n); b.nq = c.take<uint32_t>(n); b.npos = c.take<uint32_t>(n);
     b.nrid = c.take<uint32_t>(n); b.bnd_excl = c.take<uint32_t>(n); b.keep_excl = c.take<uint32_t>(n);
-    b.tiles = c.take<uint32_t>(tiles); b.total = c.take<uint32_t>(64);
+    b.tiles = c.take<uint32_t>(tiles); b.total = c.take<unsigned long long>(32);
     b.bnd = c.take<uint8_t>(n); b.diff = c.take<uint8_t>(n); b.mixed = c.take<uint8_t>(n); b.keep = c.take<uint8_t>(n);
     b.rank = c.take<uint8_t>(256);
     b.word = c.take<uint64_t>(n);
@@ -364,12 +327,14 @@ int exclusive_scan(fqd_engine* e, hipStream_t s, const uint8_t* f, uint64_t coun
 {
     const uint32_t tiles = uint32_t((count + kScanTile - 1) / kScanTile);
     hipLaunchKernelGGL(tile_sum_kernel, dim3(tiles), dim3(kBlock), 0, s, f, count, b.tiles);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, s, b.tiles, tiles, b.total);
+    hipLaunchKernelGGL(fqdscan::scan_tiles_kernel<uint32_t>, dim3(1), dim3(1024), 0, s, b.tiles, tiles, b.total);
     hipLaunchKernelGGL(tile_apply_kernel, dim3(tiles), dim3(kBlock), 0, s, f, count, static_cast<const uint32_t*>(b.tiles), excl);
     FQD_TRY(e, hipGetLastError());
     if (total) {
-        FQD_TRY(e, hipMemcpyAsync(total, b.total, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        unsigned long long all = 0;                          // (at most count, which fits 32 bits)
+        FQD_TRY(e, hipMemcpyAsync(&all, b.total, sizeof(all), hipMemcpyDeviceToHost, s));
         FQD_TRY(e, hipStreamSynchronize(s));
+        *total = uint32_t(all);
     }
     return FQD_OK;
 }
@@ -577,10 +542,7 @@ void prefix_keys_kernel(Mates m, const uint32_t* __restrict__ size1, const uint3
             if (bytes) { const uint64_t all = sz + (accumulate ? bytes[i] : 0u); bytes[i] = all > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(all); }
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        mx1 = max(mx1, __shfl_down(mx1, d, 64)); mx2 = max(mx2, __shfl_down(mx2, d, 64)); sum += __shfl_down(sum, d, 64);
-    }
+    mx1 = wave_max(mx1); mx2 = wave_max(mx2); sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) {
         if (mx1) atomicMax(&info[kInfoLongest1], (unsigned long long)mx1);
         if (mx2) atomicMax(&info[kInfoLongest2], (unsigned long long)mx2);
@@ -595,21 +557,6 @@ void fill_u64_kernel(unsigned long long* __restrict__ p, uint32_t n, unsigned lo
 }
 
 // ---- the plan: exclusive scan of uint32 values in 64 bits (tile sums, one block over the tiles, every element) ------------
-__device__ __forceinline__ unsigned long long block_exclusive64(unsigned long long v, unsigned long long* ws, unsigned long long& total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0;
-    for (uint32_t k = 0; k < wave; ++k) before += ws[k];
-    total = ws[0] + ws[1] + ws[2] + ws[3];
-    __syncthreads();
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(kBlock)
 void bytes_tile_sum_kernel(const uint32_t* __restrict__ v, uint64_t n, unsigned long long* __restrict__ tile_sum)
 {
@@ -617,9 +564,8 @@ void bytes_tile_sum_kernel(const uint32_t* __restrict__ v, uint64_t n, unsigned 
     const uint64_t base = uint64_t(blockIdx.x) * kScanTile + uint64_t(threadIdx.x) * kScanPer;
     unsigned long long s = 0;
     for (uint32_t e = 0; e < kScanPer; ++e) s += base + e < n ? v[base + e] : 0u;
-    unsigned long long total = 0;
-    (void)block_exclusive64(s, ws, total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+    s = fqdwave::block_total<4>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 // One block: tile_sum[] becomes its exclusive scan, tile_sum[tiles] the total.
@@ -632,7 +578,7 @@ void bytes_tile_scan_kernel(unsigned long long* __restrict__ tile_sum, uint64_t 
         const uint64_t i = c0 + threadIdx.x;
         const unsigned long long v = i < tiles ? tile_sum[i] : 0ull;
         unsigned long long total = 0;
-        const unsigned long long ex = block_exclusive64(v, ws, total);
+        const unsigned long long ex = block_exclusive<4>(v, ws, total);
         if (i < tiles) tile_sum[i] = carry + ex;
         carry += total;
     }
@@ -648,7 +594,7 @@ void bytes_tile_apply_kernel(const uint32_t* __restrict__ v, uint64_t n, const u
     unsigned long long s = 0;
     for (uint32_t e = 0; e < kScanPer; ++e) s += base + e < n ? v[base + e] : 0u;
     unsigned long long total = 0;
-    unsigned long long at = tile_base[blockIdx.x] + block_exclusive64(s, ws, total);
+    unsigned long long at = tile_base[blockIdx.x] + block_exclusive<4>(s, ws, total);
     for (uint32_t e = 0; e < kScanPer; ++e)
         if (base + e < n) { prefix[base + e] = at; at += v[base + e]; }
 }

@@ -95,6 +95,8 @@ __device__ __forceinline__ Pick shfl_up_pick(Pick v, int d)
     return Pick{__shfl_up((unsigned long long)v.best, d, 64), __shfl_up(v.start, d, 64)};
 }
 
+// (A scan over fqdseq::combine, not a sum: it stays here.  fqd_wave.hpp's block_exclusive is for sums only — this one and
+// fqd_size.hip's are too few users for a helper over operation, identity and shuffle.)
 // The combined element of everything in the block BEFORE this lane (lanes in order), and the block's whole in `total`.
 __device__ __forceinline__ Pick block_exclusive_pick(Pick v, Pick* ws, Pick& total)
 {

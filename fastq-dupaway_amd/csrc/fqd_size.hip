@@ -19,6 +19,7 @@
 #include "fqd_internal.hpp"
 #include "fqd_size_core.hpp"
 #include "fqd_umi_core.hpp"
+#include "fqd_wave.hpp"
 
 namespace {
 
@@ -49,7 +50,8 @@ void size_tiles_kernel(const uint8_t* __restrict__ head, uint64_t n, uint32_t* _
     if (threadIdx.x == 0) tile_last[blockIdx.x] = fqdsize::combine(fqdsize::combine(ws[0], ws[1]), fqdsize::combine(ws[2], ws[3]));
 }
 
-// (u64_scan_kernel's shape with combine for the sum: exclusive, in place, by one block)
+// (scan_tiles_kernel's shape with combine for the sum: exclusive, in place, by one block.  fqd_wave.hpp's scans are sums only:
+// this one and fqd_seq_pick.hip's are the two over another operation, too few for a helper over operation and identity.)
 __global__ __launch_bounds__(1024)
 void size_carry_kernel(uint32_t* __restrict__ data, uint32_t n)
 {
@@ -74,13 +76,6 @@ void size_carry_kernel(uint32_t* __restrict__ data, uint32_t n)
         if (threadIdx.x == 1023u) carry = fqdsize::combine(before, inc);
         __syncthreads();
     }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                // (lane 0's is the wave's)
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -135,15 +130,14 @@ void size_places_kernel(const uint32_t* __restrict__ perm, const uint8_t* __rest
                 const bool mine = lv == L;
                 const unsigned long long m = __ballot(mine);
                 // the rows 1 .. 9 hold one size each; the others take the sum
-                const unsigned long long records = L < 9u ? uint64_t(__popcll(m)) * (L + 1u) : wave_sum(mine ? run : 0u);
+                const unsigned long long records = L < 9u ? uint64_t(__popcll(m)) * (L + 1u) : fqdwave::wave_sum<unsigned long long>(mine ? run : 0u);
                 if (lane == 0) { atomicAdd(&s_clusters[L], uint32_t(__popcll(m))); atomicAdd(&s_records[L], records); }
                 todo &= ~m;
             }
         }
     }
     if (!levels) return;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const uint32_t o = __shfl_down(largest, d, 64); largest = o > largest ? o : largest; }
+    largest = fqdwave::wave_max(largest);
     if (lane == 0 && largest) atomicMax(&s_largest, largest);
     __syncthreads();
     if (threadIdx.x < fqdsize::kLevels && s_clusters[threadIdx.x]) {
@@ -154,13 +148,6 @@ void size_places_kernel(const uint32_t* __restrict__ perm, const uint8_t* __rest
 }
 
 // ---- labels ----------------------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ uint32_t group_min(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) { const uint32_t o = __shfl_xor(v, d, int(kGroup)); v = o < v ? o : v; }
-    return v;
-}
 
 // One wave per tile of kWaveTile records; see the head of the file.
 __global__ __launch_bounds__(kBlock)
@@ -186,7 +173,7 @@ void size_labels_kernel(const uint8_t* __restrict__ text, const uint64_t* __rest
             const bool live = end == fqdumi::kNone && c0 < chunks;
             fqdumi::Look k{0u, 0u, 0u};
             if (live) k = fqdumi::lane_look(line, L, uint8_t(' '), c0, gl);     // (the separator masks are not looked at)
-            const uint32_t e = group_min(fqdumi::look_end(k));
+            const uint32_t e = fqdwave::group_min<kGroup>(fqdumi::look_end(k));
             if (live) end = e;
         }
         if (end == fqdumi::kNone) end = L;                   // no word end in the line: the word ends with it
@@ -201,8 +188,7 @@ void size_labels_kernel(const uint8_t* __restrict__ text, const uint64_t* __rest
         out_size[mine] = rec_size[mine] + (kept ? fqdsize::label_len(N) : 0u);
         bad = kept && N == 0u;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) bad += __shfl_down(bad, d, 64);
+    bad = fqdwave::wave_sum(bad);
     if (lane == 0 && bad) atomicAdd(n_bad, static_cast<unsigned long long>(bad));
 }
 

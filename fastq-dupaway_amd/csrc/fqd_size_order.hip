@@ -7,7 +7,7 @@
 //            where both pointers allow it), the three counters summed wave by wave, then over the block's four waves in LDS:
 //            three global atomics a block, none per record.  Only a lane that clears a flag stores.
 //   order    the kept head places compacted into (key, record) pairs in place order — order_tiles_kernel (kOffTile places a
-//            block, one count a tile), fqd_record_scan.hpp's u64_scan_kernel (one block over the tile counts, exclusive; its
+//            block, one count a tile), fqd_record_scan.hpp's scan_tiles_kernel (one block over the tile counts, exclusive; its
 //            total is W), order_places_kernel (kOffTile places a block again; it also counts the clusters above 255 members
 //            and finds the largest) — then tier 1, one pass of fqd_internal_radix_sort over all W pairs by the size's digit,
 //            order_rekey_kernel over the L pairs of bucket 0, and tier 2, the passes of largest - 256 over those L alone.
@@ -29,12 +29,8 @@ constexpr int kOffTile = fqdscan::kOffTile;                  // places a block o
 struct FilterCounts { unsigned long long clusters, records, bad; };
 struct OrderStats { unsigned long long above, bad; uint32_t largest, reserved; };
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                // (lane 0's is the wave's)
-}
+using fqdwave::wave_max;
+using fqdwave::wave_sum;
 
 // ---- filter ----------------------------------------------------------------------------------------------------------------
 
@@ -72,6 +68,7 @@ void size_filter_kernel(const uint32_t* __restrict__ size, uint64_t n, uint32_t 
             for (int j = 0; j < 4; ++j) if ((cleared >> j) & 1u) keep[r0 + uint32_t(j)] = 0;   // (a cleared flag's record lies below n: its flag was loaded)
         }
     }
+    // (three sums behind ONE barrier, a thread an atomic: block_total would be a barrier a sum)
     clusters = wave_sum(clusters); records = wave_sum(records); bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0) { ws[0][threadIdx.x >> 6] = clusters; ws[1][threadIdx.x >> 6] = records; ws[2][threadIdx.x >> 6] = bad; }
     __syncthreads();
@@ -102,10 +99,8 @@ void order_tiles_kernel(const uint32_t* __restrict__ perm, const uint8_t* __rest
     unsigned long long c = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { uint32_t r = 0; c += kept_place(perm, head, keep, n, base + uint32_t(e), r) ? 1u : 0u; }
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    c = fqdwave::block_total<4>(c, ws);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -118,20 +113,13 @@ void order_places_kernel(const uint32_t* __restrict__ perm, const uint8_t* __res
     if (threadIdx.x == 0) { s_above = 0; s_bad = 0; s_largest = 0; }
     const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
     uint32_t rec[8];
-    uint32_t mask = 0, c = 0;
+    uint32_t mask = 0, c = 0, total;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         rec[e] = 0;
         if (kept_place(perm, head, keep, n, base + uint32_t(e), rec[e])) { mask |= 1u << e; ++c; }
     }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long at = tile_start[blockIdx.x] + inc - c;
-    for (uint32_t w = 0; w < wave; ++w) at += ws[w];
+    unsigned long long at = tile_start[blockIdx.x] + fqdwave::block_exclusive<4>(c, ws, total);   // (its barriers stand behind thread 0's stores above)
     uint32_t above = 0, bad = 0, largest = 0;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -143,14 +131,8 @@ void order_places_kernel(const uint32_t* __restrict__ perm, const uint8_t* __res
         bad += sz == 0u;
         largest = sz > largest ? sz : largest;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        above += __shfl_down(above, d, 64);
-        bad += __shfl_down(bad, d, 64);
-        const uint32_t o = __shfl_down(largest, d, 64);
-        largest = o > largest ? o : largest;
-    }
-    if (lane == 0) {
+    above = wave_sum(above); bad = wave_sum(bad); largest = wave_max(largest);
+    if ((threadIdx.x & 63) == 0) {
         if (above) atomicAdd(&s_above, above);
         if (bad) atomicAdd(&s_bad, bad);
         if (largest) atomicMax(&s_largest, largest);
@@ -279,7 +261,7 @@ int fqd_size_order_ex(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
     (void)carve_counts(tiles, static_cast<char*>(base), cb);
     FQD_TRY(e, hipMemsetAsync(cb.stats, 0, sizeof(OrderStats), s));
     hipLaunchKernelGGL(order_tiles_kernel, dim3(tiles), dim3(kBlock), 0, s, perm, head, keep, n, cb.tile);
-    hipLaunchKernelGGL(fqdscan::u64_scan_kernel, dim3(1), dim3(1024), 0, s, cb.tile, tiles, cb.total);
+    hipLaunchKernelGGL(fqdscan::scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, s, cb.tile, tiles, cb.total);
     FQD_TRY(e, hipGetLastError());
     unsigned long long w = 0;
     FQD_TRY(e, hipMemcpyAsync(&w, cb.total, sizeof w, hipMemcpyDeviceToHost, s));

@@ -21,6 +21,7 @@
 #include "fqd_size_core.hpp"
 #include "fqd_sizein_core.hpp"
 #include "fqd_umi_core.hpp"
+#include "fqd_wave.hpp"
 
 namespace {
 
@@ -41,33 +42,7 @@ static_assert(sizeof(Seg) == 16, "a tile value is sixteen bytes");
 
 struct Found { unsigned long long bad, annotated, extra; };  // the lowest (record << 3 | reason); records with an annotation; the sum of weight - 1
 
-__device__ __forceinline__ uint32_t group_min(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) { const uint32_t o = __shfl_xor(v, d, int(kGroup)); v = o < v ? o : v; }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t group_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) v += __shfl_xor(v, d, int(kGroup));
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long group_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) v += __shfl_xor(v, d, int(kGroup));
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                // (lane 0's is the wave's)
-}
+using fqdwave::wave_sum;
 
 // One wave per tile of kWaveTile records; see the head of the file.
 __global__ __launch_bounds__(kBlock)
@@ -95,10 +70,10 @@ void size_annotations_kernel(const uint8_t* __restrict__ text, const uint64_t* _
             const bool live = end == fqdumi::kNone && c0 < chunks;
             fqdumi::Look k{0u, 0u, 0u};
             if (live) k = fqdumi::lane_look(line, L, uint8_t(';'), c0, gl);
-            const uint32_t e = group_min(fqdumi::look_end(k));
+            const uint32_t e = fqdwave::group_min<kGroup>(fqdumi::look_end(k));
             fqdsizein::Cand c{kNone, 0u};
             if (live && k.seps) c = fqdsizein::lane_candidates(line, L, k, e);
-            const uint32_t f = group_min(c.first), many = group_sum(c.count);
+            const uint32_t f = fqdwave::group_min<kGroup>(c.first), many = fqdwave::group_sum<kGroup>(c.count);
             if (live) { end = e; if (first == kNone) first = f; count += many; }
         }
         if (end == fqdumi::kNone) end = L;                   // no word end in the line: the word ends with it
@@ -111,7 +86,7 @@ void size_annotations_kernel(const uint8_t* __restrict__ text, const uint64_t* _
         const uint32_t other_mask = uint32_t((__ballot(cls == fqdsizein::kOther) >> (kGroup * g)) & 0xFFFFull);
         const uint32_t nd = fqdsizein::digits_in_front(digit_mask);
         const uint32_t behind = (semi_mask >> nd) & 1u ? uint32_t(fqdsizein::kSemi) : (other_mask >> nd) & 1u ? uint32_t(fqdsizein::kOther) : uint32_t(fqdsizein::kBehind);
-        const unsigned long long value = group_sum64(fqdsizein::lane_value(digit, gl, nd));
+        const unsigned long long value = fqdwave::group_sum<kGroup, unsigned long long>(fqdsizein::lane_value(digit, gl, nd));
         const fqdsizein::Parsed p = fqdsizein::judge(count, first, end, nd, behind, value);
 
         const int from = int((lane & 3u) * kGroup);
@@ -128,8 +103,7 @@ void size_annotations_kernel(const uint8_t* __restrict__ text, const uint64_t* _
         if (my.reason) word = (static_cast<unsigned long long>(mine) << 3) | my.reason;
         else if (my.cut) { annotated = 1; extra = my.weight - 1u; }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(word, d, 64); word = o < word ? o : word; }
+    word = fqdwave::wave_min(word);
     annotated = wave_sum(annotated);
     extra = wave_sum(extra);
     if (lane == 0) {
@@ -150,7 +124,8 @@ __device__ __forceinline__ Seg seg_up(const Seg& v, int d)
     return o;
 }
 
-// The wave's inclusive combine: lane l holds combine(v(0), .., v(l)).
+// The wave's inclusive combine: lane l holds combine(v(0), .., v(l)).  (A scan over another operation than the sum, as
+// fqd_size.hip's and fqd_seq_pick.hip's: fqd_wave.hpp's scans are sums only.)
 __device__ __forceinline__ Seg wave_scan(Seg v, uint32_t lane)
 {
 #pragma unroll
@@ -272,23 +247,21 @@ void weight_places_kernel(const uint32_t* __restrict__ perm, const uint8_t* __re
                 const bool same = lv == L;
                 const unsigned long long m = __ballot(same);
                 // the rows 1 .. 9 hold one size each; the others take the sum
-                const unsigned long long records = L < 9u ? uint64_t(__popcll(m)) * (L + 1u) : wave_sum(same ? run : 0u);
+                const unsigned long long records = L < 9u ? uint64_t(__popcll(m)) * (L + 1u) : wave_sum<unsigned long long>(same ? run : 0u);
                 if (lane == 0) { atomicAdd(&s_clusters[L], uint32_t(__popcll(m))); atomicAdd(&s_records[L], records); }
                 todo &= ~m;
             }
         }
     }
     if (report) return;
-    const unsigned long long bad = wave_sum(zeros);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(over, d, 64); over = o < over ? o : over; }
+    const unsigned long long bad = wave_sum<unsigned long long>(zeros);
+    over = fqdwave::wave_min(over);
     if (lane == 0) {
         if (bad) atomicAdd(&out->n_bad, bad);
         if (over != kNoBad) atomicMin(&out->over_record, over);
     }
     if (!levels) return;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const uint32_t o = __shfl_down(largest, d, 64); largest = o > largest ? o : largest; }
+    largest = fqdwave::wave_max(largest);
     if (lane == 0 && largest) atomicMax(&s_largest, largest);
     __syncthreads();
     if (threadIdx.x < fqdsize::kLevels && s_clusters[threadIdx.x]) {

@@ -2,7 +2,7 @@
 // into the orientation it is keyed in, packed back to back, with descriptors the engine takes as they are.  Rule and
 // proofs: fqd_strand_core.hpp.
 //
-//   sizes    record_bytes_kernel + u64_scan_kernel + record_offsets_kernel (fqd_record_scan.hpp, shared with
+//   sizes    record_bytes_kernel + scan_tiles_kernel + record_offsets_kernel (fqd_record_scan.hpp, shared with
 //            fqd_umi.hip): where every record's canonical bytes start.  A record's bytes (len0 + len1) do not depend on its orientation, so the offsets are known before any base
 //            has been looked at: the three-step scan of fqd_output_plan (2048 records a block, one block over the
 //            block sums, 2048 records a block again).
@@ -35,7 +35,7 @@ using fqdscan::Mate;                                         // the descriptors 
 using fqdscan::mate_off;
 using fqdscan::mate_len;
 using fqdscan::record_bytes_kernel;
-using fqdscan::u64_scan_kernel;
+using fqdscan::scan_tiles_kernel;
 using fqdscan::record_offsets_kernel;
 
 // What a group's lanes found in one round, read off the wave's two ballots: has a lane of the group seen a difference,
@@ -102,9 +102,7 @@ void canon_kernel(Mate m0, Mate m1, uint64_t n, uint8_t* __restrict__ out, const
         out_len0[mine] = my_flip ? (S == 2 ? len_b : len_a) : len_a;
         if (S == 2) { out_off1[mine] = base + (my_flip ? len_b : len_a); out_len1[mine] = my_flip ? len_a : len_b; }
     }
-    uint32_t turned = my_flip;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) turned += __shfl_down(turned, d, 64);
+    const uint32_t turned = fqdwave::wave_sum(my_flip);
     if (lane == 0 && turned) atomicAdd(n_flipped, static_cast<unsigned long long>(turned));
 }
 
@@ -164,7 +162,7 @@ int fqd_canonical_reads(fqd_engine* e, const fqd_reads* seg, uint64_t n, uint8_t
     FQD_TRY(e, hipMemsetAsync(d_flipped, 0, sizeof(unsigned long long), stream));
     if (S == 1) hipLaunchKernelGGL(record_bytes_kernel<1>, dim3(tiles), dim3(kBlock), 0, stream, m0, m1, n, tile);
     else        hipLaunchKernelGGL(record_bytes_kernel<2>, dim3(tiles), dim3(kBlock), 0, stream, m0, m1, n, tile);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
+    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
     FQD_TRY(e, hipGetLastError());
     // the size of the output before a byte of it is written: known here for uniform reads, else read back from the scan
     // (one 8-byte copy the call waits for, as a ragged fqd_submit does for its key words)

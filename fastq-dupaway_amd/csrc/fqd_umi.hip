@@ -12,7 +12,7 @@
 //            compares it with record 0's shape, which a first launch over record 0 alone has left in scratch.  The
 //            lowest refused record and its reason come back through one 64-bit atomicMin a wave of (record << 3 | reason).
 //            Nothing is written besides umi_off and that word.
-//   sizes    record_bytes_kernel + u64_scan_kernel + record_offsets_kernel (fqd_record_scan.hpp, shared with
+//   sizes    record_bytes_kernel + scan_tiles_kernel + record_offsets_kernel (fqd_record_scan.hpp, shared with
 //            fqd_strand.hip): a record's bytes are Lb + len0, the Lb entering as a second, uniform "mate" of that length.
 //   pack     umi_pack_kernel: sixteen lanes a record again.  The Lb bases go one byte a lane through a table of their
 //            places in the field, passed by value: the shape is fixed, so taking the joiners out is a constant gather.
@@ -37,25 +37,11 @@ using fqdscan::Mate;
 using fqdscan::mate_off;
 using fqdscan::mate_len;
 using fqdscan::record_bytes_kernel;
-using fqdscan::u64_scan_kernel;
+using fqdscan::scan_tiles_kernel;
 using fqdscan::record_offsets_kernel;
 
 // What comes back from a find: the lowest (record << 3 | reason), and record 0's shape (ulen 0: record 0 is refused).
 struct Found { unsigned long long bad; unsigned long long joiners; uint32_t ulen, reserved; };
-
-__device__ __forceinline__ uint32_t group_min(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) { const uint32_t o = __shfl_xor(v, d, int(kGroup)); v = o < v ? o : v; }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t group_max(uint32_t v)
-{
-#pragma unroll
-    for (int d = 8; d > 0; d >>= 1) { const uint32_t o = __shfl_xor(v, d, int(kGroup)); v = o > v ? o : v; }
-    return v;
-}
 
 // One wave per tile of kWaveTile records; see the head of the file.  define_shape: the launch over record 0 alone that
 // leaves its shape in *found; every other launch compares with it.
@@ -86,8 +72,8 @@ void umi_find_kernel(const uint8_t* __restrict__ text, const uint64_t* __restric
             const bool live = end == fqdumi::kNone && c0 < chunks;
             fqdumi::Look k{0u, 0u, 0u};
             if (live) k = fqdumi::lane_look(line, L, uint8_t(sep), c0, gl);
-            const uint32_t e = group_min(fqdumi::look_end(k));
-            const uint32_t s = group_max(fqdumi::look_sep(k, e));
+            const uint32_t e = fqdwave::group_min<kGroup>(fqdumi::look_end(k));
+            const uint32_t s = fqdwave::group_max<kGroup>(fqdumi::look_sep(k, e));
             if (live) { end = e; if (s) sep1 = s; }
         }
         if (end == fqdumi::kNone) end = L;                   // no word end in the line: the word ends with it
@@ -115,8 +101,7 @@ void umi_find_kernel(const uint8_t* __restrict__ text, const uint64_t* __restric
         umi_off[mine] = my_off;
         if (my_reason) word = (static_cast<unsigned long long>(mine) << 3) | my_reason;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned long long o = __shfl_down(word, d, 64); word = o < word ? o : word; }
+    word = fqdwave::wave_min(word);
     if (lane == 0 && word != kNoBad) atomicMin(&found->bad, word);
 }
 
@@ -224,7 +209,7 @@ int fqd_umi_reads(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, 
     unsigned long long* tile = static_cast<unsigned long long*>(scratch);
     unsigned long long* d_total = tile + tiles;
     hipLaunchKernelGGL(record_bytes_kernel<2>, dim3(tiles), dim3(kBlock), 0, stream, m0, umi, n, tile);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
+    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
     FQD_TRY(e, hipGetLastError());
     // the size of the output before a byte of it is written: known here for uniform reads, else read back from the scan
     unsigned long long total = 0;

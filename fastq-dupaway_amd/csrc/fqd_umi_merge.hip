@@ -2,7 +2,7 @@
 // clusters of one sequence that differ in a base or two merged by UMI-tools' directional rule.  Rule and proofs:
 // fqd_umi_merge_core.hpp.
 //
-//   nodes    node_count_kernel + u64_scan_kernel + node_write_kernel (the three launches of fqd_record_scan.hpp's scan,
+//   nodes    node_count_kernel + scan_tiles_kernel + node_write_kernel (the three launches of fqd_record_scan.hpp's scan,
 //            kOffTile records a block): the records that own themselves in the exact grouping, compacted in input order as
 //            (key = their owner in the grouping by sequence, value = the record).  The count comes back to size the rest.
 //   group    fqd_internal_radix_sort over the bits of n - 1: stable, so the nodes of a sequence stand together in the order
@@ -38,7 +38,9 @@ constexpr unsigned long long kNoGroup = ~0ull;
 static_assert(kNodesPerThread * kMergeBlock == int(fqdmerge::kMaxGroup), "a block's threads share the largest group evenly");
 static_assert(fqdmerge::kWave == 64 && 64 % fqdmerge::kSmall == 0, "the lane kernels' groups tile a wave");
 
-using fqdscan::u64_scan_kernel;
+using fqdscan::scan_tiles_kernel;
+using fqdwave::wave_max;
+using fqdwave::wave_sum;
 
 // What the kernels count (one in scratch, zeroed per call).
 struct Counters {
@@ -48,20 +50,6 @@ struct Counters {
     uint32_t listed[3];                                      // groups on the small, wave and block lists
     uint32_t over_groups, largest, sweeps;
 };
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;                                                // (lane 0's is the wave's)
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const uint32_t o = __shfl_down(v, d, 64); v = o > v ? o : v; }
-    return v;
-}
 
 // ---- nodes -----------------------------------------------------------------------------------------------------------------
 
@@ -82,11 +70,9 @@ void node_count_kernel(const uint32_t* __restrict__ owner_exact, const uint32_t*
         else bad += o > k || owner_exact[o] != o || owner_seq[k] > k;    // (an owner is its cluster's first record: never behind it)
     }
     bad = wave_sum(bad);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_down(s, d, 64);
-    if ((threadIdx.x & 63) == 0) { ws[threadIdx.x >> 6] = s; if (bad) atomicAdd(&counters->bad, static_cast<unsigned long long>(bad)); }
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&counters->bad, static_cast<unsigned long long>(bad));
+    s = fqdwave::block_total<4>(s, ws);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -96,17 +82,10 @@ void node_write_kernel(const uint32_t* __restrict__ owner_exact, const uint32_t*
     __shared__ uint32_t ws[4];
     const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
     bool is_node[8];
-    uint32_t s = 0;
+    uint32_t s = 0, total;
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const uint64_t k = base + uint32_t(e); is_node[e] = k < n && owner_exact[k] == k; s += is_node[e]; }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t up = __shfl_up(inc, d, 64); if (int(lane) >= d) inc += up; }
-    if (lane == 63u) ws[wave] = inc;
-    __syncthreads();
-    unsigned long long at = tile_start[blockIdx.x] + inc - s;
-    for (uint32_t w = 0; w < wave; ++w) at += ws[w];
+    unsigned long long at = tile_start[blockIdx.x] + fqdwave::block_exclusive<4>(s, ws, total);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const uint64_t k = base + uint32_t(e);
@@ -159,12 +138,7 @@ void classify_kernel(const uint64_t* __restrict__ key, const uint32_t* __restric
     const uint32_t cls = s < 2u ? 3u : s <= fqdmerge::kSmall ? 0u : s <= fqdmerge::kWave ? 1u : s <= fqdmerge::kMaxGroup ? 2u : 4u;
 #pragma unroll
     for (uint32_t c = 0; c < 3u; ++c) {
-        const unsigned long long mine = __ballot(cls == c);
-        if (!mine) continue;                                 // (the same for every lane)
-        const int leader = __ffsll(mine) - 1;
-        uint32_t at = 0;
-        if (int(lane) == leader) at = atomicAdd(&counters->listed[c], uint32_t(__popcll(mine)));
-        at = __shfl(at, leader, 64) + uint32_t(__popcll(mine & ((1ull << lane) - 1ull)));
+        const uint32_t at = fqdwave::ballot_append(cls == c, &counters->listed[c]);
         if (cls == c) lists.of[c][at] = (static_cast<unsigned long long>(k) << 32) | s;
     }
     if (cls == 4u) { atomicMin(&counters->over, (static_cast<unsigned long long>(first[k]) << 32) | s); atomicAdd(&counters->over_groups, 1u); }
@@ -340,7 +314,7 @@ int fqd_umi_merge(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, 
     FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
     FQD_TRY(e, hipMemsetAsync(&counters->over, 0xFF, sizeof(unsigned long long), stream));
     hipLaunchKernelGGL(node_count_kernel, dim3(tiles), dim3(kBlock), 0, stream, owner_exact, owner_seq, size, n, tile, counters);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
+    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
     FQD_TRY(e, hipGetLastError());
     unsigned long long m = 0;
     Counters got{};

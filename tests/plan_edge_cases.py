@@ -1,6 +1,6 @@
 """Inputs and the numpy reference for fqd_output_offsets / fqd_output_plan / fqd_copy_spans (csrc/fqd_join.hip) at the
 edges of their units: a lane takes 8 entries, a tile is 2048 (kOffTile), the tile sums are scanned by one workgroup of
-1024 lanes (16 waves of 64 tiles) that loops over 1024 tiles at a time (u64_scan_kernel).  131 072 = 64 x 2048 entries
+1024 lanes (16 waves of 64 tiles) that loops over 1024 tiles at a time (scan_tiles_kernel).  131 072 = 64 x 2048 entries
 fill the first wave of that scan, 2 097 152 = 1024 x 2048 its first round.  numpy only, seeded; the reference is
 numpy's cumsum in uint64.  tests/test_edge_inputs.py holds the inputs to their claims, tests/test_gpu_plan_edges.py
 holds the kernels to the reference."""

@@ -135,6 +135,32 @@ def test_five_thousand_members_with_the_default_bounds():
     assert a == b
 
 
+def test_more_places_than_the_tile_scans_first_round():
+    """The one block that scans the head counts takes 1024 tiles of 2048 places a round: 1024 tiles, one tile and three places
+    more, of ten-byte records (`@`, two bases, `+`, two qualities).  Clusters of one but for a few of 3 to 5 members: at the
+    start, across the round's edge, in the tile behind it and across the last tile's edge.  ref.apply over the same text is the statement."""
+    n = 1024 * 2048 + 2048 + 3
+    rng = np.random.default_rng(8)
+    text = np.tile(np.frombuffer(b"@\nAC\n+\nII\n", np.uint8), n).reshape(n, 10)
+    runs = [(100, 3), (1024 * 2048 - 2, 5), (1024 * 2048 + 1000, 4), (n - 5, 5)]       # (the last one across the last tile's edge)
+    head = np.ones(n, np.uint8)
+    for at, m in runs:
+        head[at + 1:at + m] = 0
+        text[at:at + m, 2:4] = rng.choice(np.frombuffer(b"ACGTN", np.uint8), (m, 2))
+        text[at:at + m, 7:9] = rng.integers(33, 75, (m, 2))
+    text = np.concatenate([text.reshape(-1), np.full(32, 0xEE, np.uint8)])
+    start = np.arange(n, dtype=np.uint64) * np.uint64(10)
+    arrays = (start, np.full(n, 10, np.uint32), start + np.uint64(2), np.full(n, 2, np.uint32))
+    expect = bytearray(text.tobytes())
+    info = ref.apply(expect, *arrays, [list(range(at, at + m)) for at, m in runs])
+    assert info["clusters"] == 4 and info["bases_changed"] > 0
+    with Engine() as e:
+        got, said = call(e, text.tobytes(), arrays, np.arange(n, dtype=np.uint32), head)
+    assert got == bytes(expect)
+    assert (said.clusters, said.members, said.bases_changed, said.reads_changed, said.largest) == (
+        4, 17, info["bases_changed"], info["reads_changed"], 5)
+
+
 # ---- columns of one kind -----------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("copies", [1, 3, 22], ids=["as they are", "9 members at most", "66 members at most"])

@@ -27,7 +27,7 @@ Reached:
   from them in one bit, and lines of 64 .. 66 bytes whose first '.' lies in the last 8-byte word or behind it.
 
 Not reached: `radix_rowscan_kernel`'s second round of 1024 tiles needs more than 4 M records, `join_carry_scan_kernel`'s
-and `u32_scan_kernel`'s more than 2 M, and the grid loops of the histogram and the scatter (2048 blocks) more than 8 M.
+and `scan_tiles_kernel`'s more than 2 M, and the grid loops of the histogram and the scatter (2048 blocks) more than 8 M.
 Only test_gpu_join.py::test_join_at_50m_tags_per_side goes there; a list that fits a test of seconds does not take those
 paths, so nothing here stands in for them."""
 import numpy as np

@@ -259,6 +259,34 @@ def test_split_a_cluster_that_straddles_a_scan_tile(cap):
     assert set(owner[2030:2070].tolist()) == {2030}
 
 
+def test_split_more_places_than_the_tile_scans_first_round(cap):
+    """The one block that scans the head counts takes 1024 tiles of 2048 places a round: a grouping of 1024 tiles, one tile and
+    three places more.  Clusters of one, a chain across the round's edge and a grid at the end; the records share the ID
+    lines of one small file, which fqd_read_places has read."""
+    tile, n = 2048, 1024 * 2048 + 2048 + 3
+    rng = random.Random(56)
+    base = chain(30) + grid(4, 4, 3) + [(SURFACE, 1101, rng.randrange(10 ** 6), rng.randrange(10 ** 6)) for _ in range(15)]
+    pick = 46 + np.arange(n) % 15
+    owner = np.arange(n, dtype=np.uint32)
+    edge = 1024 * tile - 20
+    pick[edge:edge + 30], owner[edge:edge + 30] = np.arange(30), edge
+    pick[n - 16:], owner[n - 16:] = 30 + np.arange(16), n - 16
+    with Engine(segments=1) as e:
+        ids, arrays, _ = places_on_device(e, [id_line(*p) for p in base])
+        at = torch.from_numpy(pick).cuda()
+        big = [t[:len(base)][at].contiguous() for t in arrays]
+        exp_owner, exp_info = ref.split(owner, [base[p] for p in pick.tolist()], 10, cap)
+        perm, head = grouping(owner)
+        owner_out = torch.full((n + GUARD,), -1, dtype=torch.int32, device="cuda")
+        got = e.optical_split(dev(perm), dev(head), ids.text, ids.start[:len(base)][at].contiguous(), *big, n, 10, owner_out)
+        e.sync()
+    out = host(owner_out, np.uint32)
+    assert info_dict(got) == exp_info and exp_info["clusters_in"] == n - 29 - 15 and exp_info["split"] == 0
+    assert np.all(out[n:] == NONE32)
+    bad = np.nonzero(out[:n] != exp_owner)[0]
+    assert bad.size == 0, (bad[:10], out[bad[:10]], exp_owner[bad[:10]])
+
+
 def test_split_a_random_file_of_20000_records(cap):
     rng = random.Random(54)
     clusters = []

@@ -186,6 +186,18 @@ def test_tiles_without_a_kept_head(e):
     assert check_order(e, perm, head, size, keep) == [int(perm[starts[-1]])]
 
 
+def test_more_places_than_the_tile_scans_first_round(e):
+    """The one block that scans the tile counts takes 1024 tiles a round: 1024 tiles of places, one tile and three places more."""
+    n = 1024 * PLACE_TILE + PLACE_TILE + 3
+    rng = np.random.default_rng(7)
+    runs = rng.choice([1, 2, 3], n)
+    runs = runs[:int(np.searchsorted(np.cumsum(runs), n))]    # the longest prefix below n places, and one cluster for the rest
+    runs = np.append(runs, n - runs.sum())
+    perm, head, size, keep = grouping(rng, runs)
+    assert len(perm) == n and head[1024 * PLACE_TILE:].sum() > PLACE_TILE // 3
+    assert len(check_order(e, perm, head, size, keep)) == len(runs)
+
+
 def test_nothing_kept_leaves_the_order_untouched(e):
     rng = np.random.default_rng(6)
     perm, head, size, keep = grouping(rng, rng.choice([1, 2, 300], 500))

@@ -121,9 +121,9 @@ def test_record_counts_round_the_tiles(n, paired):
     canonical(mates, "gaps")
 
 
-def test_three_hundred_thousand_reads_of_150():
-    rng = np.random.default_rng(5)
-    n, L = 300_000, 150
+def uniform_single_end_reads(n, L, seed):
+    """n reads of L bases back to back through fqd_canonical_reads, against the statement by numpy (ref.canon_se_rows)."""
+    rng = np.random.default_rng(seed)
     a = rng.choice(np.frombuffer(b"ACGTN", np.uint8), size=(n, L), p=[.245, .245, .245, .245, .02])
     a[::7, L // 2:] = ref.rc_rows(a[::7, :L // 2])           # reads that are their own reverse complement among them
     rows, flip = ref.canon_se_rows(a)
@@ -142,6 +142,15 @@ def test_three_hundred_thousand_reads_of_150():
     assert np.all(host(ln, np.uint32) == L)
     assert np.array_equal(flipped.cpu().numpy(), flip)
     assert turned == int(flip.sum())
+
+
+def test_three_hundred_thousand_reads_of_150():
+    uniform_single_end_reads(300_000, 150, 5)
+
+
+def test_more_reads_than_the_tile_scans_first_round():
+    # the one block that scans the records' byte counts takes 1024 tiles of SCAN_TILE records a round: one tile and three reads more
+    uniform_single_end_reads(1024 * SCAN_TILE + SCAN_TILE + 3, 6, 6)
 
 
 @pytest.mark.parametrize("paired", [False, True], ids=["se", "pe"])

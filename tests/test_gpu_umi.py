@@ -362,6 +362,38 @@ def test_three_hundred_thousand_reads_keyed_by_umi_and_sequence():
     assert int(plain.sum()) < int(exp_keep.sum())             # a plain submit of the same reads keeps strictly fewer
 
 
+def test_more_reads_than_the_tile_scans_first_round():
+    """The one block that scans the records' byte counts takes 1024 tiles of 2048 records a round: 1024 tiles, one tile and
+    three records more, of the shortest lines and reads that numpy lays out (`@<7 digits>:<4 bases>`, reads of two bases)."""
+    rng = np.random.default_rng(20)
+    n, L, U = 1024 * SCAN_TILE + SCAN_TILE + 3, 2, 4
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    seq, umi = rng.choice(acgt, size=(n, L)), rng.choice(acgt, size=(n, U))
+    digits = (ord("0") + (np.arange(n)[:, None] // 10 ** np.arange(6, -1, -1)) % 10).astype(np.uint8)
+    lines = np.concatenate([np.full((n, 1), ord("@"), np.uint8), digits, np.full((n, 1), ord(":"), np.uint8), umi, np.full((n, 1), ord("\n"), np.uint8)], axis=1)
+    W, umi_at = lines.shape[1], 9
+    assert lines[n - 1].tobytes() == b"@%07d:" % (n - 1) + umi[n - 1].tobytes() + b"\n"
+    assert ref.umi_of(lines[n - 1].tobytes(), COLON) == (umi_at, umi[n - 1].tobytes())
+    text = dev(np.concatenate([lines.reshape(-1), np.full(PAD, FILL, np.uint8)]))
+    start, id_len = dev(np.arange(n, dtype=np.uint64) * np.uint64(W)), dev(np.full(n, W, np.uint32))
+    bases = dev(np.concatenate([seq.reshape(-1), np.full(PAD, FILL, np.uint8)]))
+    umi_off = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    out = torch.full((n * (U + L) + PAD,), FILL, dtype=torch.uint8, device="cuda")
+    off = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+    ln = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    with Engine(segments=1) as e:
+        info = e.umi_find(text, start, id_len, n, ":", umi_off)
+        assert info_tuple(info) == (U, U, 0, ref.NO_RECORD, ref.OK)
+        e.umi_reads(text, start, umi_off, info, Reads(bases, uniform_len=L, uniform_stride=L), n, out, off, ln, out_capacity=n * (U + L))
+        e.sync()
+    assert bool((umi_off == umi_at).all())
+    got = out.cpu().numpy()
+    assert np.array_equal(got[:n * (U + L)].reshape(n, U + L), np.concatenate([umi, seq], axis=1))
+    assert np.all(got[n * (U + L):] == FILL)
+    assert np.array_equal(host(off, np.uint64), np.arange(n, dtype=np.uint64) * np.uint64(U + L))
+    assert np.all(host(ln, np.uint32) == U + L)
+
+
 # ---------------------------------------------------------------- misuse
 
 def small_run():

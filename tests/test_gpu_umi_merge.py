@@ -178,6 +178,21 @@ def test_a_group_that_straddles_a_scan_tile(max_group):
     assert len(set(owner[2040:])) < 20 and all(int(o) >= 2040 for o in owner[2040:])
 
 
+def test_more_records_than_the_tile_scans_first_round(max_group):
+    """The one block that scans the node counts takes 1024 tiles of 2048 records a round: 1024 tiles, one tile and three
+    records more.  Most records repeat the UMI of their sequence group of 700, so that the statement has few nodes to walk; the
+    groups round the round's edge and the last one hold eight UMIs each, one and two bases apart."""
+    n = 1024 * 2048 + 2048 + 3
+    umis = [b"AAAA", b"AAAC", b"AACC", b"ACCC", b"CCCC", b"GGGG", b"GGGT", b"TTTT"]
+    fields, keys = [b"AAAA"] * n, [i // 700 for i in range(n)]
+    for g in (1024 * 2048 // 700 - 1, 1024 * 2048 // 700, 1024 * 2048 // 700 + 1, (n - 1) // 700):
+        for i in range(g * 700, min(n, g * 700 + 700)):
+            fields[i] = umis[(i * 7 // 50) % 8 if i % 3 else 0]
+    with Engine(segments=1) as e:
+        owner = merge_on_device(e, fields, keys, 1, max_group)
+    assert owner is not None and len(set(owner[1024 * 2048 - 700:1024 * 2048 + 700].tolist())) > 4
+
+
 def test_a_random_file_of_20000_records(max_group):
     rng = random.Random(97)
     seqs = [bytes(rng.choice(b"ACGT") for _ in range(10)) for _ in range(900)]

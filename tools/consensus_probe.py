@@ -90,7 +90,7 @@ def main():
     ap.add_argument("--no-cli", action="store_true")
     a = ap.parse_args()
     from fastq_dupaway_amd import _lib
-    reads, hit = near_probe.reads_with_errors(a.reads, a.distance, a.share)
+    reads, hit, _ = near_probe.reads_with_errors(a.reads, a.distance, a.share)
     print(f"input: {a.reads} reads of {L} bases, {hit} repeats with 1 .. {a.distance + 1} substituted bases", flush=True)
     through_the_binding(reads, a.distance, a.repeat)
     if a.no_cli:
