@@ -98,6 +98,12 @@ class ConsensusInfo(C.Structure):                            # fqd_consensus_inf
     _fields_ = [(name, C.c_uint64) for name in ("clusters", "members", "bases_changed", "reads_changed", "largest")]
 
 
+class CentroidInfo(C.Structure):                             # fqd_centroid_info
+    _fields_ = [("clusters", C.c_uint64), ("mixed", C.c_uint64), ("subclusters", C.c_uint64), ("tier_clusters", C.c_uint64 * 5),
+                ("largest", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CENTROID_BLOCK_LIMIT = 2048                                  # csrc/fqd_centroid_core.hpp: kBlockLimit
 NEAR_MAX_GROUP = 4096
 NEAR_WEAK_SEEDS = 1
 CONSENSUS_SMALL_TIERS = 1
@@ -211,6 +217,8 @@ def load_library():
     L.fqd_near_merge.argtypes = [vp, C.POINTER(ReadsDesc), vp, u64, u32, u32, vp, C.POINTER(NearInfo)]
     L.fqd_near_merge_umi.argtypes = [vp, C.POINTER(ReadsDesc), vp, vp, u64, u32, u32, vp, vp, vp, C.POINTER(UmiInfo), vp, C.POINTER(NearUmiInfo)]
     L.fqd_consensus.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, u32, vp, C.POINTER(ConsensusInfo)]
+    L.fqd_subcluster_sizes.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.POINTER(CentroidInfo)]
+    L.fqd_subcluster_scores.argtypes = [vp, vp, vp, vp, vp, u64, vp]
     L.fqd_cluster_sizes.argtypes = [vp, vp, vp, u64, vp, C.POINTER(SizeLevels)]
     L.fqd_size_labels.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp]
     L.fqd_copy_labelled.argtypes = [vp, vp, vp, vp, vp, vp, u64, vp, vp]

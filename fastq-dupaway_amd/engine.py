@@ -427,6 +427,23 @@ class Engine:
                                           self._p(seq_len), flags, self._p(changed), C.byref(got) if info else None))
         return got
 
+    # -- FQD_FAST_CENTROID=abundant (csrc/fqd_centroid.hip) ----------------------------------------------------
+    def subcluster_sizes(self, perm, head, label, n: int, abundance, weight=None, info: bool = True):
+        """abundance[r] (n uint32, device, by record) = the summed weight (weight: n uint32 by record, None: 1 each) of the
+        members of r's run of (perm, head) (group_owners') that share label[r], the exact owner; saturating at 2^32 - 1.
+        seq_pick_best over it puts every run's centroid at its head's place.  Returns the call's fqd_centroid_info
+        (_lib.CentroidInfo); info=False hands the library a null pointer and returns None."""
+        got = _lib.CentroidInfo() if info else None
+        self._check(self._L.fqd_subcluster_sizes(self._h, self._p(perm), self._p(head), self._p(label), self._p(weight), n, self._p(abundance),
+                                                 C.byref(got) if info else None))
+        return got
+
+    def subcluster_scores(self, perm, head, label, score, n: int, masked):
+        """Behind the centroid's pick: masked[r] (n uint32, device, by record) = min(score[r], 2^32 - 2) + 1 where label[r] is
+        the label of the record at the head place of r's run, 0 elsewhere.  A second seq_pick_best over it keeps the best
+        copy of the most abundant sequence."""
+        self._check(self._L.fqd_subcluster_scores(self._h, self._p(perm), self._p(head), self._p(label), self._p(score), n, self._p(masked)))
+
     # -- FQD_FAST_SIZEOUT / FQD_FAST_LEVELS (csrc/fqd_size.hip) --------------------------------------------
     def cluster_sizes(self, perm, head, n: int, size, levels: bool = True):
         """size[perm[k]] (n uint32, device) = the length of the run of (perm, head) that starts at place k where head[k], 0 at

@@ -70,6 +70,7 @@ FastModes FastModes::from_env()
     m.optical = pixel_distance("FQD_FAST_OPTICAL");
     m.hamming = uint32_t(choice("FQD_FAST_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
     m.umi_hamming = uint32_t(choice("FQD_FAST_UMI_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
+    m.centroid = choice("FQD_FAST_CENTROID", {"first", "abundant"}, "'first' or 'abundant'") == 1;
     m.consensus = is_on("FQD_FAST_CONSENSUS");
     return m;
 }
@@ -83,6 +84,7 @@ std::string FastModes::names() const
         {hamming != 0, hamming_name()},
         {optical != 0, optical_name()},
         {consensus, "FQD_FAST_CONSENSUS=1"},
+        {centroid, "FQD_FAST_CENTROID=abundant"},
         {size_out, "FQD_FAST_SIZEOUT=1"}, {levels, "FQD_FAST_LEVELS=1"}, {sort_by_size, "FQD_FAST_SORT=size"}, {size_in, "FQD_FAST_SIZEIN=1"},
         {min_size > 1, "FQD_FAST_MINSIZE=" + std::to_string(min_size)}, {max_size != 0, "FQD_FAST_MAXSIZE=" + std::to_string(max_size)}};
     std::string s;
@@ -115,6 +117,9 @@ void FastModes::check(bool unordered, size_t n_devices, Format format) const
     if (consensus && size_in)
         throw FastModeRefusal("FQD_FAST_CONSENSUS=1 with FQD_FAST_SIZEIN=1: a record that stands for several reads has lost the quality lines of the reads it stands "
                               "for, and the vote weighs every base by its quality");
+    if (centroid && !merges())
+        throw FastModeRefusal("FQD_FAST_CENTROID=abundant chooses among the different sequences of a merged cluster and nothing else: set one of FQD_FAST_UMI_MISMATCH, "
+                              "FQD_FAST_HAMMING or FQD_FAST_UMI_HAMMING as well, which merge them (without one every cluster holds one sequence)");
     if (unordered)
         throw FastModeRefusal(names() + " with --unordered: these modes run on ordered inputs only");
     if (n_devices > 1)
@@ -164,6 +169,9 @@ std::string FastModes::out_of_memory_note() const
     if (consensus)
         s += "; FQD_FAST_CONSENSUS takes, for paired files, 1 byte a record for the pairs it changed and, while it votes, 4 bytes a cluster and up to 5 bytes a "
              "record of scratch (the scratch of the grouping serves where it is as large)";
+    if (centroid)
+        s += "; FQD_FAST_CENTROID takes 4 bytes a record for the exact owners kept beside the merged ones and, while it chooses, 4 bytes a record for the "
+             "abundances, about 5 bytes a record of scratch and 32 bytes for every member of a cluster above 2048";
     return s;
 }
 

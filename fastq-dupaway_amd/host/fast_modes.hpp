@@ -1,4 +1,4 @@
-// fast_modes.hpp — the fifteen FQD_FAST_* switches of the `--fast` mode as one value: read from the environment in one place
+// fast_modes.hpp — the sixteen FQD_FAST_* switches of the `--fast` mode as one value: read from the environment in one place
 // (FastModes::from_env), checked against the command line before any GPU call (check), and asked by the run
 // (run_resident.cpp) through the predicates below.  Also the words of every refusal the switches can cause.
 // Plain C++: no HIP, nothing of run_common.hpp.
@@ -32,21 +32,22 @@ struct FastModes {
     uint32_t optical = 0;        // FQD_FAST_OPTICAL=D in 1 .. 2^31-1 (unset and 0: off): only the copies of a read within D pixels of each other on one tile of the flow cell, by the place in file 1's ID line, are duplicates (csrc/fqd_optical_core.hpp)
     uint32_t hamming = 0;        // FQD_FAST_HAMMING=D in 1 .. 3 (unset and 0: off): exact clusters of one shape whose sequences differ in at most D substituted bases a mate are one cluster, by single linkage; its first record is written (csrc/fqd_near_core.hpp)
     uint32_t umi_hamming = 0;    // FQD_FAST_UMI_HAMMING=D in 1 .. 3 (unset and 0: off; needs FQD_FAST_UMI): exact clusters under ONE UMI, of one shape, whose sequences differ in at most D substituted bases a mate are one molecule, by single linkage, together with FQD_FAST_UMI_MISMATCH's clusters; its first record is written (csrc/fqd_near_umi_core.hpp)
+    bool centroid = false;       // FQD_FAST_CENTROID=first|abundant: abundant: a merged cluster is written by the first copy of its most abundant exact sequence (UMI and sequence), not by its first record (csrc/fqd_centroid_core.hpp)
     bool consensus = false;      // FQD_FAST_CONSENSUS=1: the sequence and quality lines of every cluster's written member are replaced by the cluster's column-wise consensus (csrc/fqd_consensus_core.hpp)
 
-    // Reads the fifteen variables.  Throws std::runtime_error on a value that is none of the above, and FastModeRefusal for
+    // Reads the sixteen variables.  Throws std::runtime_error on a value that is none of the above, and FastModeRefusal for
     // a MAXSIZE below MINSIZE, in the order KEEP, SORT, MINSIZE, MAXSIZE, MAXSIZE below MINSIZE, STRAND, UMI, UMI_MISMATCH,
-    // OPTICAL, HAMMING, UMI_HAMMING.
+    // OPTICAL, HAMMING, UMI_HAMMING, CENTROID.
     static FastModes from_env();
     // What the values and the command line decide, before any GPU call; throws FastModeRefusal.  In this order: SIZEIN with
     // nothing that reads sizes, UMI_MISMATCH without UMI, HAMMING with STRAND=both, HAMMING with UMI, UMI_HAMMING without UMI,
-    // UMI_HAMMING with STRAND=both, CONSENSUS with STRAND=both, CONSENSUS with SIZEIN,
+    // UMI_HAMMING with STRAND=both, CONSENSUS with STRAND=both, CONSENSUS with SIZEIN, CENTROID=abundant with no merging switch,
     // `--unordered`, several devices, KEEP=best with FASTA, CONSENSUS with FASTA.
     void check(bool unordered, size_t n_devices, Format format) const;
 
     bool size_filter() const { return min_size > 1 || max_size != 0; }                 // a bound that can take a cluster out
     bool sized() const { return size_out || levels || sort_by_size || size_filter(); } // something reads the cluster sizes
-    bool linked() const { return keep_best || clusters || umi_mismatch || umi_hamming || optical || hamming || consensus || sized(); }   // the duplicates must be linked to their clusters
+    bool linked() const { return keep_best || clusters || umi_mismatch || umi_hamming || optical || hamming || consensus || centroid || sized(); }   // the duplicates must be linked to their clusters
     bool any() const { return linked() || both_strands || umi; }                       // only the GPU-resident ordered run will do
 
     // The switches that are set, as the messages name them: "FQD_FAST_KEEP=best and FQD_FAST_UMI=colon"; "" for none.
@@ -55,6 +56,7 @@ struct FastModes {
     std::string mismatch_name() const { return umi_mismatch ? "FQD_FAST_UMI_MISMATCH=" + std::to_string(umi_mismatch) : std::string(); }
     std::string hamming_name() const { return hamming ? "FQD_FAST_HAMMING=" + std::to_string(hamming) : std::string(); }
     std::string umi_hamming_name() const { return umi_hamming ? "FQD_FAST_UMI_HAMMING=" + std::to_string(umi_hamming) : std::string(); }
+    bool merges() const { return umi_mismatch || hamming || umi_hamming; }               // a cluster may hold several exact sequences
     std::string optical_name() const { return optical ? "FQD_FAST_OPTICAL=" + std::to_string(optical) : std::string(); }
     // What did not fit when the GPU-resident run meets the end of HBM, for the refusal.
     std::string out_of_memory_note() const;

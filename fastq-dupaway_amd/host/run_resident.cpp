@@ -71,10 +71,13 @@ struct KeyedReads {
 // Every duplicate's link to an earlier record of its key and the first record of the key, until the records are grouped.
 // FQD_FAST_UMI_HAMMING: where every record's UMI field lies and the run's shape, taken over from KeyedReads when that leaves, and
 // with FQD_FAST_UMI_MISMATCH the merged owners, which are the molecules' links while `owner` stays the exact owners.
-struct Links { Device<uint32_t> link, owner; Device<uint32_t> umi_off, umi_link; fqd_umi_info umi_info{}; };
+// FQD_FAST_CENTROID=abundant: `exact`, the owners by exact key, which the first stage that replaces them hands over instead of
+// letting them leave (4 bytes a record more); they go on to Clusters behind the last grouping.
+struct Links { Device<uint32_t> link, owner; Device<uint32_t> umi_off, umi_link, exact; fqd_umi_info umi_info{}; };
 // The records grouped by owner: an order of the n records and a flag at the first place of every cluster; with
 // FQD_FAST_SIZEIN what every record stands for, while sizes are made.  Until the outputs are planned.
-struct Clusters { Device<uint32_t> perm; Device<uint8_t> head; Device<uint32_t> weight; uint64_t count = 0; };
+// With FQD_FAST_CENTROID=abundant the exact owners, until the centroids are picked.
+struct Clusters { Device<uint32_t> perm; Device<uint8_t> head; Device<uint32_t> weight, exact; uint64_t count = 0; };
 // FQD_FAST_OPTICAL: where on the flow cell every record was read (fqd_read_places over file 1's ID lines), until the clusters
 // are split.
 struct Places {
@@ -95,6 +98,7 @@ struct OrderedResidentRun {
     uint64_t near_taken = 0;                                     // FQD_FAST_HAMMING: the exact clusters that went into another
     uint64_t umi_near_taken = 0;                                 // FQD_FAST_UMI_HAMMING: the clusters in front of the stage that went into another
     Places places; uint64_t optical_more = 0;                    // FQD_FAST_OPTICAL: the places; the clusters the split adds
+    uint64_t centroid_moved = 0;                                 // FQD_FAST_CENTROID=abundant: the clusters written by another sequence than their first member's
     uint64_t consensus_bases = 0, consensus_reads = 0;           // FQD_FAST_CONSENSUS: the bases replaced, and the records (pairs) that hold them
     std::string cluster_text[2];                                 // FQD_FAST_CLUSTERS
     Device<uint32_t> cluster_size; fqd_size_levels levels{};     // FQD_FAST_SIZEOUT / _LEVELS / _SORT / _MINSIZE / _MAXSIZE
@@ -278,7 +282,14 @@ struct OrderedResidentRun {
                       << merged.largest << ", " << merged.sweeps << " sweeps\n";
         merged_clusters = merged.nodes - merged.merged;
         if (fast.umi_hamming) links.umi_link.swap(merged_owner);     // (4 bytes a record more: the exact owners stay)
-        else links.owner.swap(merged_owner);                         // (the exact owners leave with this stage)
+        else { links.owner.swap(merged_owner); keep_exact(links, merged_owner); }   // (the exact owners leave with this stage, or stay for the centroids)
+    }
+
+    // FQD_FAST_CENTROID=abundant: `replaced` holds the owners a stage has just replaced.  Those of the FIRST stage that replaces any
+    // are the owners by exact key, and stay; a later stage's (the optical split behind a merge) are merged ones, and leave.
+    void keep_exact(Links& links, Device<uint32_t>& replaced)
+    {
+        if (fast.centroid && !links.exact.p) links.exact.swap(replaced);
     }
 
     // Stage 6: the duplicates are counted and, for the `linked` switches, the links resolved to the first record of every key
@@ -298,6 +309,7 @@ struct OrderedResidentRun {
         if (fast.umi_hamming) { merge_near_umi(links, clusters); dups = n - clusters.count; }
         if (fast.optical) { split_optical(links, clusters); dups = n - clusters.count; }
         if (clusters.count + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
+        if (fast.centroid) clusters.exact.swap(links.exact);         // (check() has seen to it that a merge ran)
     }
 
     // FQD_FAST_HAMMING, behind the grouping: fqd_near_merge makes of the exact clusters — the reads as they lie in the files, the
@@ -319,7 +331,8 @@ struct OrderedResidentRun {
                                       std::to_string(fast.hamming + 1) + " segments their first mate is cut into; a group of at most " + std::to_string(merged.max_group) +
                                       " is compared (adapter dimers, amplicons: trim the reads or dereplicate them exactly first)");
             if (merged.nodes != clusters.count) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
-            links.owner.swap(merged_owner);                          // (the owners by key leave with this stage)
+            links.owner.swap(merged_owner);                          // (the owners by key leave with this stage, or stay for the centroids)
+            keep_exact(links, merged_owner);
             engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
             engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
         }
@@ -355,7 +368,8 @@ struct OrderedResidentRun {
                                       std::to_string(merged.near.max_group) + " is compared (adapter dimers, amplicons: trim the reads, or run without the switch)");
             if (merged.near.nodes != clusters.count) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
             if (merged.near.nodes - merged.links != before) throw DeviceError("GPU engine: internal error (the links and the merged UMI clusters differ in number)");
-            links.owner.swap(merged_owner);                          // (the exact owners leave with this stage)
+            links.owner.swap(merged_owner);                          // (the exact owners leave with this stage, or stay for the centroids)
+            keep_exact(links, merged_owner);
             links.umi_link.release(); links.umi_off.release();
             engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
             engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
@@ -386,6 +400,7 @@ struct OrderedResidentRun {
                                       " is split (untrimmed poly-G and the like: trim the reads first)");
             if (split.clusters_in != clusters.count) throw DeviceError("GPU engine: internal error (the split and the grouping count different clusters)");
             links.owner.swap(split_owner);                           // (the owners by key leave with this stage)
+            keep_exact(links, split_owner);                          // (behind a merge: its exact owners are held already)
             engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
             engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
         }
@@ -431,14 +446,50 @@ struct OrderedResidentRun {
                       << " bases in " << consensus_reads << (S == 1 ? " reads" : " read pairs") << " replaced\n";
     }
 
-    // ... then, while perm and head exist: FQD_FAST_KEEP=best moves the keep flag of every cluster to its best member
+    // FQD_FAST_CENTROID=abundant, in front of everything that reads which member is written: fqd_subcluster_sizes gives every record
+    // the weight of its exact key's copies inside its cluster, fqd_seq_pick_best over them puts the first copy of the most
+    // abundant at the head's place.  With FQD_FAST_KEEP=best the scores are then masked to that sequence's copies
+    // (fqd_subcluster_scores) and picked from in place of the pick over the whole cluster.  The exact owners and the
+    // abundances leave with this stage.
+    void pick_centroids(Clusters& c)
+    {
+        fqd_centroid_info found{};
+        {
+            StageClock::Scope t("fast: most abundant sequence on the GPU");
+            Device<uint32_t> abundance;
+            abundance.reserve(n);
+            engine_ok<DeviceError>(e, fqd_subcluster_sizes(e, c.perm.p, c.head.p, c.exact.p, fast.size_in ? c.weight.p : nullptr, n, abundance.p, &found));
+            engine_ok<DeviceError>(e, fqd_seq_pick_best(e, abundance.p, c.head.p, n, c.perm.p, &centroid_moved));
+        }
+        if (StageClock::on())
+            std::cerr << "fast: most abundant sequence, " << centroid_moved << " of " << c.count << " clusters changed, " << found.mixed << " mixed clusters, " << found.subclusters
+                      << " sub-clusters, largest cluster " << found.largest << "\n";
+        if (fast.keep_best) {
+            StageClock::Scope t("fast: best-quality pick on the GPU");
+            fqd_tags recs[2];
+            for (int s = 0; s < S; ++s) recs[s] = fqd_tags{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].start.p, dev[s].size.p, n};
+            Device<uint32_t> score, masked;
+            score.reserve(n); masked.reserve(n);
+            uint64_t moved = 0;
+            engine_ok<DeviceError>(e, fqd_seq_scores(e, &recs[0], S == 2 ? &recs[1] : nullptr, score.p));
+            engine_ok<DeviceError>(e, fqd_subcluster_scores(e, c.perm.p, c.head.p, c.exact.p, score.p, n, masked.p));
+            engine_ok<DeviceError>(e, fqd_seq_pick_best(e, masked.p, c.head.p, n, c.perm.p, &moved));
+            if (StageClock::on()) std::cerr << "fast: best-quality pick, " << moved << " of " << c.count << " clusters changed\n";
+        }
+        c.exact.release();
+        engine_ok<DeviceError>(e, fqd_heads_to_keep(e, c.perm.p, c.head.p, n, keep.p));
+    }
+
+    // ... then, while perm and head exist: FQD_FAST_CENTROID=abundant picks the centroids (pick_centroids, which does
+    // FQD_FAST_KEEP=best's part as well); otherwise FQD_FAST_KEEP=best moves the keep flag of every cluster to its best member
     // (pick_best_members, fqd_heads_to_keep); FQD_FAST_CONSENSUS votes (vote_consensus); FQD_FAST_CLUSTERS takes the clusters' ID lines; the sizes are made for whatever
     // reads them (FastModes::sized), and the weights released behind them; fqd_size_filter clears the flags of the clusters
     // outside the bounds — behind the cluster files and the level table, which hold all clusters; fqd_size_order writes the
     // records that stay in order of decreasing cluster size.  The sizes stay for the writer with FQD_FAST_SIZEOUT only.
     void pick_size_filter_order(Clusters& c)
     {
-        if (fast.keep_best) {
+        if (fast.centroid) pick_centroids(c);
+        else if (fast.keep_best) {
             const uint64_t moved = pick_best_members(e, S, files, n, c.head.p, c.perm.p, "fast: best-quality pick on the GPU");
             engine_ok<DeviceError>(e, fqd_heads_to_keep(e, c.perm.p, c.head.p, n, keep.p));
             if (StageClock::on()) std::cerr << "fast: best-quality pick, " << moved << " of " << c.count << " clusters changed\n";
@@ -511,7 +562,7 @@ struct OrderedResidentRun {
 
 } // namespace
 
-// Everything about the fifteen switches that their values and the command line decide, before any GPU call.
+// Everything about the sixteen switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     fast_ = FastModes::from_env();
@@ -596,6 +647,10 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     if (verbose_ && fast_.size_filter())
         std::cout << run.dropped_clusters << " clusters holding " << run.dropped_records << (S == 1 ? " reads" : " read pairs") << " were not written (FQD_FAST_MINSIZE=" << fast_.min_size
                   << ", FQD_FAST_MAXSIZE=" << (fast_.max_size ? std::to_string(fast_.max_size) : std::string("none")) << ").\n";
+    // FQD_FAST_CENTROID=abundant: what `-v` says behind those
+    if (verbose_ && fast_.centroid)
+        std::cout << run.centroid_moved << " clusters were written by a copy of their most abundant " << (S == 1 ? "sequence" : "sequence pair") << ", not by their first "
+                  << (S == 1 ? "read" : "read pair") << " (FQD_FAST_CENTROID=abundant).\n";
     // FQD_FAST_CONSENSUS: what `-v` says behind those
     if (verbose_ && fast_.consensus)
         std::cout << run.consensus_bases << " bases in " << run.consensus_reads << (S == 1 ? " reads" : " read pairs") << " were replaced by their cluster's consensus (FQD_FAST_CONSENSUS=1).\n";

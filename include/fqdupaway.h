@@ -1039,6 +1039,46 @@ typedef struct fqd_consensus_info { uint64_t clusters;      /* clusters of >= 2 
 int  fqd_consensus(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint64_t n, uint8_t* text, const uint64_t* start, const uint32_t* size,
                    const uint64_t* seq_off, const uint32_t* seq_len, uint32_t flags, uint8_t* changed, fqd_consensus_info* info);
 
+/* ---- FQD_FAST_CENTROID=abundant: the most abundant sequence of every cluster (csrc/fqd_centroid_core.hpp) --------------------
+ * A merged cluster (FQD_FAST_UMI_MISMATCH, _HAMMING, _UMI_HAMMING, FQD_FAST_OPTICAL on top of them) is a union of exact
+ * clusters.  (perm, head) = fqd_group_owners' over the final owners: a run is a cluster, its members in input order.
+ * label[r] (device, n uint32 by record) = record r's exact owner, fqd_owners' over the run's exact keys.  The SUB-CLUSTER of a
+ * member is the members OF ITS RUN with its label — a label may stand in several runs, behind an optical split — and its
+ * abundance the sum of their weights (weight: device, n uint32 by record, NULL: 1 each), summed in 64 bits and stored as
+ * min(sum, 2^32 - 1).  A weighted cluster above 2^31 - 1 ends a run in fqd_cluster_weights before any output exists, so a
+ * saturated value never decides an output.
+ *
+ * fqd_subcluster_sizes: abundance[r] (device, n uint32 by record, like fqd_seq_scores' scores) = that sum for every record r,
+ * each entry stored exactly once, nothing else stored to.  Device memory only (info: host, may be NULL); n < 2^31.
+ * fqd_seq_pick_best(e, abundance, head, n, perm, &moved) then puts every cluster's centroid — the first member of the
+ * sub-cluster of the largest abundance, of equal ones the one whose first member stands earliest — at the head's place;
+ * moved = the clusters written by another sequence than their first member's.  The result does not depend on how members
+ * are dealt to lanes and workgroups nor on the order of atomics.  *info: clusters; mixed = those of two or more
+ * sub-clusters; subclusters = all of them; tier_clusters = the clusters of one member, of up to 8 (eight lanes a cluster),
+ * up to 64 (a wave), up to 2048 (a workgroup, its labels in a table in LDS) and above (many workgroups a cluster and a table
+ * in scratch keyed (head place << 32 | label); no upper limit and no refusal); largest = the members of the largest cluster.
+ * FQD_ERR_ARG, with NOTHING written: n >= 2^31 (before anything is allocated); abundance overlapping an input; head[0] == 0,
+ * an order that names a record outside 0 .. n-1 or a label outside 0 .. n-1 — counted on the device in the first launch and
+ * reported once.  n = 0: FQD_OK without a launch.  Scratch during the call: 4 bytes a cluster, about 5 bytes a record for
+ * the lists, and 32 bytes a member of the clusters above 2048.  Two results come back in between (the clusters and checks,
+ * the lists' lengths); returns after the stream has drained.
+ *
+ * fqd_subcluster_scores, behind that pick, for FQD_FAST_KEEP=best INSIDE the winning sub-cluster: masked[r] (device, n uint32
+ * by record) = min(score[r], 2^32 - 2) + 1 where label[r] is the label of the record at the head place of r's run, 0
+ * elsewhere; every entry stored exactly once.  A second fqd_seq_pick_best over masked puts the best-scored copy of the most
+ * abundant sequence at the head's place, the earliest in the input among equals (the centroid stands at the head, the
+ * other copies of its sequence in input order behind it).  Same memory rules and FQD_ERR_ARG cases as above, without the
+ * labels' range (they are only compared); scratch: 4 bytes a tile of 2048 places; returns after the stream has drained. */
+typedef struct fqd_centroid_info {
+    uint64_t clusters, mixed /* clusters of >= 2 sub-clusters */, subclusters;
+    uint64_t tier_clusters[5];   /* one member, <= 8, <= 64, a workgroup's, above */
+    uint32_t largest, reserved;
+} fqd_centroid_info;
+int  fqd_subcluster_sizes(fqd_engine* e, const uint32_t* perm, const uint8_t* head, const uint32_t* label,
+                          const uint32_t* weight /* NULL: 1 each */, uint64_t n, uint32_t* abundance, fqd_centroid_info* info /* host, may be NULL */);
+int  fqd_subcluster_scores(fqd_engine* e, const uint32_t* perm, const uint8_t* head, const uint32_t* label,
+                           const uint32_t* score, uint64_t n, uint32_t* masked);
+
 /* keep_out[origin[k]] = flags[k] for k < n: puts the flags that came back from the
  * owners (in partition order) into input order.  All device pointers. */
 int  fqd_scatter_flags(fqd_engine* e, const uint8_t* flags, const uint32_t* origin, uint64_t n, uint8_t* keep_out);
