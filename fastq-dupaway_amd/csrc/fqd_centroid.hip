@@ -3,12 +3,10 @@
 // first copy of the cluster's most abundant sequence at the head's place, and the scores masked to that sequence's copies for
 // FQD_FAST_KEEP=best.  Rule and proofs: fqd_centroid_core.hpp.  Nothing in here is called unless the switch is set.
 //
-//   heads    head_count_kernel + scan_tiles_kernel + head_write_kernel (the three launches of fqd_record_scan.hpp's scan):
-//            the head places of (perm, head) compacted in order, so that a cluster's size is the next head place minus its
-//            own.  The first launch also counts what ends the call: a record of the order or a label outside 0 .. n-1, and
-//            place 0 without a head.
-//   classes  classify_kernel, a lane a cluster (fqd_optical.hip's): a cluster of ONE member — most of them — is only counted;
-//            a longer one goes on the list of its size class, a wave adding to a list with one atomic.
+//   heads    fqd_clusters.hpp's: head_count_kernel (tile_count; its own part is what ends the call: a record of the order
+//            or a label outside 0 .. n-1, and place 0 without a head) + scan_tiles_kernel + head_write_kernel.
+//   classes  classify_kernel, a lane a cluster (cluster_at): a cluster of ONE member — most of them — is only counted;
+//            a longer one goes on the list of its size class (list_append).
 //   sums     singles_kernel: a lane a cluster of one, the abundance is the weight.  small_kernel: eight lanes a cluster,
 //            eight clusters a wave, a lane sums the weights of the lanes of its group that hold its label.  wave_kernel: a
 //            wave a cluster; the loop runs once per DISTINCT label — the lowest open lane's label is read across the wave
@@ -26,8 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fqd_centroid_core.hpp"
-#include "fqd_internal.hpp"
-#include "fqd_record_scan.hpp"
+#include "fqd_clusters.hpp"
 
 namespace {
 
@@ -43,8 +40,9 @@ static_assert(kPerThread * kTableBlock == int(kBlockLimit), "a block's threads s
 static_assert(64 % kSmall == 0 && kWave == 64, "the lane kernels' groups tile a wave");
 static_assert(kBlockTableBytes + 64 <= 64 * 1024, "the table and the block's counter fit a workgroup's static LDS");
 
-using fqdscan::head_write_kernel;
-using fqdscan::scan_tiles_kernel;
+using fqdclusters::cluster_at;
+using fqdclusters::entry_members;
+using fqdclusters::entry_place;
 using fqdwave::wave_max;
 using fqdwave::wave_sum;
 
@@ -65,34 +63,19 @@ __global__ __launch_bounds__(kBlock)
 void head_count_kernel(const uint32_t* __restrict__ perm, const uint8_t* __restrict__ head, const uint32_t* __restrict__ label, uint64_t n,
                        unsigned long long* __restrict__ tile_sum, Checks* checks)
 {
-    __shared__ unsigned long long ws[4];
-    const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
-    unsigned long long s = 0;
     uint32_t bad = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint64_t k = base + uint32_t(e);
-        if (k >= n) continue;
+    fqdclusters::tile_count<4>(n, tile_sum, [&](uint64_t k) __attribute__((always_inline)) {
         const bool h = head[k] != 0;
-        s += h;
         bad += perm[k] >= n || (k == 0 && !h) || label[k] >= n;
-    }
+        return h;
+    });
     bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&checks->bad, static_cast<unsigned long long>(bad));
-    s = fqdwave::block_total<4>(s, ws);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 // ---- classes -----------------------------------------------------------------------------------------------------------------
 
-struct Lists { unsigned long long* of[4]; };                 // entries (first place << 32 | members)
-
-// Cluster c of m: its first place and its members.
-__device__ __forceinline__ uint32_t cluster_at(const uint32_t* __restrict__ head_place, uint64_t m, uint64_t n, uint64_t c, uint32_t* k0)
-{
-    *k0 = head_place[c];
-    return uint32_t((c + 1 < m ? uint64_t(head_place[c + 1]) : n) - *k0);
-}
+using Lists = fqdclusters::Lists<4>;                         // the small, wave, block and large lists
 
 __global__ __launch_bounds__(kBlock)
 void classify_kernel(const uint32_t* __restrict__ head_place, uint64_t m, uint64_t n, Lists lists, Counters* counters)
@@ -102,12 +85,7 @@ void classify_kernel(const uint32_t* __restrict__ head_place, uint64_t m, uint64
     uint32_t s = 0, k0 = 0;
     if (c < m) s = cluster_at(head_place, m, n, c, &k0);
     const uint32_t tier = s == 0u ? 5u : tier_of(s);
-#pragma unroll
-    for (uint32_t t = 0; t < 4u; ++t) {
-        const bool mine = tier == t + 1u;
-        const uint32_t at = fqdwave::ballot_append(mine, &counters->listed[t]);
-        if (mine) lists.of[t][at] = (static_cast<unsigned long long>(k0) << 32) | s;
-    }
+    fqdclusters::list_append(lists, counters->listed, tier - 1u, k0, s);   // (tier 0, one member, and tier 5, none: on no list)
     const uint32_t singles = uint32_t(__popcll(__ballot(tier == kTierOne)));
     const unsigned long long large = wave_sum(tier == kTierLarge ? static_cast<unsigned long long>(s) : 0ull);
     const uint32_t largest = wave_max(s);
@@ -142,7 +120,7 @@ void small_kernel(const unsigned long long* __restrict__ list, uint32_t n_items,
     const uint64_t item = (blockIdx.x * uint64_t(kBlock) + threadIdx.x) / G;
     uint32_t s = 0;
     uint64_t k0 = 0;
-    if (item < n_items) { const unsigned long long e = list[item]; k0 = e >> 32; s = uint32_t(e); }
+    if (item < n_items) { const unsigned long long e = list[item]; k0 = entry_place(e); s = entry_members(e); }
     if (s > G) s = 0;                                        // (no list holds such an entry)
     const bool live = gl < s;
     uint32_t rec = 0, lab = kNoLabel, w = 0;
@@ -172,7 +150,7 @@ void wave_kernel(const unsigned long long* __restrict__ list, uint32_t n_items, 
     const uint64_t item = (blockIdx.x * uint64_t(kBlock) + threadIdx.x) / kWave;
     uint32_t s = 0;
     uint64_t k0 = 0;
-    if (item < n_items) { const unsigned long long e = list[item]; k0 = e >> 32; s = uint32_t(e); }
+    if (item < n_items) { const unsigned long long e = list[item]; k0 = entry_place(e); s = entry_members(e); }
     if (s > kWave) s = 0;                                    // (no list holds such an entry)
     const bool live = lane < s;
     uint32_t rec = 0, lab = kNoLabel, w = 0;
@@ -203,8 +181,8 @@ void block_kernel(const unsigned long long* __restrict__ list, Members mb, uint3
     __shared__ uint32_t keys[kBlockSlots];
     __shared__ uint32_t distinct;
     const unsigned long long e = list[blockIdx.x];
-    const uint64_t k0 = e >> 32;
-    uint32_t s = uint32_t(e);
+    const uint64_t k0 = entry_place(e);
+    uint32_t s = entry_members(e);
     if (s > kBlockLimit) s = 0;                              // (no list holds such an entry)
     const uint32_t slots = block_slots(s);
     for (uint32_t t = threadIdx.x; t < slots; t += kTableBlock) { keys[t] = kNoLabel; sums[t] = 0ull; }
@@ -262,7 +240,7 @@ void large_add_kernel(const unsigned long long* __restrict__ list, uint32_t n_it
 {
     for (uint32_t item = blockIdx.y; item < n_items; item += gridDim.y) {
         const unsigned long long e = list[item];
-        const uint32_t k0 = uint32_t(e >> 32), s = uint32_t(e);
+        const uint32_t k0 = uint32_t(entry_place(e)), s = entry_members(e);
         for (uint64_t v0 = uint64_t(blockIdx.x) * kBlock; v0 < s; v0 += uint64_t(gridDim.x) * kBlock) {   // (the whole block)
             const uint64_t v = v0 + threadIdx.x;
             const bool live = v < s;
@@ -285,7 +263,7 @@ void large_store_kernel(const unsigned long long* __restrict__ list, uint32_t n_
 {
     for (uint32_t item = blockIdx.y; item < n_items; item += gridDim.y) {
         const unsigned long long e = list[item];
-        const uint32_t k0 = uint32_t(e >> 32), s = uint32_t(e);
+        const uint32_t k0 = uint32_t(entry_place(e)), s = entry_members(e);
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             const uint32_t d = t.distinct[item];
             atomicAdd(&counters->subclusters, static_cast<unsigned long long>(d));
@@ -391,19 +369,6 @@ void masked_scores_kernel(const uint32_t* __restrict__ perm, const uint8_t* __re
     }
 }
 
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 struct SumBuffers { Counters* counters; uint32_t* head_place; Lists lists; };
 
 size_t carve_sums(uint64_t n, uint64_t m, char* base, SumBuffers& b)
@@ -411,10 +376,7 @@ size_t carve_sums(uint64_t n, uint64_t m, char* base, SumBuffers& b)
     Carver c{base};
     b.counters = c.take<Counters>(1);
     b.head_place = c.take<uint32_t>(m);
-    b.lists.of[0] = c.take<unsigned long long>(n / 2 + 1);                    // a listed cluster has two members at least,
-    b.lists.of[1] = c.take<unsigned long long>(n / (kSmall + 1) + 1);         // more than kSmall,
-    b.lists.of[2] = c.take<unsigned long long>(n / (kWave + 1) + 1);          // more than kWave,
-    b.lists.of[3] = c.take<unsigned long long>(n / (kBlockLimit + 1) + 1);    // more than kBlockLimit
+    fqdclusters::take_lists(c, n, {1u, kSmall, kWave, kBlockLimit}, b.lists);
     return c.used + 256;
 }
 
@@ -439,32 +401,26 @@ int fqd_subcluster_sizes(fqd_engine* e, const uint32_t* perm, const uint8_t* hea
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_subcluster_sizes: bad arguments (the order and its head flags, the exact owners, and room for the abundances of at most 2^31-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(label) || (weight && !on_device(weight)) || !on_device(abundance))
+    if (!all_on_device(perm, head, label, abundance) || (weight && !on_device(weight)))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_subcluster_sizes: every array is device memory");
     const size_t words = size_t(n) * sizeof(uint32_t);
     if (overlap(abundance, words, perm, words) || overlap(abundance, words, head, size_t(n)) || overlap(abundance, words, label, words) ||
-        (weight && overlap(abundance, words, weight, words)))
+        overlap(abundance, words, weight, words))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_subcluster_sizes: abundance overlaps an input");
     hipStream_t stream = fqd_internal_stream(e);
 
     // ---- heads ----
-    const uint32_t tiles = uint32_t((n + kOffTile - 1) / kOffTile);
-    void* small = nullptr;
-    int rc = fqd_internal_scratch(e, 1, (size_t(tiles) + 1) * sizeof(unsigned long long) + 256 + sizeof(Checks), &small);
+    TileScratch<Checks> slot;
+    int rc = slot.reserve(e, fqdclusters::tiles_of(n), stream);
     if (rc) return rc;
-    unsigned long long* tile_sum = static_cast<unsigned long long*>(small);
-    unsigned long long* d_total = tile_sum + tiles;
-    Checks* checks = reinterpret_cast<Checks*>(static_cast<char*>(small) + (((size_t(tiles) + 1) * sizeof(unsigned long long) + 255) & ~size_t(255)));
-    FQD_TRY(e, hipMemsetAsync(checks, 0, sizeof(Checks), stream));
-    hipLaunchKernelGGL(head_count_kernel, dim3(tiles), dim3(kBlock), 0, stream, perm, head, label, n, tile_sum, checks);
-    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile_sum, tiles, d_total);
-    FQD_TRY(e, hipGetLastError());
     unsigned long long m = 0;
     Checks found{};
-    FQD_TRY(e, hipMemcpyAsync(&m, d_total, sizeof m, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipMemcpyAsync(&found, checks, sizeof found, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
-    if (found.bad || m == 0 || m > n)
+    bool fits = false;
+    rc = fqdclusters::count_heads(e, stream, slot, n, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(head_count_kernel, grid, block, 0, stream, perm, head, label, n, slot.tile_sum, slot.counters);
+    }, &m, &found, &fits);
+    if (rc) return rc;
+    if (found.bad || !fits)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_subcluster_sizes: head[0] is not set, or the order names a record or a record's label is one outside 0 .. n-1 (are perm and head those of fqd_group_owners over these records, and the labels fqd_owners'? nothing was written)");
 
     // ---- classes ----
@@ -473,14 +429,12 @@ int fqd_subcluster_sizes(fqd_engine* e, const uint32_t* perm, const uint8_t* hea
     if ((rc = fqd_internal_scratch(e, 0, carve_sums(n, m, nullptr, b), &base))) return rc;
     (void)carve_sums(n, m, static_cast<char*>(base), b);
     FQD_TRY(e, hipMemsetAsync(b.counters, 0, sizeof(Counters), stream));
-    hipLaunchKernelGGL(head_write_kernel, dim3(tiles), dim3(kBlock), 0, stream, head, n, uint64_t(m), static_cast<const unsigned long long*>(tile_sum),
-                       b.head_place);
+    fqdclusters::write_heads(stream, slot, head, n, m, b.head_place);
     hipLaunchKernelGGL(classify_kernel, dim3(uint32_t((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(b.head_place), uint64_t(m), n,
                        b.lists, b.counters);
     FQD_TRY(e, hipGetLastError());
     Counters got{};
-    FQD_TRY(e, hipMemcpyAsync(&got, b.counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));                // (the tile sums have been read: the large tier may take their scratch)
+    FQD_TRY(e, read_back(got, b.counters, stream));          // (the tile sums have been read: the large tier may take their scratch)
 
     // ---- sums: the clusters of one, eight lanes, a wave, a block ----
     const Members mb{perm, label, weight};
@@ -514,8 +468,7 @@ int fqd_subcluster_sizes(fqd_engine* e, const uint32_t* perm, const uint8_t* hea
         hipLaunchKernelGGL(large_store_kernel, grid, dim3(kBlock), 0, stream, list, items, mb, t, abundance, b.counters);
         FQD_TRY(e, hipGetLastError());
     }
-    FQD_TRY(e, hipMemcpyAsync(&got, b.counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, b.counters, stream));
     if (info) {
         info->clusters = m;
         info->mixed = got.mixed;
@@ -535,7 +488,7 @@ int fqd_subcluster_scores(fqd_engine* e, const uint32_t* perm, const uint8_t* he
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_subcluster_scores: bad arguments (the order and its head flags, the exact owners, the scores, and room for the masked scores of at most 2^31-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(label) || !on_device(score) || !on_device(masked))
+    if (!all_on_device(perm, head, label, score, masked))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_subcluster_scores: every array is device memory");
     const size_t words = size_t(n) * sizeof(uint32_t);
     if (overlap(masked, words, perm, words) || overlap(masked, words, head, size_t(n)) || overlap(masked, words, label, words) || overlap(masked, words, score, words))
@@ -545,15 +498,15 @@ int fqd_subcluster_scores(fqd_engine* e, const uint32_t* perm, const uint8_t* he
     void* small = nullptr;
     const int rc = fqd_internal_scratch(e, 1, size_t(tiles) * sizeof(uint32_t) + 512 + sizeof(Checks), &small);
     if (rc) return rc;
-    uint32_t* tile_last = static_cast<uint32_t*>(small);
-    Checks* checks = reinterpret_cast<Checks*>(static_cast<char*>(small) + ((size_t(tiles) * sizeof(uint32_t) + 255) & ~size_t(255)));
+    Carver c{static_cast<char*>(small)};
+    uint32_t* tile_last = c.take<uint32_t>(tiles);
+    Checks* checks = c.take<Checks>(1);
     FQD_TRY(e, hipMemsetAsync(checks, 0, sizeof(Checks), stream));
     hipLaunchKernelGGL(last_head_tiles_kernel, dim3(tiles), dim3(kBlock), 0, stream, perm, head, n, tile_last, checks);
     hipLaunchKernelGGL(last_head_carry_kernel, dim3(1), dim3(1024), 0, stream, tile_last, tiles);
     FQD_TRY(e, hipGetLastError());
     Checks found{};
-    FQD_TRY(e, hipMemcpyAsync(&found, checks, sizeof found, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(found, checks, stream));
     if (found.bad)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_subcluster_scores: head[0] is not set, or the order names a record outside 0 .. n-1 (are perm and head those of fqd_group_owners over these records? nothing was written)");
     hipLaunchKernelGGL(masked_scores_kernel, dim3(tiles), dim3(kBlock), 0, stream, perm, head, label, score, n, static_cast<const uint32_t*>(tile_last), masked);

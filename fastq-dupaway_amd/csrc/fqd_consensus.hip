@@ -2,13 +2,14 @@
 // of every cluster's written member replaced, where they lie in the text, by the cluster's column-wise consensus.  Rule and
 // proofs: fqd_consensus_core.hpp.  Nothing in here is called unless the switch is set.
 //
-//   heads    check_heads_kernel + scan_tiles_kernel + head_write_kernel (the three launches of fqd_record_scan.hpp's scan): the
-//            head places of (perm, head) compacted in order, so that a cluster's size is the next head place minus its own.
-//            The first of them also holds every record's lines against lines_fit, every member's sequence length against the
-//            member in front of it, and finds the longest sequence.  The counts come back; a bad one ends the call here,
-//            before any store to the text.
-//   classes  classify_kernel, a lane a cluster: a cluster of ONE member — most of them — is passed over; a longer one goes on the
-//            list of its tier; a block's waves count in LDS and the block adds to a list with one atomic.  The lists' lengths come back for the grids.
+//   heads    fqd_clusters.hpp's: check_heads_kernel (tile_count) + scan_tiles_kernel + head_write_kernel.  check_heads_kernel's
+//            own part: it holds every record's lines against lines_fit, every member's sequence length against the member in
+//            front of it, and finds the longest sequence.  The counts come back; a bad one ends the call here, before any
+//            store to the text.
+//   classes  classify_kernel, a lane a cluster (cluster_at): a cluster of ONE member — most of them — is passed over; a longer
+//            one goes on the list of its tier.  NOT through fqd_clusters.hpp's list_append: a block's waves count in LDS and the
+//            block adds to a list with one atomic (a wave-wide atomic a list was this kernel's 3.43 ms).  The lists'
+//            lengths come back for the grids.
 //   votes    LANES RUN ALONG COLUMNS, kChunk = 4 columns a lane and load, and the members go one after the other within a lane:
 //            a member's row is read by neighbouring lanes at neighbouring addresses.  A whole chunk is one 4-byte load a line;
 //            the last, partial one goes byte by byte: no load leaves a read's line.  A lane keeps the states of its 4 columns
@@ -36,16 +37,14 @@
 
 #include <vector>
 
-#include "fqd_internal.hpp"
+#include "fqd_clusters.hpp"
 #include "fqd_consensus_core.hpp"
-#include "fqd_record_scan.hpp"
 
 namespace {
 
 using namespace fqdconsensus;
 
 constexpr int kBlock = fqdscan::kBlock;
-constexpr int kOffTile = fqdscan::kOffTile;                  // places a block of the scan's two passes
 constexpr uint32_t kGroup = 16;                              // lanes a small cluster
 constexpr uint32_t kWaves = kBlock / 64;
 constexpr uint32_t kRound = 64 * kChunk;                     // columns a wave and round
@@ -56,8 +55,8 @@ static_assert((1ull << 31) / kMaxGroups <= kMax32, "a workgroup's share of a clu
 static_assert(kWaves == kChunk, "thread (w, lane) decides column kChunk * lane + w of a round: as many waves as columns a lane");
 static_assert(kWaves * kWords * kRound * sizeof(uint32_t) <= 64 * 1024, "the four waves' states of a round fit a workgroup's LDS");
 
-using fqdscan::head_write_kernel;
-using fqdscan::scan_tiles_kernel;
+using fqdclusters::entry_members;
+using fqdclusters::entry_place;
 using fqdwave::wave_max;
 using fqdwave::wave_sum;
 
@@ -79,23 +78,23 @@ struct Counters {
 __global__ __launch_bounds__(kBlock)
 void check_heads_kernel(Rows R, const uint8_t* __restrict__ head, uint64_t n, unsigned long long* __restrict__ tile_sum, Counters* counters)
 {
-    __shared__ unsigned long long ws[kWaves];
-    const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
-    unsigned long long s = 0;
     uint32_t bad_place = 0, bad_lines = 0, bad_len = 0, longest = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint64_t k = base + uint32_t(e);
-        if (k >= n) continue;
+    fqdclusters::tile_count<int(kWaves)>(n, tile_sum, [&](uint64_t k) __attribute__((always_inline)) {
         const bool h = head[k] != 0;
         const uint32_t r = R.perm[k];
-        s += h;
-        if (r >= n || (k == 0 && !h)) { ++bad_place; continue; }
-        const uint32_t L = R.seq_len[r];
-        bad_lines += !lines_fit(R.start[r], R.size[r], R.seq_off[r], L);
+        const bool lost = r >= n || (k == 0 && !h);
+        uint32_t L = 0;
+        bool lines = false, len = false;
+        if (!lost) {
+            L = R.seq_len[r];
+            lines = !lines_fit(R.start[r], R.size[r], R.seq_off[r], L);
+            if (!h) { const uint32_t before = R.perm[k - 1]; len = before < n && R.seq_len[before] != L; }
+        }
+        // (one add a count whatever the place was: counts that branches add to apart end up in private memory)
+        bad_place += lost; bad_lines += lines; bad_len += len;
         longest = L > longest ? L : longest;
-        if (!h) { const uint32_t before = R.perm[k - 1]; bad_len += before < n && R.seq_len[before] != L; }
-    }
+        return h;
+    });
     bad_place = wave_sum(bad_place); bad_lines = wave_sum(bad_lines); bad_len = wave_sum(bad_len); longest = wave_max(longest);
     if ((threadIdx.x & 63) == 0) {
         if (bad_place) atomicAdd(&counters->bad_place, static_cast<unsigned long long>(bad_place));
@@ -103,13 +102,11 @@ void check_heads_kernel(Rows R, const uint8_t* __restrict__ head, uint64_t n, un
         if (bad_len) atomicAdd(&counters->bad_len, static_cast<unsigned long long>(bad_len));
         if (longest) atomicMax(&counters->longest, longest);
     }
-    s = fqdwave::block_total<kWaves>(s, ws);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 // ---- classes -----------------------------------------------------------------------------------------------------------------
 
-struct Lists { unsigned long long* of[3]; uint32_t* many_len; };   // entries (first place << 32 | members); the sequence length of every entry of of[2]
+struct Lists : fqdclusters::Lists<3> { uint32_t* many_len; };   // the lanes', the workgroup's and the many-workgroups list; the sequence length of every entry of of[2]
 
 constexpr int kClassBlock = 1024;                            // clusters a block of classify_kernel
 
@@ -126,7 +123,7 @@ void classify_kernel(const uint32_t* __restrict__ head_place, Rows R, uint64_t m
     const uint64_t c = blockIdx.x * uint64_t(kClassBlock) + threadIdx.x;   // (no stride: every lane of a wave reaches the ballots)
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t s = 0, k0 = 0;
-    if (c < m) { k0 = head_place[c]; s = uint32_t((c + 1 < m ? uint64_t(head_place[c + 1]) : n) - k0); }
+    if (c < m) s = fqdclusters::cluster_at(head_place, m, n, c, &k0);
     const uint32_t cls = s < 2u ? 3u : s <= tiers.small ? 0u : s <= tiers.block ? 1u : 2u;
     uint32_t at = 0;                                         // the cluster's place among the block's of its class
 #pragma unroll
@@ -146,7 +143,7 @@ void classify_kernel(const uint32_t* __restrict__ head_place, Rows R, uint64_t m
     }
     __syncthreads();
     if (cls < 3u) {
-        lists.of[cls][base[cls] + at] = (static_cast<unsigned long long>(k0) << 32) | s;
+        lists.of[cls][base[cls] + at] = fqdclusters::entry(k0, s);
         if (cls == 2u) lists.many_len[base[cls] + at] = R.seq_len[R.perm[k0]];
     }
 }
@@ -191,7 +188,7 @@ void vote_lanes_kernel(const unsigned long long* __restrict__ list, uint32_t n_i
     const uint64_t item = (blockIdx.x * uint64_t(kBlock) + threadIdx.x) / kGroup;
     uint32_t m = 0;
     uint64_t k0 = 0;
-    if (item < n_items) { const unsigned long long e = list[item]; k0 = e >> 32; m = uint32_t(e); }
+    if (item < n_items) { const unsigned long long e = list[item]; k0 = entry_place(e); m = entry_members(e); }
     if (m > limit) m = 0;                                    // (no list holds such an entry)
     uint32_t written = 0, L = 0;
     unsigned long long own_seq = 0, own_qual = 0;
@@ -251,7 +248,7 @@ void vote_block_kernel(const unsigned long long* __restrict__ list, Rows R, uint
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (!kMany) {
         const unsigned long long e = list[blockIdx.x];
-        k0 = e >> 32; m = uint32_t(e);
+        k0 = entry_place(e); m = entry_members(e);
         if (m > limit) m = 0;                                // (no list holds such an entry)
     }
     // this wave's members: first, first + stride, ... below m; a workgroup's are at most `share` <= kMax32 of them (Sum32)
@@ -341,24 +338,14 @@ void finish_many_kernel(Rows R, uint64_t k0, const unsigned long long* __restric
     if ((threadIdx.x & 63) == 0 && n_changed) atomicAdd(&counters->bases_changed, static_cast<unsigned long long>(n_changed));
 }
 
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 struct VoteBuffers { uint32_t* head_place; Lists lists; unsigned long long* columns; uint32_t* marked; };
 
 size_t carve_votes(uint64_t n, uint64_t m, uint32_t longest, const Tiers& tiers, char* base, VoteBuffers& b)
 {
     Carver c{base};
-    const size_t many = n / (size_t(tiers.block) + 1) + 1;
     b.head_place = c.take<uint32_t>(m);
-    b.lists.of[0] = c.take<unsigned long long>(n / 2 + 1);                       // a listed cluster has two members at least,
-    b.lists.of[1] = c.take<unsigned long long>(n / (size_t(tiers.small) + 1) + 1);   // more than tiers.small,
-    b.lists.of[2] = c.take<unsigned long long>(many);                            // more than tiers.block
-    b.lists.many_len = c.take<uint32_t>(many);
+    fqdclusters::take_lists<3>(c, n, {1u, tiers.small, tiers.block}, b.lists);
+    b.lists.many_len = c.take<uint32_t>(fqdclusters::list_room(n, tiers.block));
     b.columns = c.take<unsigned long long>(n > tiers.block ? size_t(longest) * kWords : 0);
     b.marked = c.take<uint32_t>(1);
     return c.used + 256;
@@ -377,31 +364,25 @@ int fqd_consensus(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_consensus: bad arguments (the info, flags of 0 or FQD_CONSENSUS_SMALL_TIERS, the order and its head flags, the text, and the starts, sizes, sequence offsets and sequence lengths of at most 2^31-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(text) || !on_device(start) || !on_device(size) || !on_device(seq_off) || !on_device(seq_len) ||
-        (changed && !on_device(changed)))
+    if (!all_on_device(perm, head, text, start, size, seq_off, seq_len) || (changed && !on_device(changed)))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_consensus: the text and every array are device memory");
     hipStream_t stream = fqd_internal_stream(e);
     const Tiers tiers = flags & FQD_CONSENSUS_SMALL_TIERS ? kSmallTiers : kTiers;
     const Rows R{text, perm, start, size, seq_off, seq_len};
 
     // ---- heads, and everything that can refuse the call ----
-    const uint32_t tiles = uint32_t((n + kOffTile - 1) / kOffTile);
-    void* small = nullptr;
-    int rc = fqd_internal_scratch(e, 1, (size_t(tiles) + 1) * sizeof(unsigned long long) + 256 + sizeof(Counters), &small);
+    TileScratch<Counters> slot;
+    int rc = slot.reserve(e, fqdclusters::tiles_of(n), stream);
     if (rc) return rc;
-    unsigned long long* tile_sum = static_cast<unsigned long long*>(small);
-    unsigned long long* d_total = tile_sum + tiles;
-    Counters* counters = reinterpret_cast<Counters*>(static_cast<char*>(small) + (((size_t(tiles) + 1) * sizeof(unsigned long long) + 255) & ~size_t(255)));
-    FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
-    hipLaunchKernelGGL(check_heads_kernel, dim3(tiles), dim3(kBlock), 0, stream, R, head, n, tile_sum, counters);
-    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile_sum, tiles, d_total);
-    FQD_TRY(e, hipGetLastError());
+    Counters* counters = slot.counters;
     unsigned long long m = 0;
     Counters got{};
-    FQD_TRY(e, hipMemcpyAsync(&m, d_total, sizeof m, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
-    if (got.bad_place || m == 0 || m > n)
+    bool fits = false;
+    rc = fqdclusters::count_heads(e, stream, slot, n, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(check_heads_kernel, grid, block, 0, stream, R, head, n, slot.tile_sum, counters);
+    }, &m, &got, &fits);
+    if (rc) return rc;
+    if (got.bad_place || !fits)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_consensus: head[0] is not set, or the order names a record outside 0 .. n-1 (are perm and head those of fqd_group_owners over these records? nothing was written)");
     if (got.bad_lines)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_consensus: a record's quality line, seq_len bytes at start + size - 1 - seq_len, does not lie behind its sequence line inside the record (FASTQ records only; nothing was written)");
@@ -413,13 +394,11 @@ int fqd_consensus(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint
     void* base = nullptr;
     if ((rc = fqd_internal_scratch(e, 0, carve_votes(n, m, got.longest, tiers, nullptr, b), &base))) return rc;
     (void)carve_votes(n, m, got.longest, tiers, static_cast<char*>(base), b);
-    hipLaunchKernelGGL(head_write_kernel, dim3(tiles), dim3(kBlock), 0, stream, head, n, uint64_t(m), static_cast<const unsigned long long*>(tile_sum),
-                       b.head_place);
+    fqdclusters::write_heads(stream, slot, head, n, m, b.head_place);
     hipLaunchKernelGGL(classify_kernel, dim3(uint32_t((m + kClassBlock - 1) / kClassBlock)), dim3(kClassBlock), 0, stream, static_cast<const uint32_t*>(b.head_place), R,
                        uint64_t(m), n, tiers, b.lists, counters);
     FQD_TRY(e, hipGetLastError());
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, counters, stream));
     std::vector<unsigned long long> many(got.listed[2]);
     std::vector<uint32_t> many_len(got.listed[2]);
     if (!many.empty()) {
@@ -437,8 +416,8 @@ int fqd_consensus(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint
                            uint64_t(0), 0u, tiers.block, static_cast<unsigned long long*>(nullptr), changed, counters);
     FQD_TRY(e, hipGetLastError());
     for (size_t k = 0; k < many.size(); ++k) {
-        const uint64_t k0 = many[k] >> 32;
-        const uint32_t members = uint32_t(many[k]), L = many_len[k];
+        const uint64_t k0 = entry_place(many[k]);
+        const uint32_t members = entry_members(many[k]), L = many_len[k];
         if (L == 0 || L > got.longest) continue;             // (no column; the second cannot be)
         // (a workgroup's members: every groups-th run of kWaves, at most max(share, 2^31 / kMaxGroups) = kMax32 of them)
         const uint32_t groups = std::min<uint32_t>((members + tiers.share - 1) / tiers.share, kMaxGroups);
@@ -450,8 +429,7 @@ int fqd_consensus(fqd_engine* e, const uint32_t* perm, const uint8_t* head, uint
                            b.marked, changed, counters);
         FQD_TRY(e, hipGetLastError());
     }
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, counters, stream));
     *info = fqd_consensus_info{got.clusters, got.members, got.bases_changed, got.reads_changed, got.largest};
     return FQD_OK;
 }

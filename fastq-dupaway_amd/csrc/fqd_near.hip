@@ -31,7 +31,6 @@
 //            labels, jump_kernel (labels[v] = next[next[v]]).  finish_kernel: owner_out[i] = labels[owner[i]].
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdlib>
 #include <string>
 
@@ -341,19 +340,6 @@ void finish_kernel(const uint32_t* __restrict__ owner, const uint32_t* __restric
     if ((threadIdx.x & 63) == 0 && merged) atomicAdd(&counters->merged, merged);
 }
 
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-    return b && pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 struct Buffers { uint64_t* keys[2]; uint32_t* vals[2]; uint32_t *counts, *tot, *labels; };
 
 size_t carve(uint64_t n, uint64_t N, char* base, Buffers& b)
@@ -392,8 +378,8 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
         return fail(FQD_ERR_ARG, ": bad arguments (the info, a distance of 1 .. 3, no flag but FQD_NEAR_WEAK_SEEDS, the engine's segments as fqd_reads — offsets and lengths both or neither — the owners and room for the merged owners of at most 2^31-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    bool device = on_device(owner) && on_device(owner_out) && (!link || on_device(link));
-    for (int s = 0; s < S; ++s) device = device && on_device(reads[s].bases) && (!reads[s].offsets || (on_device(reads[s].offsets) && on_device(reads[s].lengths)));
+    bool device = all_on_device(owner, owner_out) && (!link || on_device(link));
+    for (int s = 0; s < S; ++s) device = device && on_device(reads[s].bases) && (!reads[s].offsets || all_on_device(reads[s].offsets, reads[s].lengths));
     if (!device) return fail(FQD_ERR_ARG, ": the reads and every array are device memory");
     const size_t words = size_t(n) * sizeof(uint32_t);
     bool overlaps = overlap(owner_out, words, owner, words) || overlap(owner_out, words, link, words);
@@ -403,12 +389,7 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
                    (!reads[s].offsets && overlap(owner_out, words, reads[s].bases, size_t(n - 1) * reads[s].uniform_stride + reads[s].uniform_len));
     if (overlaps) return fail(FQD_ERR_ARG, ": owner_out overlaps an input");
     hipStream_t stream = fqd_internal_stream(e);
-    auto clock = std::chrono::steady_clock::now();
-    auto stage = [&](int k) {                                   // (behind a wait of the call's own: what the stage cost, seen from the host)
-        const auto now = std::chrono::steady_clock::now();
-        out->stage_ms[k] = std::chrono::duration<float, std::milli>(now - clock).count();
-        clock = now;
-    };
+    StageTimer timer{out->stage_ms};
     const uint32_t D = distance;
     const bool paired = S == 2, weak = (flags & FQD_NEAR_WEAK_SEEDS) != 0;
     const Mate m1{reads[0].bases, reads[0].offsets, reads[0].lengths, reads[0].uniform_len, reads[0].uniform_stride};
@@ -420,22 +401,17 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
     if (rc) return rc;
     Counters* counters = static_cast<Counters*>(small);
     Counters got{};
-    auto fetch = [&]() -> hipError_t {
-        hipError_t err = hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream);
-        return err != hipSuccess ? err : hipStreamSynchronize(stream);
-    };
-    FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
-    FQD_TRY(e, hipMemsetAsync(&counters->over, 0xFF, sizeof(unsigned long long), stream));
+    FQD_TRY(e, zero_counters(counters, stream, &Counters::over));
     hipLaunchKernelGGL(count_nodes_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, owner, n, counters);
     FQD_TRY(e, hipGetLastError());
-    FQD_TRY(e, fetch());
+    FQD_TRY(e, read_back(got, counters, stream));
     if (got.bad || got.nodes == 0 || got.nodes > n)
         return fail(FQD_ERR_ARG, ": an owner lies above its record or is not its own owner (is owner that of fqd_owners over these records? nothing was written)");
     uint64_t L = 0;
     if (link) {
         hipLaunchKernelGGL(count_links_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, owner, link, n, counters);
         FQD_TRY(e, hipGetLastError());
-        FQD_TRY(e, fetch());
+        FQD_TRY(e, read_back(got, counters, stream));
         if (got.bad || got.links >= got.nodes)
             return fail(FQD_ERR_ARG, ": a node's link lies above it or names a record that is no node (is link fqd_umi_merge's owner_out over these owners? nothing was written)");
         *links = L = got.links;
@@ -462,12 +438,12 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
     uint64_t* work = b.keys[cur ^ 1];                         // (the sort's other key array is free from here on)
     hipLaunchKernelGGL(mark_kernel, dim3(uint32_t((N + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, keys, vals, N, work, counters);
     FQD_TRY(e, hipGetLastError());
-    FQD_TRY(e, fetch());
+    FQD_TRY(e, read_back(got, counters, stream));
     if (got.cursor != N) return fail(FQD_ERR_HIP, ": internal error (the nodes counted and the nodes listed differ)");
     out->groups = got.groups; out->largest_group = got.largest;
     const uint64_t W = got.work;
     if (W > N) return fail(FQD_ERR_HIP, ": internal error (more entries with a successor than entries)");
-    stage(0);
+    timer.mark(0);
     if (got.over != kNoOver) {                                // refused: owner_out stays unspecified
         out->over_limit_first = got.over >> 32;
         out->over_limit_nodes = got.over & 0xFFFFFFFFull;
@@ -481,7 +457,7 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
         if ((rc = fqd_internal_scratch(e, 1, kEdgesAt + size_t(room) * sizeof(uint2), &small))) return rc;
         counters = static_cast<Counters*>(small);               // (a larger block is a new one: the counters verify adds to start at 0 either way)
         edges = reinterpret_cast<uint2*>(static_cast<char*>(small) + kEdgesAt);
-        FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
+        FQD_TRY(e, zero_counters(counters, stream));
         if (L) hipLaunchKernelGGL(links_kernel, dim3(uint32_t((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, owner, link, n, edges, room, counters);
         if (W && tags)
             hipLaunchKernelGGL(verify_umi_kernel, dim3(uint32_t((W * kLanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, keys, vals, N,
@@ -490,7 +466,7 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
             hipLaunchKernelGGL(verify_kernel, dim3(uint32_t((W * kLanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, keys, vals, N,
                                static_cast<const uint64_t*>(work), W, m1, m2, paired, D, edges, room, counters);
         FQD_TRY(e, hipGetLastError());
-        FQD_TRY(e, fetch());
+        FQD_TRY(e, read_back(got, counters, stream));
         if (got.edges <= room) break;
         if (attempt) return fail(FQD_ERR_HIP, ": internal error (two runs of the verification count different edges)");
         room = got.edges;
@@ -498,7 +474,7 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
     const uint64_t m = got.edges;                               // (the links in front, the near edges behind them)
     if (m < L) return fail(FQD_ERR_HIP, ": internal error (fewer edges than links)");
     out->pairs = got.pairs; out->edges = m - L;
-    stage(1);
+    timer.mark(1);
 
     // ---- sweeps ----
     uint32_t* next = owner_out;
@@ -511,16 +487,15 @@ int merge(fqd_engine* e, const char* name, const fqd_reads* reads, const uint32_
                            static_cast<const uint32_t*>(b.labels), next, &counters->changed);
         FQD_TRY(e, hipGetLastError());
         uint32_t changed = 0;
-        FQD_TRY(e, hipMemcpyAsync(&changed, &counters->changed, sizeof changed, hipMemcpyDeviceToHost, stream));
-        FQD_TRY(e, hipStreamSynchronize(stream));
+        FQD_TRY(e, read_back(changed, &counters->changed, stream));
         if (!changed) break;
         hipLaunchKernelGGL(jump_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(next), b.labels, n);
     }
     hipLaunchKernelGGL(finish_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, owner, static_cast<const uint32_t*>(b.labels), n, owner_out, counters);
     FQD_TRY(e, hipGetLastError());
-    FQD_TRY(e, fetch());
+    FQD_TRY(e, read_back(got, counters, stream));
     out->merged = got.merged; out->sweeps = sweeps;
-    stage(2);
+    timer.mark(2);
     return FQD_OK;
 }
 
@@ -546,7 +521,7 @@ int fqd_near_merge_umi(fqd_engine* e, const fqd_reads* reads, const uint32_t* ow
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_near_merge_umi: bad arguments (the info, fqd_umi_find's text, ID starts, UMI offsets and its info with no record refused and a UMI of 1 .. 64 bytes)");
     if (n) {
         FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-        if (!on_device(text) || !on_device(id_start) || !on_device(umi_off))
+        if (!all_on_device(text, id_start, umi_off))
             return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_near_merge_umi: the text, the ID starts and the UMI offsets are device memory");
     }
     const Tags tags{text, id_start, umi_off, info->umi_len, info->joiners};

@@ -9,11 +9,10 @@
 //            group takes the places of the 4th .. 7th.  Lanes 0, 1 and 2 read tile, x and y; all sixteen hold the surface
 //            against record 0's, a byte a lane.  The lowest refused record and its reason come back through one 64-bit
 //            atomicMin a wave of (record << 3 | reason).  No load leaves the ID line.
-//   heads    head_count_kernel + scan_tiles_kernel + head_write_kernel (the three launches of fqd_record_scan.hpp's scan):
-//            the head places of (perm, head) compacted in order, so that a cluster's size is the next head place minus its
-//            own.  The count comes back to size the rest.
-//   classes  classify_kernel, a lane a cluster: a cluster of ONE member — most of them — is only counted; a longer one goes
-//            on the list of its size class, a wave adding to a list with one atomic.  A cluster beyond the limit is reported
+//   heads    fqd_clusters.hpp's: head_count_kernel (tile_count; its own part: a place whose record lies outside 0 .. n-1,
+//            place 0 without a head) + scan_tiles_kernel + head_write_kernel.  The count comes back to size the rest.
+//   classes  classify_kernel, a lane a cluster (cluster_at): a cluster of ONE member — most of them — is only counted; a
+//            longer one goes on the list of its size class (list_append).  A cluster beyond the limit is reported
 //            through one 64-bit atomicMin of (first record << 32 | members).  The counts come back for the grids.
 //   split    singles_kernel: a lane a cluster of one, one store.  split_lanes_kernel<8>: eight lanes a cluster, eight
 //            clusters a wave; split_lanes_kernel<64>: a wave a cluster — a lane holds its member's neighbours as a 64-bit
@@ -26,31 +25,28 @@
 //            Every kernel stores owner_out of its own clusters' members; nothing is stored where a cluster is refused.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-
-#include "fqd_internal.hpp"
+#include "fqd_clusters.hpp"
 #include "fqd_optical_core.hpp"
-#include "fqd_record_scan.hpp"
 
 namespace {
 
 using namespace fqdoptical;
 
 constexpr int kBlock = fqdscan::kBlock;
-constexpr int kOffTile = fqdscan::kOffTile;                  // places a block of the scan's two passes
 constexpr uint32_t kWaveTile = 64;                           // records a wave (places)
 constexpr uint32_t kTile = kWaveTile * (kBlock / 64);        // records a block (places)
 constexpr int kSplitBlock = 1024;                            // threads of a cluster's block
 constexpr int kPerThread = int(kBlockLimit) / kSplitBlock;
 constexpr uint32_t kLargeChunks = (kMaxCluster + kBlock - 1) / kBlock;
-constexpr unsigned long long kNoBad = ~0ull;
 
 static_assert(kPerThread * kSplitBlock == int(kBlockLimit), "a block's threads share the largest cluster in LDS evenly");
 static_assert(kWave == 64 && 64 % kSmall == 0 && kGroup == 16, "the lane kernels' groups tile a wave");
 static_assert(6 * kBlockLimit * sizeof(uint32_t) <= 64 * 1024, "places, records and labels of a cluster fit a workgroup's LDS");
 
-using fqdscan::head_write_kernel;
-using fqdscan::scan_tiles_kernel;
+using fqdclusters::cluster_at;
+using fqdclusters::entry_members;
+using fqdclusters::entry_place;
+using fqdclusters::kNoBad;
 using fqdwave::wave_max;
 using fqdwave::wave_sum;
 
@@ -121,7 +117,7 @@ void read_places_kernel(const uint8_t* __restrict__ text, const uint64_t* __rest
     uint32_t other = 0;
     if (mine < n) {
         tile[mine] = my.tile; x[mine] = my.x; y[mine] = my.y; surface[mine] = my.surface;
-        if (my.reason) word = (static_cast<unsigned long long>(mine) << 3) | my.reason;
+        if (my.reason) word = fqdclusters::bad_word(mine, my.reason);
         else other = my.surface & kSameSurface ? 0u : 1u;
     }
     word = fqdwave::wave_min(word);
@@ -148,34 +144,19 @@ __global__ __launch_bounds__(kBlock)
 void head_count_kernel(const uint32_t* __restrict__ perm, const uint8_t* __restrict__ head, uint64_t n, unsigned long long* __restrict__ tile_sum,
                        Counters* counters)
 {
-    __shared__ unsigned long long ws[4];
-    const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
-    unsigned long long s = 0;
     uint32_t bad = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint64_t k = base + uint32_t(e);
-        if (k >= n) continue;
+    fqdclusters::tile_count<4>(n, tile_sum, [&](uint64_t k) __attribute__((always_inline)) {
         const bool h = head[k] != 0;
-        s += h;
         bad += perm[k] >= n || (k == 0 && !h);
-    }
+        return h;
+    });
     bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&counters->bad, static_cast<unsigned long long>(bad));
-    s = fqdwave::block_total<4>(s, ws);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 // ---- classes -----------------------------------------------------------------------------------------------------------------
 
-struct Lists { unsigned long long* of[4]; };                 // entries (first place << 32 | members)
-
-// Cluster c of m: its first place and its members.
-__device__ __forceinline__ uint32_t cluster_at(const uint32_t* __restrict__ head_place, uint64_t m, uint64_t n, uint64_t c, uint32_t* k0)
-{
-    *k0 = head_place[c];
-    return uint32_t((c + 1 < m ? uint64_t(head_place[c + 1]) : n) - *k0);
-}
+using Lists = fqdclusters::Lists<4>;                         // the small, wave, block and large lists
 
 __global__ __launch_bounds__(kBlock)
 void classify_kernel(const uint32_t* __restrict__ head_place, const uint32_t* __restrict__ perm, uint64_t m, uint64_t n, Lists lists, Counters* counters)
@@ -185,11 +166,7 @@ void classify_kernel(const uint32_t* __restrict__ head_place, const uint32_t* __
     uint32_t s = 0, k0 = 0;
     if (c < m) s = cluster_at(head_place, m, n, c, &k0);
     const uint32_t cls = s == 0u ? 6u : s == 1u ? 5u : s <= kSmall ? 0u : s <= kWave ? 1u : s <= kBlockLimit ? 2u : s <= kMaxCluster ? 3u : 4u;
-#pragma unroll
-    for (uint32_t t = 0; t < 4u; ++t) {
-        const uint32_t at = fqdwave::ballot_append(cls == t, &counters->listed[t]);
-        if (cls == t) lists.of[t][at] = (static_cast<unsigned long long>(k0) << 32) | s;
-    }
+    fqdclusters::list_append(lists, counters->listed, cls, k0, s);
     if (cls == 4u) atomicMin(&counters->over, (static_cast<unsigned long long>(perm[k0]) << 32) | s);
     const uint32_t singles = uint32_t(__popcll(__ballot(cls == 5u)));
     const uint32_t largest = wave_max(s);
@@ -222,7 +199,7 @@ void split_lanes_kernel(const unsigned long long* __restrict__ list, uint32_t n_
     const uint64_t item = (blockIdx.x * uint64_t(kBlock) + threadIdx.x) / G;
     uint32_t s = 0;
     uint64_t k0 = 0;
-    if (item < n_items) { const unsigned long long e = list[item]; k0 = e >> 32; s = uint32_t(e); }
+    if (item < n_items) { const unsigned long long e = list[item]; k0 = entry_place(e); s = entry_members(e); }
     if (s > G) s = 0;                                        // (no list holds such an entry)
     const bool live = gl < s;
     uint32_t rec = 0, t = 0, x = 0, y = 0, sw = 0;
@@ -265,8 +242,8 @@ void split_block_kernel(const unsigned long long* __restrict__ list, const uint3
 {
     __shared__ uint32_t T[kBlockLimit], X[kBlockLimit], Y[kBlockLimit], S[kBlockLimit], R[kBlockLimit], labels[kBlockLimit];
     const unsigned long long e = list[blockIdx.x];
-    const uint64_t k0 = e >> 32;
-    uint32_t s = uint32_t(e);
+    const uint64_t k0 = entry_place(e);
+    uint32_t s = entry_members(e);
     if (s > kBlockLimit) s = 0;                              // (no list holds such an entry)
     for (uint32_t v = threadIdx.x; v < s; v += kSplitBlock) {
         const uint32_t r = perm[k0 + v];
@@ -321,8 +298,8 @@ void large_start_kernel(const unsigned long long* __restrict__ list, uint32_t n_
 {
     for (uint32_t item = blockIdx.y; item < n_items; item += gridDim.y) {
         const unsigned long long e = list[item];
-        const uint64_t k0 = e >> 32;
-        const uint32_t s = uint32_t(e), v = blockIdx.x * kBlock + threadIdx.x;
+        const uint64_t k0 = entry_place(e);
+        const uint32_t s = entry_members(e), v = blockIdx.x * kBlock + threadIdx.x;
         if (v < s && s <= kMaxCluster) lg.labels[k0 + v] = v;
         if (v == 0) lg.sweeps[item] = 0;
     }
@@ -335,8 +312,8 @@ void large_min_kernel(const unsigned long long* __restrict__ list, uint32_t n_it
 {
     for (uint32_t item = blockIdx.y; item < n_items; item += gridDim.y) {
         const unsigned long long e = list[item];
-        const uint64_t k0 = e >> 32;
-        const uint32_t s = uint32_t(e), v = blockIdx.x * kBlock + threadIdx.x;
+        const uint64_t k0 = entry_place(e);
+        const uint32_t s = entry_members(e), v = blockIdx.x * kBlock + threadIdx.x;
         if (blockIdx.x * kBlock >= s || s > kMaxCluster) continue;       // (the whole block)
         if (was && !was[item]) continue;                                 // (the whole block: the cluster is at rest)
         const bool live = v < s;
@@ -367,8 +344,8 @@ void large_jump_kernel(const unsigned long long* __restrict__ list, uint32_t n_i
 {
     for (uint32_t item = blockIdx.y; item < n_items; item += gridDim.y) {
         const unsigned long long e = list[item];
-        const uint64_t k0 = e >> 32;
-        const uint32_t s = uint32_t(e), v = blockIdx.x * kBlock + threadIdx.x;
+        const uint64_t k0 = entry_place(e);
+        const uint32_t s = entry_members(e), v = blockIdx.x * kBlock + threadIdx.x;
         if (blockIdx.x * kBlock >= s || s > kMaxCluster || !now[item]) continue;
         if (v < s) lg.labels[k0 + v] = lg.next[k0 + lg.next[k0 + v]];
         if (v == 0) { lg.sweeps[item] += 1u; atomicAdd(&counters->live, 1u); }
@@ -382,8 +359,8 @@ void large_finish_kernel(const unsigned long long* __restrict__ list, uint32_t n
 {
     for (uint32_t item = blockIdx.y; item < n_items; item += gridDim.y) {
         const unsigned long long e = list[item];
-        const uint64_t k0 = e >> 32;
-        const uint32_t s = uint32_t(e), v = blockIdx.x * kBlock + threadIdx.x;
+        const uint64_t k0 = entry_place(e);
+        const uint32_t s = entry_members(e), v = blockIdx.x * kBlock + threadIdx.x;
         if (blockIdx.x * kBlock >= s || s > kMaxCluster) continue;
         uint32_t label = 0;
         if (v < s) { label = lg.labels[k0 + v]; owner_out[perm[k0 + v]] = perm[k0 + label]; }
@@ -397,30 +374,14 @@ void large_finish_kernel(const unsigned long long* __restrict__ list, uint32_t n
     }
 }
 
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const char *pa = static_cast<const char*>(a), *pb = static_cast<const char*>(b);
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-
 struct SplitBuffers { uint32_t* head_place; Lists lists; Large large; };
 
 size_t carve_split(uint64_t n, uint64_t m, char* base, SplitBuffers& b)
 {
     Carver c{base};
     b.head_place = c.take<uint32_t>(m);
-    b.lists.of[0] = c.take<unsigned long long>(n / 2 + 1);                    // a listed cluster has two members at least,
-    b.lists.of[1] = c.take<unsigned long long>(n / (kSmall + 1) + 1);         // more than kSmall,
-    b.lists.of[2] = c.take<unsigned long long>(n / (kWave + 1) + 1);          // more than kWave,
-    b.lists.of[3] = c.take<unsigned long long>(n / (kBlockLimit + 1) + 1);    // more than kBlockLimit
-    const size_t large = n / (kBlockLimit + 1) + 1;
+    fqdclusters::take_lists(c, n, {1u, kSmall, kWave, kBlockLimit}, b.lists);
+    const size_t large = fqdclusters::list_room(n, kBlockLimit);
     b.large.labels = c.take<uint32_t>(n > kBlockLimit ? n : 0); b.large.next = c.take<uint32_t>(n > kBlockLimit ? n : 0);
     b.large.changed[0] = c.take<uint32_t>(large); b.large.changed[1] = c.take<uint32_t>(large); b.large.sweeps = c.take<uint32_t>(large);
     return c.used + 256;
@@ -439,21 +400,19 @@ int fqd_read_places(fqd_engine* e, const uint8_t* text, const uint64_t* id_start
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_read_places: bad arguments (info, the text, the ID lines' starts and lengths, and room for tile, x, y and surface of at most 2^32-2 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(text) || !on_device(id_start) || !on_device(id_len) || !on_device(tile) || !on_device(x) || !on_device(y) || !on_device(surface))
+    if (!all_on_device(text, id_start, id_len, tile, x, y, surface))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_read_places: the text and every array are device memory");
     hipStream_t s = fqd_internal_stream(e);
     void* scratch = nullptr;
     const int rc = fqd_internal_scratch(e, 1, 4096, &scratch);
     if (rc) return rc;
     Found* found = static_cast<Found*>(scratch);
-    FQD_TRY(e, hipMemsetAsync(found, 0, sizeof(Found), s));
-    FQD_TRY(e, hipMemsetAsync(&found->bad, 0xFF, sizeof(unsigned long long), s));
+    FQD_TRY(e, zero_counters(found, s, &Found::bad));
     hipLaunchKernelGGL(read_places_kernel, dim3(uint32_t((n + kTile - 1) / kTile)), dim3(kBlock), 0, s, text, id_start, id_len, n, tile, x, y, surface, found);
     FQD_TRY(e, hipGetLastError());
     Found got{};
-    FQD_TRY(e, hipMemcpyAsync(&got, found, sizeof got, hipMemcpyDeviceToHost, s));
-    FQD_TRY(e, hipStreamSynchronize(s));
-    if (got.bad != kNoBad) { info->bad_record = got.bad >> 3; info->bad_reason = uint32_t(got.bad & 7u); }
+    FQD_TRY(e, read_back(got, found, s));
+    if (got.bad != kNoBad) fqdclusters::bad_parts(got.bad, &info->bad_record, &info->bad_reason);
     info->other_surface = got.other;
     return FQD_OK;
 }
@@ -469,8 +428,7 @@ int fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_optical_split: bad arguments (the info, a distance of 1 .. 2^31-1, the order and its head flags, the text, the ID lines' starts, tile, x, y and surface, and room for the owners of at most 2^31-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(text) || !on_device(id_start) || !on_device(tile) || !on_device(x) || !on_device(y) ||
-        !on_device(surface) || !on_device(owner_out))
+    if (!all_on_device(perm, head, text, id_start, tile, x, y, surface, owner_out))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_optical_split: the text and every array are device memory");
     const size_t words = size_t(n) * sizeof(uint32_t);
     if (overlap(owner_out, words, perm, words) || overlap(owner_out, words, head, size_t(n)) || overlap(owner_out, words, id_start, 2 * words) ||
@@ -478,32 +436,21 @@ int fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
         overlap(owner_out, words, surface, words))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_optical_split: owner_out overlaps an input");
     hipStream_t stream = fqd_internal_stream(e);
-    auto clock = std::chrono::steady_clock::now();
-    auto stage = [&](int k) {                                   // (behind a wait of the call's own: what the stage cost, seen from the host)
-        const auto now = std::chrono::steady_clock::now();
-        out->stage_ms[k] = std::chrono::duration<float, std::milli>(now - clock).count();
-        clock = now;
-    };
+    StageTimer timer{out->stage_ms};
 
     // ---- heads ----
-    const uint32_t tiles = uint32_t((n + kOffTile - 1) / kOffTile);
-    void* small = nullptr;
-    int rc = fqd_internal_scratch(e, 1, (size_t(tiles) + 1) * sizeof(unsigned long long) + 256 + sizeof(Counters), &small);
+    TileScratch<Counters> slot;
+    int rc = slot.reserve(e, fqdclusters::tiles_of(n), stream, &Counters::over);
     if (rc) return rc;
-    unsigned long long* tile_sum = static_cast<unsigned long long*>(small);
-    unsigned long long* d_total = tile_sum + tiles;
-    Counters* counters = reinterpret_cast<Counters*>(static_cast<char*>(small) + (((size_t(tiles) + 1) * sizeof(unsigned long long) + 255) & ~size_t(255)));
-    FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
-    FQD_TRY(e, hipMemsetAsync(&counters->over, 0xFF, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(head_count_kernel, dim3(tiles), dim3(kBlock), 0, stream, perm, head, n, tile_sum, counters);
-    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile_sum, tiles, d_total);
-    FQD_TRY(e, hipGetLastError());
+    Counters* counters = slot.counters;
     unsigned long long m = 0;
     Counters got{};
-    FQD_TRY(e, hipMemcpyAsync(&m, d_total, sizeof m, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
-    if (got.bad || m == 0 || m > n)
+    bool fits = false;
+    rc = fqdclusters::count_heads(e, stream, slot, n, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(head_count_kernel, grid, block, 0, stream, perm, head, n, slot.tile_sum, counters);
+    }, &m, &got, &fits);
+    if (rc) return rc;
+    if (got.bad || !fits)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_optical_split: head[0] is not set, or the order names a record outside 0 .. n-1 (are perm and head those of fqd_group_owners over these records? nothing was written)");
     out->clusters_in = m;
 
@@ -512,16 +459,14 @@ int fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
     void* base = nullptr;
     if ((rc = fqd_internal_scratch(e, 0, carve_split(n, m, nullptr, b), &base))) return rc;
     (void)carve_split(n, m, static_cast<char*>(base), b);
-    hipLaunchKernelGGL(head_write_kernel, dim3(tiles), dim3(kBlock), 0, stream, head, n, uint64_t(m), static_cast<const unsigned long long*>(tile_sum),
-                       b.head_place);
+    fqdclusters::write_heads(stream, slot, head, n, m, b.head_place);
     hipLaunchKernelGGL(classify_kernel, dim3(uint32_t((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, static_cast<const uint32_t*>(b.head_place), perm,
                        uint64_t(m), n, b.lists, counters);
     FQD_TRY(e, hipGetLastError());
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, counters, stream));
     out->largest = got.largest;
-    stage(0);
-    if (got.over != ~0ull) {                                  // refused: owner_out stays as it is
+    timer.mark(0);
+    if (got.over != kNoBad) {                                 // refused: owner_out stays as it is
         out->over_limit_first = got.over >> 32;
         out->over_limit_members = uint32_t(got.over);
         return FQD_OK;
@@ -544,7 +489,7 @@ int fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
                            owner_out, counters);
     FQD_TRY(e, hipGetLastError());
     FQD_TRY(e, hipStreamSynchronize(stream));
-    stage(1);
+    timer.mark(1);
 
     // ---- the large tier: a launch a step, a question a sweep ----
     if (const uint32_t items = got.listed[3]) {
@@ -560,20 +505,18 @@ int fqd_optical_split(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
             hipLaunchKernelGGL(large_jump_kernel, grid, dim3(kBlock), 0, stream, list, items, b.large, static_cast<const uint32_t*>(now), counters);
             FQD_TRY(e, hipGetLastError());
             uint32_t live = 0;
-            FQD_TRY(e, hipMemcpyAsync(&live, &counters->live, sizeof live, hipMemcpyDeviceToHost, stream));
-            FQD_TRY(e, hipStreamSynchronize(stream));
+            FQD_TRY(e, read_back(live, &counters->live, stream));
             if (!live) break;
         }
         FQD_TRY(e, hipMemsetAsync(b.large.changed[0], 0, size_t(items) * sizeof(uint32_t), stream));
         hipLaunchKernelGGL(large_finish_kernel, grid, dim3(kBlock), 0, stream, list, items, perm, b.large, b.large.changed[0], owner_out, counters);
         FQD_TRY(e, hipGetLastError());
     }
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, counters, stream));
     out->clusters_out = got.singles + got.groups;
     out->split = got.split;
     out->sweeps = got.sweeps;
-    stage(2);
+    timer.mark(2);
     return FQD_OK;
 }
 

@@ -79,13 +79,6 @@ size_t carve_group(uint64_t n, char* base, GroupBuffers& b)
 }
 
 // Is p memory the device can be handed?  Asked of the runtime's bookkeeping: nothing is allocated or touched.
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 } // namespace
 
 extern "C" {
@@ -97,7 +90,7 @@ int fqd_owners(fqd_engine* e, const uint8_t* keep, const uint32_t* link, uint64_
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_owners: bad arguments (keep flags, links and room for the owners of at most 2^32-2 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(keep) || !on_device(link) || !on_device(owner))
+    if (!all_on_device(keep, link, owner))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_owners: keep, link and owner are device memory");
     hipStream_t s = fqd_internal_stream(e);
     void* small = nullptr;
@@ -122,7 +115,7 @@ int fqd_group_owners(fqd_engine* e, const uint32_t* owner, uint64_t n, uint32_t*
     if (n_clusters) *n_clusters = 0;
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(owner) || !on_device(perm) || !on_device(head))
+    if (!all_on_device(owner, perm, head))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_group_owners: owner, perm and head are device memory");
     hipStream_t s = fqd_internal_stream(e);
     GroupBuffers b{};
@@ -151,7 +144,7 @@ int fqd_heads_to_keep(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_heads_to_keep: bad arguments (the order, its head flags and room for the keep flags of at most 2^32-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(keep))
+    if (!all_on_device(perm, head, keep))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_heads_to_keep: perm, head and keep are device memory");
     hipStream_t s = fqd_internal_stream(e);
     hipLaunchKernelGGL(heads_to_keep_kernel, dim3(grid_for(n, kBlock, 4096)), dim3(kBlock), 0, s, perm, head, n, keep);

@@ -87,8 +87,8 @@ void record_offsets_kernel(Mate m0, Mate m1, uint64_t n, const unsigned long lon
 }
 
 // Compaction of byte flags by the same scan (a count of the flags a tile into tile_start, scan_tiles_kernel, then this):
-// head_place[j] = the place of the j-th set flag of head[0 .. n), for j < m.  Used by fqd_optical.hip and
-// fqd_consensus.hip; the other units that include this header do not launch it, hence [[maybe_unused]].
+// head_place[j] = the place of the j-th set flag of head[0 .. n), for j < m.  Launched by fqd_clusters.hpp's write_heads;
+// the other units that include this header do not launch it, hence [[maybe_unused]].
 [[maybe_unused]] __global__ __launch_bounds__(kBlock)
 void head_write_kernel(const uint8_t* __restrict__ head, uint64_t n, uint64_t m, const unsigned long long* __restrict__ tile_start,
                        uint32_t* __restrict__ head_place)

@@ -208,13 +208,6 @@ void copy_labelled_kernel(const uint8_t* __restrict__ src, const uint64_t* __res
 }
 
 // Is p memory the device can be handed?  Asked of the runtime's bookkeeping: nothing is allocated or touched.
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 struct SizeBuffers { uint32_t* tile; fqd_size_levels* levels; };
 
 size_t carve_sizes(uint32_t tiles, char* base, SizeBuffers& b)
@@ -237,7 +230,7 @@ int fqd_cluster_sizes(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_cluster_sizes: bad arguments (the order, its head flags and room for the sizes of at most 2^31-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(size))
+    if (!all_on_device(perm, head, size))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_cluster_sizes: perm, head and size are device memory");
     hipStream_t s = fqd_internal_stream(e);
     uint8_t head0 = 0;
@@ -269,8 +262,7 @@ int fqd_size_labels(fqd_engine* e, const uint8_t* text, const uint64_t* start, c
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_labels: bad arguments (the text, the records' starts, ID line lengths, sizes, keep flags and cluster sizes, and room for label_at and out_size of at most 2^32-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(text) || !on_device(start) || !on_device(id_len) || !on_device(rec_size) || !on_device(keep) || !on_device(size) ||
-        !on_device(label_at) || !on_device(out_size))
+    if (!all_on_device(text, start, id_len, rec_size, keep, size, label_at, out_size))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_labels: the text and every array are device memory");
     hipStream_t s = fqd_internal_stream(e);
     void* small = nullptr;

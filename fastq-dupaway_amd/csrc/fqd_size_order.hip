@@ -164,13 +164,6 @@ void take_u32_kernel(const uint32_t* __restrict__ values, const uint32_t* __rest
 }
 
 // Is p memory the device can be handed?  Asked of the runtime's bookkeeping: nothing is allocated or touched.
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 struct CountBuffers { OrderStats* stats; unsigned long long* total; unsigned long long* tile; };
 
 size_t carve_counts(uint32_t tiles, char* base, CountBuffers& b)
@@ -208,7 +201,7 @@ int fqd_size_filter(fqd_engine* e, const uint32_t* size, uint64_t n, uint32_t mi
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_filter: bad arguments (the sizes and keep flags of at most 2^31-1 records, 1 <= min_size <= 2^31-1, max_size 0 for none or min_size <= max_size <= 2^31-1)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(size) || !on_device(keep)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_filter: size and keep are device memory");
+    if (!all_on_device(size, keep)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_filter: size and keep are device memory");
     hipStream_t s = fqd_internal_stream(e);
     void* small = nullptr;
     const int rc = fqd_internal_scratch(e, 1, 4096, &small);
@@ -246,7 +239,7 @@ int fqd_size_order_ex(fqd_engine* e, const uint32_t* perm, const uint8_t* head, 
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_order: bad arguments (the order, its head flags, the sizes and keep flags of at most 2^31-1 records, room for the written order and for its length)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(size) || !on_device(keep) || !on_device(order))
+    if (!all_on_device(perm, head, size, keep, order))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_order: perm, head, size, keep and order are device memory");
     hipStream_t s = fqd_internal_stream(e);
     uint8_t head0 = 0;
@@ -304,7 +297,7 @@ int fqd_take_u32(fqd_engine* e, const uint32_t* values, const uint32_t* idx, uin
     if (n && (!values || !idx || !out)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_take_u32: bad arguments");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(values) || !on_device(idx) || !on_device(out)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_take_u32: values, idx and out are device memory");
+    if (!all_on_device(values, idx, out)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_take_u32: values, idx and out are device memory");
     hipLaunchKernelGGL(take_u32_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, fqd_internal_stream(e), values, idx, n, out);
     FQD_TRY(e, hipGetLastError());
     return FQD_OK;

@@ -17,6 +17,7 @@
 //   copy     copy_relabelled_kernel: copy_labelled_kernel with the cut.
 #include <hip/hip_runtime.h>
 
+#include "fqd_clusters_core.hpp"
 #include "fqd_internal.hpp"
 #include "fqd_size_core.hpp"
 #include "fqd_sizein_core.hpp"
@@ -34,7 +35,7 @@ constexpr uint32_t kWaveTile = 64;                           // records a wave (
 constexpr uint32_t kTile = kWaveTile * (kBlock / 64);        // records a block (parse)
 constexpr uint32_t kNone = fqdsizein::kNone;
 constexpr uint32_t kSpanLanes = fqdsize::kSpanLanes;
-constexpr unsigned long long kNoBad = ~0ull;
+using fqdclusters::kNoBad;
 
 static_assert(sizeof(Seg) == 16, "a tile value is sixteen bytes");
 
@@ -100,7 +101,7 @@ void size_annotations_kernel(const uint8_t* __restrict__ text, const uint64_t* _
         if (weight) weight[mine] = my.weight;
         if (label_at) label_at[mine] = my.label_at;
         if (cut) cut[mine] = my.cut;
-        if (my.reason) word = (static_cast<unsigned long long>(mine) << 3) | my.reason;
+        if (my.reason) word = fqdclusters::bad_word(mine, my.reason);
         else if (my.cut) { annotated = 1; extra = my.weight - 1u; }
     }
     word = fqdwave::wave_min(word);
@@ -302,13 +303,6 @@ void copy_relabelled_kernel(const uint8_t* __restrict__ src, const uint64_t* __r
 }
 
 // Is p memory the device can be handed?  Asked of the runtime's bookkeeping: nothing is allocated or touched.
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 struct WeightBuffers { Seg* tile; fqd_size_levels* levels; WeightScratch* out; };
 
 size_t carve_weights(uint32_t tiles, char* base, WeightBuffers& b)
@@ -333,7 +327,7 @@ int fqd_size_annotations(fqd_engine* e, const uint8_t* text, const uint64_t* sta
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_annotations: bad arguments (info, the text, and the ID lines' starts and lengths of at most 2^32-2 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(text) || !on_device(start) || !on_device(id_len) || (expect && !on_device(expect)) || (weight && !on_device(weight)) ||
+    if (!all_on_device(text, start, id_len) || (expect && !on_device(expect)) || (weight && !on_device(weight)) ||
         (label_at && !on_device(label_at)) || (cut && !on_device(cut)))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_annotations: the text and every array are device memory");
     hipStream_t s = fqd_internal_stream(e);
@@ -341,15 +335,13 @@ int fqd_size_annotations(fqd_engine* e, const uint8_t* text, const uint64_t* sta
     const int rc = fqd_internal_scratch(e, 1, 4096, &scratch);
     if (rc) return rc;
     Found* found = static_cast<Found*>(scratch);
-    FQD_TRY(e, hipMemsetAsync(found, 0, sizeof(Found), s));
-    FQD_TRY(e, hipMemsetAsync(&found->bad, 0xFF, sizeof(unsigned long long), s));
+    FQD_TRY(e, zero_counters(found, s, &Found::bad));
     hipLaunchKernelGGL(size_annotations_kernel, dim3(uint32_t((n + kTile - 1) / kTile)), dim3(kBlock), 0, s, text, start, id_len, n, expect,
                        weight, label_at, cut, found);
     FQD_TRY(e, hipGetLastError());
     Found got{};
-    FQD_TRY(e, hipMemcpyAsync(&got, found, sizeof got, hipMemcpyDeviceToHost, s));
-    FQD_TRY(e, hipStreamSynchronize(s));
-    if (got.bad != kNoBad) { info->bad_record = got.bad >> 3; info->bad_reason = uint32_t(got.bad & 7u); }
+    FQD_TRY(e, read_back(got, found, s));
+    if (got.bad != kNoBad) fqdclusters::bad_parts(got.bad, &info->bad_record, &info->bad_reason);
     info->annotated = got.annotated;
     info->total_weight = n + got.extra;
     return FQD_OK;
@@ -365,7 +357,7 @@ int fqd_cluster_weights(fqd_engine* e, const uint32_t* perm, const uint8_t* head
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_cluster_weights: bad arguments (info, the order, its head flags, the weights and room for the sizes of at most 2^31-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(perm) || !on_device(head) || !on_device(weight) || !on_device(size))
+    if (!all_on_device(perm, head, weight, size))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_cluster_weights: perm, head, weight and size are device memory");
     hipStream_t s = fqd_internal_stream(e);
     uint8_t head0 = 0;
@@ -379,8 +371,7 @@ int fqd_cluster_weights(fqd_engine* e, const uint32_t* perm, const uint8_t* head
     if (rc) return rc;
     (void)carve_weights(tiles, static_cast<char*>(base), b);
     if (levels) FQD_TRY(e, hipMemsetAsync(b.levels, 0, sizeof(fqd_size_levels), s));
-    FQD_TRY(e, hipMemsetAsync(b.out, 0, sizeof(WeightScratch), s));
-    FQD_TRY(e, hipMemsetAsync(&b.out->over_record, 0xFF, sizeof(unsigned long long), s));
+    FQD_TRY(e, zero_counters(b.out, s, &WeightScratch::over_record));
     hipLaunchKernelGGL(weight_tiles_kernel, dim3(tiles), dim3(kBlock), 0, s, perm, head, weight, n, b.tile);
     hipLaunchKernelGGL(weight_carry_kernel, dim3(1), dim3(1024), 0, s, b.tile, tiles);
     hipLaunchKernelGGL(weight_places_kernel, dim3(tiles), dim3(kBlock), 0, s, perm, head, weight, n, static_cast<const Seg*>(b.tile), size,
@@ -399,8 +390,7 @@ int fqd_cluster_weights(fqd_engine* e, const uint32_t* perm, const uint8_t* head
         hipLaunchKernelGGL(weight_places_kernel, dim3(tiles), dim3(kBlock), 0, s, perm, head, weight, n, static_cast<const Seg*>(b.tile), size,
                            static_cast<fqd_size_levels*>(nullptr), b.out, uint32_t(got.over_record));
         FQD_TRY(e, hipGetLastError());
-        FQD_TRY(e, hipMemcpyAsync(&got.over_sum, &b.out->over_sum, sizeof got.over_sum, hipMemcpyDeviceToHost, s));
-        FQD_TRY(e, hipStreamSynchronize(s));
+        FQD_TRY(e, read_back(got.over_sum, &b.out->over_sum, s));
         info->over_record = got.over_record;
         info->over_sum = got.over_sum;
         if (levels) *levels = fqd_size_levels{};
@@ -416,7 +406,7 @@ int fqd_size_relabel(fqd_engine* e, const uint32_t* rec_size, const uint8_t* kee
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_relabel: bad arguments (the records' sizes, keep flags, cluster sizes and cuts, and room for out_size of at most 2^32-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(rec_size) || !on_device(keep) || !on_device(size) || !on_device(cut) || !on_device(out_size))
+    if (!all_on_device(rec_size, keep, size, cut, out_size))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_relabel: every array is device memory");
     hipStream_t s = fqd_internal_stream(e);
     void* small = nullptr;
@@ -427,8 +417,7 @@ int fqd_size_relabel(fqd_engine* e, const uint32_t* rec_size, const uint8_t* kee
     hipLaunchKernelGGL(size_relabel_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, s, rec_size, keep, size, cut, n, out_size, n_bad);
     FQD_TRY(e, hipGetLastError());
     unsigned long long bad = 0;
-    FQD_TRY(e, hipMemcpyAsync(&bad, n_bad, sizeof bad, hipMemcpyDeviceToHost, s));
-    FQD_TRY(e, hipStreamSynchronize(s));
+    FQD_TRY(e, read_back(bad, n_bad, s));
     if (bad) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_size_relabel: a kept record has cluster size 0 (are keep and size those of one grouping, after fqd_heads_to_keep?)");
     return FQD_OK;
 }

@@ -106,13 +106,6 @@ void canon_kernel(Mate m0, Mate m1, uint64_t n, uint8_t* __restrict__ out, const
     if (lane == 0 && turned) atomicAdd(n_flipped, static_cast<unsigned long long>(turned));
 }
 
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 bool is_uniform(const fqd_reads& r) { return r.offsets == nullptr && r.lengths == nullptr; }
 
 } // namespace
@@ -144,10 +137,10 @@ int fqd_canonical_reads(fqd_engine* e, const fqd_reads* seg, uint64_t n, uint8_t
     }
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
     for (int s = 0; s < S; ++s)
-        if ((seg[s].bases && !on_device(seg[s].bases)) || (seg[s].offsets && (!on_device(seg[s].offsets) || !on_device(seg[s].lengths))))
+        if ((seg[s].bases && !on_device(seg[s].bases)) || (seg[s].offsets && !all_on_device(seg[s].offsets, seg[s].lengths)))
             return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_canonical_reads: the reads and their descriptors are device memory");
-    if ((out && !on_device(out)) || !on_device(out_off0) || !on_device(out_len0) || !on_device(flipped) ||
-        (S == 2 && (!on_device(out_off1) || !on_device(out_len1))))
+    if ((out && !on_device(out)) || !all_on_device(out_off0, out_len0, flipped) ||
+        (S == 2 && !all_on_device(out_off1, out_len1)))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_canonical_reads: out, the offsets, the lengths and flipped are device memory");
     hipStream_t stream = fqd_internal_stream(e);
     const Mate m0{seg[0].bases, seg[0].offsets, seg[0].lengths, seg[0].uniform_len, seg[0].uniform_stride};

@@ -19,6 +19,7 @@
 //            The sequence follows with fqdstrand::copy_lane: 16-byte loads and stores, the destination at any alignment.
 #include <hip/hip_runtime.h>
 
+#include "fqd_clusters_core.hpp"
 #include "fqd_internal.hpp"
 #include "fqd_record_scan.hpp"
 #include "fqd_strand_core.hpp"
@@ -31,7 +32,7 @@ constexpr uint32_t kGroup = 16;                              // lanes a record
 constexpr uint32_t kWaveTile = 64;                           // records a wave
 constexpr uint32_t kTile = kWaveTile * (kBlock / 64);        // records a block of the two kernels
 constexpr int kOffTile = fqdscan::kOffTile;                  // records a block of the scan's two passes
-constexpr unsigned long long kNoBad = ~0ull;
+using fqdclusters::kNoBad;
 
 using fqdscan::Mate;
 using fqdscan::mate_off;
@@ -99,7 +100,7 @@ void umi_find_kernel(const uint8_t* __restrict__ text, const uint64_t* __restric
     unsigned long long word = kNoBad;
     if (mine < n) {
         umi_off[mine] = my_off;
-        if (my_reason) word = (static_cast<unsigned long long>(mine) << 3) | my_reason;
+        if (my_reason) word = fqdclusters::bad_word(mine, my_reason);
     }
     word = fqdwave::wave_min(word);
     if (lane == 0 && word != kNoBad) atomicMin(&found->bad, word);
@@ -132,13 +133,6 @@ void umi_pack_kernel(const uint8_t* __restrict__ text, const uint64_t* __restric
     if (mine < n) out_len[mine] = lb + len_a;
 }
 
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 bool is_uniform(const fqd_reads& r) { return r.offsets == nullptr && r.lengths == nullptr; }
 
 } // namespace
@@ -154,7 +148,7 @@ int fqd_umi_find(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, c
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_find: bad arguments (info, a separator ':' or '_', the text, and the ID lines and room for the offsets of at most 2^32-2 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(text) || !on_device(id_start) || !on_device(id_len) || !on_device(umi_off))
+    if (!all_on_device(text, id_start, id_len, umi_off))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_find: the text, the ID lines' starts and lengths and umi_off are device memory");
     hipStream_t stream = fqd_internal_stream(e);
     void* scratch = nullptr;
@@ -167,12 +161,11 @@ int fqd_umi_find(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, c
     hipLaunchKernelGGL(umi_find_kernel, dim3(blocks), dim3(kBlock), 0, stream, text, id_start, id_len, n, uint32_t(sep), 0, found, umi_off);
     FQD_TRY(e, hipGetLastError());
     Found got{};
-    FQD_TRY(e, hipMemcpyAsync(&got, found, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, found, stream));
     info->umi_len = got.ulen;
     info->joiners = got.joiners;
     info->n_bases = got.ulen - uint32_t(__builtin_popcountll(got.joiners));
-    if (got.bad != kNoBad) { info->bad_record = got.bad >> 3; info->bad_reason = uint32_t(got.bad & 7u); }
+    if (got.bad != kNoBad) fqdclusters::bad_parts(got.bad, &info->bad_record, &info->bad_reason);
     return FQD_OK;
 }
 
@@ -191,10 +184,10 @@ int fqd_umi_reads(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, 
     if (!is_uniform(m) && (!m.offsets || !m.lengths)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_reads: offsets and lengths go together");
     if (!m.bases && !(is_uniform(m) && m.uniform_len == 0)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_reads: null bases");
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(text) || !on_device(id_start) || !on_device(umi_off) || (m.bases && !on_device(m.bases)) ||
-        (m.offsets && (!on_device(m.offsets) || !on_device(m.lengths))))
+    if (!all_on_device(text, id_start, umi_off) || (m.bases && !on_device(m.bases)) ||
+        (m.offsets && !all_on_device(m.offsets, m.lengths)))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_reads: the text, the ID lines' starts, the UMI offsets, the reads and their descriptors are device memory");
-    if ((out && !on_device(out)) || !on_device(out_off) || !on_device(out_len))
+    if ((out && !on_device(out)) || !all_on_device(out_off, out_len))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_reads: out, the offsets and the lengths are device memory");
     hipStream_t stream = fqd_internal_stream(e);
     fqdumi::Table table;

@@ -2,15 +2,16 @@
 // clusters of one sequence that differ in a base or two merged by UMI-tools' directional rule.  Rule and proofs:
 // fqd_umi_merge_core.hpp.
 //
-//   nodes    node_count_kernel + scan_tiles_kernel + node_write_kernel (the three launches of fqd_record_scan.hpp's scan,
-//            kOffTile records a block): the records that own themselves in the exact grouping, compacted in input order as
-//            (key = their owner in the grouping by sequence, value = the record).  The count comes back to size the rest.
+//   nodes    fqd_clusters.hpp's heads phase over another flag: node_count_kernel (tile_count with "the record owns itself in
+//            the exact grouping", and the checks of the owners) + scan_tiles_kernel + node_write_kernel, which is this unit's:
+//            the nodes compacted in input order as (key = their owner in the grouping by sequence, value = the record).
+//            The count comes back to size the rest.
 //   group    fqd_internal_radix_sort over the bits of n - 1: stable, so the nodes of a sequence stand together in the order
 //            of their first records.  node_pack_kernel then packs every node's B(U) at its sorted place, four bits a base
 //            through the shape's table (umi_pack_kernel's gather), and fetches its count.
 //   classes  classify_kernel, a lane a sorted place: a place that starts no group is done; a group of ONE node — nearly all
 //            of them — is settled there with one store; a longer one is measured by a gallop over the equal keys and put
-//            on the list of its size class, a wave adding to a list with one atomic.  A group beyond the limit is reported
+//            on the list of its size class (list_append).  A group beyond the limit is reported
 //            through one 64-bit atomicMin of (first record << 32 | nodes).  The three counts come back for the grids.
 //   merge    merge_lanes_kernel<8>: eight lanes a group, eight groups a wave; merge_lanes_kernel<64>: a wave a group.  A
 //            lane holds its node's in-edges as a 64-bit mask and its label; a sweep reads the other lanes' labels across
@@ -20,11 +21,8 @@
 //   spread   spread_kernel: owner_out[i] = what the node of owner_exact[i] was given.  The only writer of owner_out.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-
-#include "fqd_internal.hpp"
+#include "fqd_clusters.hpp"
 #include "fqd_owner_core.hpp"
-#include "fqd_record_scan.hpp"
 #include "fqd_umi_merge_core.hpp"
 
 namespace {
@@ -38,7 +36,8 @@ constexpr unsigned long long kNoGroup = ~0ull;
 static_assert(kNodesPerThread * kMergeBlock == int(fqdmerge::kMaxGroup), "a block's threads share the largest group evenly");
 static_assert(fqdmerge::kWave == 64 && 64 % fqdmerge::kSmall == 0, "the lane kernels' groups tile a wave");
 
-using fqdscan::scan_tiles_kernel;
+using fqdclusters::entry_members;
+using fqdclusters::entry_place;
 using fqdwave::wave_max;
 using fqdwave::wave_sum;
 
@@ -57,22 +56,15 @@ __global__ __launch_bounds__(kBlock)
 void node_count_kernel(const uint32_t* __restrict__ owner_exact, const uint32_t* __restrict__ owner_seq, const uint32_t* __restrict__ size,
                        uint64_t n, unsigned long long* __restrict__ tile_sum, Counters* counters)
 {
-    __shared__ unsigned long long ws[4];
-    const uint64_t base = uint64_t(blockIdx.x) * kOffTile + uint64_t(threadIdx.x) * 8u;
-    unsigned long long s = 0;
     uint32_t bad = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint64_t k = base + uint32_t(e);
-        if (k >= n) continue;
+    fqdclusters::tile_count<4>(n, tile_sum, [&](uint64_t k) __attribute__((always_inline)) {
         const uint32_t o = owner_exact[k];
-        if (o == k) { s += 1; bad += size[k] == 0 || owner_seq[k] > k; }
+        if (o == k) bad += size[k] == 0 || owner_seq[k] > k;
         else bad += o > k || owner_exact[o] != o || owner_seq[k] > k;    // (an owner is its cluster's first record: never behind it)
-    }
+        return o == k;
+    });
     bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad) atomicAdd(&counters->bad, static_cast<unsigned long long>(bad));
-    s = fqdwave::block_total<4>(s, ws);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(kBlock)
@@ -122,7 +114,7 @@ __device__ __forceinline__ uint64_t group_end(const uint64_t* __restrict__ key, 
     return hi;
 }
 
-struct Lists { unsigned long long* of[3]; };                 // entries (first sorted place << 32 | nodes)
+using Lists = fqdclusters::Lists<3>;                         // the small, wave and block lists; entries (first sorted place << 32 | nodes)
 
 __global__ __launch_bounds__(kBlock)
 void classify_kernel(const uint64_t* __restrict__ key, const uint32_t* __restrict__ first, uint64_t m, uint32_t* __restrict__ given,
@@ -136,11 +128,7 @@ void classify_kernel(const uint64_t* __restrict__ key, const uint32_t* __restric
         else s = uint32_t(group_end(key, m, k) - k);
     }
     const uint32_t cls = s < 2u ? 3u : s <= fqdmerge::kSmall ? 0u : s <= fqdmerge::kWave ? 1u : s <= fqdmerge::kMaxGroup ? 2u : 4u;
-#pragma unroll
-    for (uint32_t c = 0; c < 3u; ++c) {
-        const uint32_t at = fqdwave::ballot_append(cls == c, &counters->listed[c]);
-        if (cls == c) lists.of[c][at] = (static_cast<unsigned long long>(k) << 32) | s;
-    }
+    fqdclusters::list_append(lists, counters->listed, cls, uint32_t(k), s);   // (k < m < 2^31)
     if (cls == 4u) { atomicMin(&counters->over, (static_cast<unsigned long long>(first[k]) << 32) | s); atomicAdd(&counters->over_groups, 1u); }
     const uint32_t largest = wave_max(s);
     if (lane == 0 && largest > 1u) atomicMax(&counters->largest, largest);
@@ -159,7 +147,7 @@ void merge_lanes_kernel(const unsigned long long* __restrict__ list, uint32_t n_
     const uint64_t item = (blockIdx.x * uint64_t(kBlock) + threadIdx.x) / G;
     uint32_t s = 0;
     uint64_t k0 = 0;
-    if (item < n_items) { const unsigned long long e = list[item]; k0 = e >> 32; s = uint32_t(e); }
+    if (item < n_items) { const unsigned long long e = list[item]; k0 = entry_place(e); s = entry_members(e); }
     if (s > G) s = 0;                                        // (no list holds such an entry)
     const bool live = gl < s;
     const uint64_t* __restrict__ P = packed + k0 * W;
@@ -195,8 +183,8 @@ void merge_block_kernel(const unsigned long long* __restrict__ list, const uint6
     __shared__ unsigned long long labels[fqdmerge::kMaxGroup];
     __shared__ uint32_t lowest[fqdmerge::kMaxGroup];         // per root: the lowest place of its cluster
     const unsigned long long e = list[blockIdx.x];
-    const uint64_t k0 = e >> 32;
-    uint32_t s = uint32_t(e);
+    const uint64_t k0 = entry_place(e);
+    uint32_t s = entry_members(e);
     if (s > fqdmerge::kMaxGroup) s = 0;                      // (no list holds such an entry)
     const uint64_t* __restrict__ P = packed + k0 * W;
     const uint32_t* __restrict__ C = count + k0;
@@ -246,13 +234,6 @@ void owners_to_keep_kernel(const uint32_t* __restrict__ owner, uint64_t n, uint8
     for (uint64_t i = blockIdx.x * uint64_t(kBlock) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kBlock) keep[i] = owner[i] == i ? 1 : 0;
 }
 
-bool on_device(const void* p)
-{
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
 struct MergeBuffers {
     uint64_t* keys[2]; uint32_t* vals[2]; uint32_t *counts, *tot;
     uint64_t* packed; uint32_t* count; uint32_t* given; Lists lists;
@@ -265,9 +246,7 @@ size_t carve_merge(uint64_t n, uint64_t m, uint32_t W, char* base, MergeBuffers&
     b.vals[0] = c.take<uint32_t>(m); b.vals[1] = c.take<uint32_t>(m);
     b.counts = c.take<uint32_t>(fqd_internal_radix_counts(m)); b.tot = c.take<uint32_t>(256);
     b.packed = c.take<uint64_t>(m * W); b.count = c.take<uint32_t>(m); b.given = c.take<uint32_t>(n);
-    b.lists.of[0] = c.take<unsigned long long>(m / 2 + 1);                          // a listed group has two nodes at least,
-    b.lists.of[1] = c.take<unsigned long long>(m / (fqdmerge::kSmall + 1) + 1);     // more than kSmall,
-    b.lists.of[2] = c.take<unsigned long long>(m / (fqdmerge::kWave + 1) + 1);      // more than kWave
+    fqdclusters::take_lists(c, m, {1u, fqdmerge::kSmall, fqdmerge::kWave}, b.lists);   // (groups among the m nodes)
     return c.used + 256;
 }
 
@@ -290,49 +269,37 @@ int fqd_umi_merge(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, 
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_merge: info is not what fqd_umi_find leaves for records it does not refuse");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(text) || !on_device(id_start) || !on_device(umi_off) || !on_device(owner_exact) || !on_device(owner_seq) ||
-        !on_device(size) || !on_device(owner_out))
+    if (!all_on_device(text, id_start, umi_off, owner_exact, owner_seq, size, owner_out))
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_merge: the text and every array are device memory");
     hipStream_t stream = fqd_internal_stream(e);
     fqdumi::Table table;
     const uint32_t lb = fqdumi::bases_table(info->umi_len, info->joiners, &table), W = fqdmerge::words(lb);
-    auto clock = std::chrono::steady_clock::now();
-    auto stage = [&](int k) {                                   // (behind a wait of the call's own: what the stage cost, seen from the host)
-        const auto now = std::chrono::steady_clock::now();
-        out->stage_ms[k] = std::chrono::duration<float, std::milli>(now - clock).count();
-        clock = now;
-    };
+    StageTimer timer{out->stage_ms};
 
     // ---- nodes ----
-    const uint32_t tiles = uint32_t((n + kOffTile - 1) / kOffTile);
-    void* small = nullptr;
-    int rc = fqd_internal_scratch(e, 1, (size_t(tiles) + 1) * sizeof(unsigned long long) + 256 + sizeof(Counters), &small);
+    TileScratch<Counters> slot;
+    int rc = slot.reserve(e, fqdclusters::tiles_of(n), stream, &Counters::over);
     if (rc) return rc;
-    unsigned long long* tile = static_cast<unsigned long long*>(small);
-    unsigned long long* d_total = tile + tiles;
-    Counters* counters = reinterpret_cast<Counters*>(static_cast<char*>(small) + (((size_t(tiles) + 1) * sizeof(unsigned long long) + 255) & ~size_t(255)));
-    FQD_TRY(e, hipMemsetAsync(counters, 0, sizeof(Counters), stream));
-    FQD_TRY(e, hipMemsetAsync(&counters->over, 0xFF, sizeof(unsigned long long), stream));
-    hipLaunchKernelGGL(node_count_kernel, dim3(tiles), dim3(kBlock), 0, stream, owner_exact, owner_seq, size, n, tile, counters);
-    hipLaunchKernelGGL(scan_tiles_kernel<unsigned long long>, dim3(1), dim3(1024), 0, stream, tile, tiles, d_total);
-    FQD_TRY(e, hipGetLastError());
+    Counters* counters = slot.counters;
     unsigned long long m = 0;
     Counters got{};
-    FQD_TRY(e, hipMemcpyAsync(&m, d_total, sizeof m, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
-    if (got.bad || m == 0 || m > n)
+    bool fits = false;
+    rc = fqdclusters::count_heads(e, stream, slot, n, [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(node_count_kernel, grid, block, 0, stream, owner_exact, owner_seq, size, n, slot.tile_sum, counters);
+    }, &m, &got, &fits);
+    if (rc) return rc;
+    if (got.bad || !fits)
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_umi_merge: an owner that stands behind its record, or a record that owns itself with size 0 (are owner_exact, owner_seq and size those of fqd_owners and fqd_cluster_sizes over these records? nothing was written)");
     out->nodes = m;
-    stage(0);
+    timer.mark(0);
 
     // ---- group ----
     MergeBuffers b{};
     void* base = nullptr;
     if ((rc = fqd_internal_scratch(e, 0, carve_merge(n, m, W, nullptr, b), &base))) return rc;
     (void)carve_merge(n, m, W, static_cast<char*>(base), b);
-    hipLaunchKernelGGL(node_write_kernel, dim3(tiles), dim3(kBlock), 0, stream, owner_exact, owner_seq, n, uint64_t(m),
-                       static_cast<const unsigned long long*>(tile), b.keys[0], b.vals[0]);
+    hipLaunchKernelGGL(node_write_kernel, dim3(slot.tiles), dim3(kBlock), 0, stream, owner_exact, owner_seq, n, uint64_t(m),
+                       static_cast<const unsigned long long*>(slot.tile_sum), b.keys[0], b.vals[0]);
     int cur = 0;
     if ((rc = fqd_internal_radix_sort(e, stream, b.keys, b.vals, b.counts, b.tot, m, fqdowner::group_bits(n), &cur))) return rc;
     const uint64_t* key = b.keys[cur];
@@ -344,11 +311,10 @@ int fqd_umi_merge(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, 
     hipLaunchKernelGGL(classify_kernel, dim3(uint32_t((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, key, first, uint64_t(m), b.given,
                        b.lists, counters);
     FQD_TRY(e, hipGetLastError());
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, counters, stream));
     out->groups = uint64_t(got.listed[0]) + got.listed[1] + got.listed[2] + got.over_groups;
     out->largest = got.largest ? got.largest : 1u;
-    stage(1);
+    timer.mark(1);
     if (got.over != kNoGroup) {                               // refused: owner_out stays as it is
         out->over_limit_first = got.over >> 32;
         out->over_limit_nodes = uint32_t(got.over);
@@ -370,11 +336,10 @@ int fqd_umi_merge(fqd_engine* e, const uint8_t* text, const uint64_t* id_start, 
                            static_cast<const uint64_t*>(b.packed), static_cast<const uint32_t*>(b.count), first, W, D, b.given, counters);
     hipLaunchKernelGGL(spread_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, stream, owner_exact, static_cast<const uint32_t*>(b.given), n, owner_out);
     FQD_TRY(e, hipGetLastError());
-    FQD_TRY(e, hipMemcpyAsync(&got, counters, sizeof got, hipMemcpyDeviceToHost, stream));
-    FQD_TRY(e, hipStreamSynchronize(stream));
+    FQD_TRY(e, read_back(got, counters, stream));
     out->merged = got.merged;
     out->sweeps = got.sweeps;
-    stage(2);
+    timer.mark(2);
     return FQD_OK;
 }
 
@@ -385,7 +350,7 @@ int fqd_owners_to_keep(fqd_engine* e, const uint32_t* owner, uint64_t n, uint8_t
         return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_owners_to_keep: bad arguments (the owners and room for the keep flags of at most 2^32-1 records)");
     if (n == 0) return FQD_OK;
     FQD_TRY(e, hipSetDevice(fqd_internal_device(e)));
-    if (!on_device(owner) || !on_device(keep)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_owners_to_keep: owner and keep are device memory");
+    if (!all_on_device(owner, keep)) return fqd_internal_fail(e, FQD_ERR_ARG, "fqd_owners_to_keep: owner and keep are device memory");
     hipLaunchKernelGGL(owners_to_keep_kernel, dim3(grid_for(n, kBlock, 8192)), dim3(kBlock), 0, fqd_internal_stream(e), owner, n, keep);
     FQD_TRY(e, hipGetLastError());
     return FQD_OK;

@@ -148,6 +148,9 @@ struct OrderedResidentRun {
         return true;
     }
 
+    // The sequences of file s where the record scan found them in the text.
+    fqd_reads reads_as_they_lie(int s) const { return fqd_reads{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].seq_off.p, dev[s].seq_len.p, 0, 0}; }
+
     // Stage 3, between the record scan and the submit loop.  FQD_FAST_STRAND=both: one fqd_canonical_reads over all n records.
     // FQD_FAST_UMI behind it: fqd_umi_find over file 1's ID lines, then fqd_umi_reads, which packs `UMI bases ‖ sequence` of
     // (the canonical) mate 1 for the submit loop's segment 0.  FQD_FAST_SIZEIN: fqd_size_annotations reads every record's weight
@@ -161,7 +164,7 @@ struct OrderedResidentRun {
             return format == Format::Fasta ? dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 3 * n)
                                            : (dev[s].text.used - std::min<uint64_t>(dev[s].text.used, 6 * n)) / 2 + 1;
         };
-        for (int s = 0; s < S; ++s) k.reads[s] = fqd_reads{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].seq_off.p, dev[s].seq_len.p, 0, 0};
+        for (int s = 0; s < S; ++s) k.reads[s] = reads_as_they_lie(s);
         if (fast.both_strands) {
             // the canonical sequences and their descriptors
             uint64_t bound = 0;
@@ -292,6 +295,19 @@ struct OrderedResidentRun {
         if (fast.centroid && !links.exact.p) links.exact.swap(replaced);
     }
 
+    // The tail of merge_near, merge_near_umi and split_optical: new_owner become THE owners (the replaced ones leave with the
+    // caller's buffer, or stay for the centroids), fqd_owners_to_keep makes the flags of them and fqd_group_owners groups the
+    // records once more, into the clusters the stage counted.  what: "merge" / "split", for the message.
+    void regroup_under(Links& links, Clusters& clusters, Device<uint32_t>& new_owner, uint64_t expected, const char* what)
+    {
+        links.owner.swap(new_owner);
+        keep_exact(links, new_owner);
+        engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
+        engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
+        if (clusters.count != expected)
+            throw DeviceError(std::string("GPU engine: internal error (the ") + what + " and the second grouping count different clusters)");
+    }
+
     // Stage 6: the duplicates are counted and, for the `linked` switches, the links resolved to the first record of every key
     // (fqd_owners; done already where the merge made the owners) and the records grouped by it (fqd_group_owners) ...
     void count_and_group(Links& links, Clusters& clusters)
@@ -313,14 +329,12 @@ struct OrderedResidentRun {
     }
 
     // FQD_FAST_HAMMING, behind the grouping: fqd_near_merge makes of the exact clusters — the reads as they lie in the files, the
-    // owners by key — the merged ones, each owned by its first record; the merged owners are THE owners from here on,
-    // fqd_owners_to_keep makes the flags of them and fqd_group_owners groups the records once more.
+    // owners by key — the merged ones, each owned by its first record; regroup_under makes the merged owners THE owners.
     void merge_near(Links& links, Clusters& clusters)
     {
         Device<uint32_t> merged_owner;
         merged_owner.reserve(n);
-        fqd_reads reads[2] = {};
-        for (int s = 0; s < S; ++s) reads[s] = fqd_reads{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].seq_off.p, dev[s].seq_len.p, 0, 0};
+        const fqd_reads reads[2] = {reads_as_they_lie(0), S == 2 ? reads_as_they_lie(1) : fqd_reads{}};
         fqd_near_info merged{};
         {
             StageClock::Scope t("fast: substitutions, exact clusters merged on the GPU");
@@ -331,12 +345,8 @@ struct OrderedResidentRun {
                                       std::to_string(fast.hamming + 1) + " segments their first mate is cut into; a group of at most " + std::to_string(merged.max_group) +
                                       " is compared (adapter dimers, amplicons: trim the reads or dereplicate them exactly first)");
             if (merged.nodes != clusters.count) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
-            links.owner.swap(merged_owner);                          // (the owners by key leave with this stage, or stay for the centroids)
-            keep_exact(links, merged_owner);
-            engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
-            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
+            regroup_under(links, clusters, merged_owner, merged.merged, "merge");   // (the owners by key leave with this stage, or stay for the centroids)
         }
-        if (clusters.count != merged.merged) throw DeviceError("GPU engine: internal error (the merge and the second grouping count different clusters)");
         near_taken = merged.nodes - merged.merged;
         if (StageClock::on())
             std::cerr << "fast: substitutions <= " << fast.hamming << ", " << near_taken << " of " << merged.nodes << " exact clusters merged into others, " << merged.pairs
@@ -346,14 +356,12 @@ struct OrderedResidentRun {
     // FQD_FAST_UMI_HAMMING, behind the grouping, where merge_near stands (the two never run together): fqd_near_merge_umi makes of
     // the exact clusters of the run keyed `UMI bases ‖ sequence` — the reads as they lie in the files, the exact owners, every
     // record's UMI field and, with FQD_FAST_UMI_MISMATCH, the merged owners as links — the molecules, each owned by its first
-    // record; their owners are THE owners from here on, fqd_owners_to_keep makes the flags of them and fqd_group_owners groups
-    // the records once more.  The clusters in front of the stage are the exact ones, or the merge's where it ran.
+    // record; regroup_under makes their owners THE owners.  The clusters in front of the stage are the exact ones, or the merge's.
     void merge_near_umi(Links& links, Clusters& clusters)
     {
         Device<uint32_t> merged_owner;
         merged_owner.reserve(n);
-        fqd_reads reads[2] = {};
-        for (int s = 0; s < S; ++s) reads[s] = fqd_reads{reinterpret_cast<const uint8_t*>(dev[s].text.p), dev[s].seq_off.p, dev[s].seq_len.p, 0, 0};
+        const fqd_reads reads[2] = {reads_as_they_lie(0), S == 2 ? reads_as_they_lie(1) : fqd_reads{}};
         const uint64_t before = fast.umi_mismatch ? merged_clusters : clusters.count;
         fqd_near_umi_info merged{};
         {
@@ -368,13 +376,9 @@ struct OrderedResidentRun {
                                       std::to_string(merged.near.max_group) + " is compared (adapter dimers, amplicons: trim the reads, or run without the switch)");
             if (merged.near.nodes != clusters.count) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
             if (merged.near.nodes - merged.links != before) throw DeviceError("GPU engine: internal error (the links and the merged UMI clusters differ in number)");
-            links.owner.swap(merged_owner);                          // (the exact owners leave with this stage, or stay for the centroids)
-            keep_exact(links, merged_owner);
             links.umi_link.release(); links.umi_off.release();
-            engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
-            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
+            regroup_under(links, clusters, merged_owner, merged.near.merged, "merge");   // (the exact owners leave with this stage, or stay for the centroids)
         }
-        if (clusters.count != merged.near.merged) throw DeviceError("GPU engine: internal error (the merge and the second grouping count different clusters)");
         umi_near_taken = before - merged.near.merged;
         if (StageClock::on())
             std::cerr << "fast: UMI substitutions <= " << fast.umi_hamming << ", " << umi_near_taken << " of " << before << " clusters merged into others, " << merged.near.pairs
@@ -383,8 +387,7 @@ struct OrderedResidentRun {
     }
 
     // FQD_FAST_OPTICAL, behind the grouping (and the merges, where they run): fqd_optical_split makes of every cluster its
-    // optical groups, each owned by its first member; the split owners are THE owners from here on, fqd_owners_to_keep makes
-    // the flags of them and fqd_group_owners groups the records once more.  The places leave with this stage.
+    // optical groups, each owned by its first member; regroup_under makes the split owners THE owners.  The places leave with this stage.
     void split_optical(Links& links, Clusters& clusters)
     {
         Device<uint32_t> split_owner;
@@ -399,12 +402,8 @@ struct OrderedResidentRun {
                                       std::to_string(split.over_limit_members) + " identical reads, a cluster of at most " + std::to_string(split.max_cluster) +
                                       " is split (untrimmed poly-G and the like: trim the reads first)");
             if (split.clusters_in != clusters.count) throw DeviceError("GPU engine: internal error (the split and the grouping count different clusters)");
-            links.owner.swap(split_owner);                           // (the owners by key leave with this stage)
-            keep_exact(links, split_owner);                          // (behind a merge: its exact owners are held already)
-            engine_ok<DeviceError>(e, fqd_owners_to_keep(e, links.owner.p, n, keep.p));
-            engine_ok<DeviceError>(e, fqd_group_owners(e, links.owner.p, n, clusters.perm.p, clusters.head.p, &clusters.count));
+            regroup_under(links, clusters, split_owner, split.clusters_out, "split");   // (the owners by key leave with this stage; behind a merge its exact owners are held already)
         }
-        if (clusters.count != split.clusters_out) throw DeviceError("GPU engine: internal error (the split and the second grouping count different clusters)");
         optical_more = split.clusters_out - split.clusters_in;
         if (StageClock::on())
             std::cerr << "fast: optical duplicates within " << fast.optical << " pixels, " << split.split << " of " << split.clusters_in << " clusters split, " << optical_more

@@ -152,6 +152,32 @@ def test_all_classes_in_one_call_and_the_info():
     assert all(info["tier_clusters"]) and info["mixed"] > 20 and info["largest"] == 2 * LIMIT + 100
 
 
+def big_grouping():
+    """(perm, head, label) of 1024 tiles of 2048 places, one tile and three places more: clusters of one but for five mixed ones."""
+    edge = 1024 * 2048
+    n = edge + 2048 + 3
+    # (first place, members): near the front; ending two places short of the round's edge; from there across that edge; 1000
+    # places behind the edge; across the last tile's edge
+    runs = [(100, 3), (edge - 2 - 40, 40), (edge - 2, 5), (edge + 1000, 300), (n - 9, 9)]
+    perm = np.arange(n - 1, -1, -1, dtype=np.uint32)             # place k holds record n - 1 - k
+    head = np.ones(n, np.uint8)
+    label = np.arange(n, dtype=np.uint32)
+    for at, m in runs:
+        head[at + 1:at + m] = 0
+        label[perm[at:at + m]] = np.where(np.arange(m) % 3 == 0, 5, 6)   # a third of the members under one label, the rest under another
+    return perm, head, label
+
+
+def test_more_places_than_the_tile_scans_first_round():
+    """The one block that scans the head counts takes 1024 tiles of 2048 places a round: the smallest grouping that reaches the
+    second round.  The four mixed clusters lie near the front, up to two places short of the round's edge, 1000 places behind
+    it and across the last tile's edge; a fifth starts where the second ends and lies across the round's edge itself."""
+    perm, head, label = big_grouping()
+    with Engine(segments=1) as e:
+        _, want = check_sizes(e, perm, head, label, None)
+    assert sorted(set(want.tolist())) == [1, 2, 3, 6, 14, 26, 100, 200]   # every mixed cluster's two sub-clusters, and the ones
+
+
 def test_a_mixed_call_inside_guards():
     """Every buffer of the two calls in one guarded arena: a store outside abundance or masked shows."""
     rng = np.random.default_rng(9)
