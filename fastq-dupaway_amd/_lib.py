@@ -94,6 +94,12 @@ class NearUmiInfo(C.Structure):                              # fqd_near_umi_info
     _fields_ = [("near", NearInfo), ("links", C.c_uint64), ("reserved", C.c_uint64)]
 
 
+class PrefixInfo(C.Structure):                               # fqd_prefix_info
+    _fields_ = [(name, C.c_uint64) for name in ("nodes", "eligible", "merged", "groups", "pairs", "related", "children", "largest_group", "deepest", "jumps",
+                                                "over_limit_first", "over_limit_nodes")] + [("max_group", C.c_uint32), ("reserved", C.c_uint32),
+                                                                                            ("stage_ms", C.c_float * 3)]
+
+
 class ConsensusInfo(C.Structure):                            # fqd_consensus_info
     _fields_ = [(name, C.c_uint64) for name in ("clusters", "members", "bases_changed", "reads_changed", "largest")]
 
@@ -106,6 +112,8 @@ class CentroidInfo(C.Structure):                             # fqd_centroid_info
 CENTROID_BLOCK_LIMIT = 2048                                  # csrc/fqd_centroid_core.hpp: kBlockLimit
 NEAR_MAX_GROUP = 4096
 NEAR_WEAK_SEEDS = 1
+PREFIX_MAX_GROUP = 4096
+PREFIX_WEAK_SEEDS = 1
 CONSENSUS_SMALL_TIERS = 1
 UMI_NO_RECORD = 0xFFFFFFFFFFFFFFFF
 PLACE_OK, PLACE_FEW_FIELDS, PLACE_EMPTY_FIELD, PLACE_NOT_DIGIT, PLACE_TOO_LONG, PLACE_BAD_END = range(6)
@@ -215,6 +223,7 @@ def load_library():
     L.fqd_read_places.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp, C.POINTER(PlacesInfo)]
     L.fqd_optical_split.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, vp, C.POINTER(OpticalInfo)]
     L.fqd_near_merge.argtypes = [vp, C.POINTER(ReadsDesc), vp, u64, u32, u32, vp, C.POINTER(NearInfo)]
+    L.fqd_prefix_merge.argtypes = [vp, C.POINTER(ReadsDesc), vp, u64, u32, u32, vp, vp, C.POINTER(PrefixInfo)]
     L.fqd_near_merge_umi.argtypes = [vp, C.POINTER(ReadsDesc), vp, vp, u64, u32, u32, vp, vp, vp, C.POINTER(UmiInfo), vp, C.POINTER(NearUmiInfo)]
     L.fqd_consensus.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, vp, u32, vp, C.POINTER(ConsensusInfo)]
     L.fqd_subcluster_sizes.argtypes = [vp, vp, vp, vp, vp, u64, vp, C.POINTER(CentroidInfo)]

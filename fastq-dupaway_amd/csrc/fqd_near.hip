@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "fqd_groups.hpp"
 #include "fqd_internal.hpp"
 #include "fqd_near_core.hpp"
 #include "fqd_near_umi_core.hpp"
@@ -67,7 +68,6 @@ struct Tags {
     __device__ __forceinline__ const uint8_t* at(uint32_t r) const { return text + id_start[r] + umi_off[r]; }
 };
 
-using fqdwave::wave_max;
 using fqdwave::wave_sum;
 
 // ---- seeds -------------------------------------------------------------------------------------------------------------------
@@ -165,60 +165,14 @@ void links_kernel(const uint32_t* __restrict__ owner, const uint32_t* __restrict
 
 // ---- groups ------------------------------------------------------------------------------------------------------------------
 
-// The first place behind e whose key is not keys[e] (N where there is none): a gallop, then a binary search.
-__device__ __forceinline__ uint64_t group_end(const uint64_t* __restrict__ keys, uint64_t N, uint64_t e)
-{
-    const uint64_t key = keys[e];
-    uint64_t lo = e, step = 1;                               // keys[lo] == key
-    while (lo + step < N && keys[lo + step] == key) { lo += step; step <<= 1; }
-    uint64_t hi = lo + step < N ? lo + step : N;             // keys[hi] != key, or hi == N
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (keys[mid] == key) lo = mid; else hi = mid;
-    }
-    return hi;
-}
+// group_end over the sorted keys: fqd_groups_core.hpp; the pass that marks the groups: fqd_groups.hpp.
+using fqdgroups::group_end;
 
-// The first place of e's group.
-__device__ __forceinline__ uint64_t group_start(const uint64_t* __restrict__ keys, uint64_t e)
-{
-    const uint64_t key = keys[e];
-    uint64_t hi = e, step = 1;                               // keys[hi] == key
-    while (hi >= step && keys[hi - step] == key) { hi -= step; step <<= 1; }
-    uint64_t lo = hi >= step ? hi - step : 0;                // keys[lo] != key, or lo == 0
-    if (keys[lo] == key) return lo;                          // (lo == 0)
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (keys[mid] == key) hi = mid; else lo = mid;
-    }
-    return hi;
-}
-
-// A lane an entry, no stride (the wave's sums).  work: room for N places — the entries that have a later entry in their group.
+// A lane an entry, no stride (fqdgroups::mark_groups).  work: room for N places — the entries that have a later entry in their group.
 __global__ __launch_bounds__(kBlock)
 void mark_kernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint64_t N, uint64_t* __restrict__ work, Counters* counters)
 {
-    const uint64_t e = blockIdx.x * uint64_t(kBlock) + threadIdx.x;
-    const bool live = e < N;
-    uint64_t key = 0;
-    if (live) key = keys[e];
-    const bool first = live && (e == 0 || keys[e - 1] != key);
-    unsigned long long size = 0;
-    if (first) size = group_end(keys, N, e) - e;
-    constexpr uint64_t half = kMaxGroup / 2;
-    if (live && ((e >= half && keys[e - half] == key) || (e + half < N && keys[e + half] == key))) {
-        const unsigned long long all = group_end(keys, N, e) - group_start(keys, e);
-        if (all > kMaxGroup) atomicMin(&counters->over, (static_cast<unsigned long long>(vals[e]) << 32) | (all > 0xFFFFFFFFull ? 0xFFFFFFFFull : all));
-    }
-    const unsigned long long groups = static_cast<unsigned long long>(__popcll(__ballot(first)));
-    const unsigned long long largest = wave_max(size);
-    const bool followed = live && e + 1 < N && keys[e + 1] == key;
-    const unsigned long long at = fqdwave::ballot_append(followed, &counters->work);
-    if (followed && at < N) work[at] = e;
-    if ((threadIdx.x & 63) == 0) {
-        if (groups) atomicAdd(&counters->groups, groups);
-        if (largest) atomicMax(&counters->largest, largest);
-    }
+    fqdgroups::mark_groups<kMaxGroup>(keys, vals, N, blockIdx.x * uint64_t(kBlock) + threadIdx.x, work, counters);
 }
 
 // ---- verify ------------------------------------------------------------------------------------------------------------------

@@ -414,6 +414,20 @@ class Engine:
                                                self._p(owner_out), C.byref(got) if out else None))
         return got
 
+    # -- FQD_FAST_PREFIX (csrc/fqd_prefix.hip) ------------------------------------------------------------------
+    def prefix_merge(self, segs: Sequence[Reads], owner, n: int, min_overlap: int, owner_out, span_out=None, flags: int = 0, out=True):
+        """owner_out[i] (n uint32, device) = the first record of record i's merged cluster: every exact cluster of `owner`
+        (owners' over the same n records of segs, device memory) whose mates have at least `min_overlap` bytes goes to the
+        shortest such cluster it is a prefix of, mate by mate (the lowest record among equals).  span_out (n uint32, device, or
+        None): len1 + len2 of every record.  flags: 0 or _lib.PREFIX_WEAK_SEEDS.  Returns the call's fqd_prefix_info
+        (_lib.PrefixInfo); out=None hands the library a null pointer, which it refuses."""
+        if segs is not None and len(segs) != self.segments:
+            raise ValueError(f"engine has {self.segments} mate(s) per record, got {len(segs)}")
+        got = _lib.PrefixInfo() if out else None
+        self._check(self._L.fqd_prefix_merge(self._h, self._desc(segs) if segs is not None else None, self._p(owner), n, min_overlap, flags,
+                                             self._p(owner_out), self._p(span_out), C.byref(got) if out else None))
+        return got
+
     # -- FQD_FAST_CONSENSUS (csrc/fqd_consensus.hip) -----------------------------------------------------------
     def consensus(self, perm, head, n: int, text, start, size, seq_off, seq_len, flags: int = 0, changed=None, info=True):
         """One file's text (device bytes, changed in place): the sequence and quality lines of the written member perm[head

@@ -48,6 +48,22 @@ uint32_t pixel_distance(const char* name)
     return zero ? 0 : size_bound(name, 0);
 }
 
+// FQD_FAST_PREFIX: a decimal integer in 1 .. 65535, and 0 (like unset) for off.
+uint32_t min_overlap(const char* name)
+{
+    const char* v = std::getenv(name);
+    if (!v) return 0;
+    uint32_t x = 0;
+    size_t digits = 0;
+    for (const char* p = v; *p; ++p, ++digits) {
+        if (*p < '0' || *p > '9' || digits >= 5) { digits = 0; break; }
+        x = x * 10 + uint32_t(*p - '0');
+    }
+    if (!digits || x > 65535 || (digits > 1 && v[0] == '0'))
+        throw std::runtime_error(std::string(name) + " must be a decimal integer in 1 .. 65535 (or 0 for off), not '" + v + "'");
+    return x;
+}
+
 } // namespace
 
 FastModes FastModes::from_env()
@@ -70,8 +86,11 @@ FastModes FastModes::from_env()
     m.optical = pixel_distance("FQD_FAST_OPTICAL");
     m.hamming = uint32_t(choice("FQD_FAST_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
     m.umi_hamming = uint32_t(choice("FQD_FAST_UMI_HAMMING", {"0", "1", "2", "3"}, "0, 1, 2 or 3"));
-    m.centroid = choice("FQD_FAST_CENTROID", {"first", "abundant"}, "'first' or 'abundant'") == 1;
+    const char* centroid = std::getenv("FQD_FAST_CENTROID");
+    m.longest = centroid && std::strcmp(centroid, "longest") == 0;
+    if (!m.longest) m.centroid = choice("FQD_FAST_CENTROID", {"first", "abundant"}, "'first' or 'abundant'") == 1;
     m.consensus = is_on("FQD_FAST_CONSENSUS");
+    m.prefix = min_overlap("FQD_FAST_PREFIX");
     return m;
 }
 
@@ -84,9 +103,10 @@ std::string FastModes::names() const
         {hamming != 0, hamming_name()},
         {optical != 0, optical_name()},
         {consensus, "FQD_FAST_CONSENSUS=1"},
-        {centroid, "FQD_FAST_CENTROID=abundant"},
+        {centroid, "FQD_FAST_CENTROID=abundant"}, {longest, "FQD_FAST_CENTROID=longest"},
         {size_out, "FQD_FAST_SIZEOUT=1"}, {levels, "FQD_FAST_LEVELS=1"}, {sort_by_size, "FQD_FAST_SORT=size"}, {size_in, "FQD_FAST_SIZEIN=1"},
-        {min_size > 1, "FQD_FAST_MINSIZE=" + std::to_string(min_size)}, {max_size != 0, "FQD_FAST_MAXSIZE=" + std::to_string(max_size)}};
+        {min_size > 1, "FQD_FAST_MINSIZE=" + std::to_string(min_size)}, {max_size != 0, "FQD_FAST_MAXSIZE=" + std::to_string(max_size)},
+        {prefix != 0, prefix_name()}};
     std::string s;
     for (const auto& one : all) if (one.first) s += (s.empty() ? "" : " and ") + one.second;
     return s;
@@ -128,6 +148,20 @@ void FastModes::check(bool unordered, size_t n_devices, Format format) const
         throw FastModeRefusal("FQD_FAST_KEEP=best needs the quality lines of FASTQ records: --format fasta has none");
     if (consensus && format == Format::Fasta)
         throw FastModeRefusal("FQD_FAST_CONSENSUS=1 with --format fasta: the vote weighs every base by its quality, and FASTA records have no quality lines");
+    if (prefix && hamming)
+        throw FastModeRefusal(prefix_name() + " with " + hamming_name() + ": a truncated copy with substituted bases inside the overlap is a rule of its own, and each of the "
+                              "two switches merges by its own rule alone");
+    if (prefix && umi)
+        throw FastModeRefusal(prefix_name() + " with " + umi_name() + (umi_mismatch ? " and " + mismatch_name() : std::string()) + (umi_hamming ? " and " + umi_hamming_name() : std::string()) +
+                              ": which sequences under one UMI are copies of one molecule is a rule of its own, and this switch merges by sequence alone");
+    if (prefix && both_strands)
+        throw FastModeRefusal(prefix_name() + " with FQD_FAST_STRAND=both: a truncated read's reverse complement is a suffix of its untrimmed copy's, not a prefix, so the two "
+                              "would be keyed in orientations that are never compared");
+    if (prefix && consensus)
+        throw FastModeRefusal(prefix_name() + " with FQD_FAST_CONSENSUS=1: the members of a merged cluster differ in length, and a column-wise vote needs members of one length");
+    if (longest && !prefix)
+        throw FastModeRefusal("FQD_FAST_CENTROID=longest chooses the sequence that all others of a merged cluster are prefixes of, and nothing else: set FQD_FAST_PREFIX as well, "
+                              "which merges them (FQD_FAST_CENTROID=abundant goes with the other merging switches)");
 }
 
 std::string FastModes::out_of_memory_note() const
@@ -172,6 +206,12 @@ std::string FastModes::out_of_memory_note() const
     if (centroid)
         s += "; FQD_FAST_CENTROID takes 4 bytes a record for the exact owners kept beside the merged ones and, while it chooses, 4 bytes a record for the "
              "abundances, about 5 bytes a record of scratch and 32 bytes for every member of a cluster above 2048";
+    if (prefix)
+        s += "; FQD_FAST_PREFIX takes 4 bytes a record for the merged owners and, while it merges, 24 bytes an exact cluster for the seeds and their sort (12 bytes a seed, "
+             "one seed a cluster of at least " + std::to_string(prefix) + " bases a mate, twice over), 8 bytes a record for the parents and 4 bytes a record for the roots";
+    if (longest)
+        s += "; FQD_FAST_CENTROID=longest takes 4 bytes a record for the exact owners kept beside the merged ones and 4 bytes a record for the lengths, and, while it chooses, "
+             "about 5 bytes a record of scratch";
     return s;
 }
 

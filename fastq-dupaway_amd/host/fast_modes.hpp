@@ -1,4 +1,4 @@
-// fast_modes.hpp — the sixteen FQD_FAST_* switches of the `--fast` mode as one value: read from the environment in one place
+// fast_modes.hpp — the seventeen FQD_FAST_* switches of the `--fast` mode as one value: read from the environment in one place
 // (FastModes::from_env), checked against the command line before any GPU call (check), and asked by the run
 // (run_resident.cpp) through the predicates below.  Also the words of every refusal the switches can cause.
 // Plain C++: no HIP, nothing of run_common.hpp.
@@ -34,20 +34,23 @@ struct FastModes {
     uint32_t umi_hamming = 0;    // FQD_FAST_UMI_HAMMING=D in 1 .. 3 (unset and 0: off; needs FQD_FAST_UMI): exact clusters under ONE UMI, of one shape, whose sequences differ in at most D substituted bases a mate are one molecule, by single linkage, together with FQD_FAST_UMI_MISMATCH's clusters; its first record is written (csrc/fqd_near_umi_core.hpp)
     bool centroid = false;       // FQD_FAST_CENTROID=first|abundant: abundant: a merged cluster is written by the first copy of its most abundant exact sequence (UMI and sequence), not by its first record (csrc/fqd_centroid_core.hpp)
     bool consensus = false;      // FQD_FAST_CONSENSUS=1: the sequence and quality lines of every cluster's written member are replaced by the cluster's column-wise consensus (csrc/fqd_consensus_core.hpp)
+    bool longest = false;        // FQD_FAST_CENTROID=longest (the variable's third value; needs FQD_FAST_PREFIX): a merged cluster is written by the first copy of its root sequence, the one all its members are prefixes of
+    uint32_t prefix = 0;         // FQD_FAST_PREFIX=L in 1 .. 65535 (unset and 0: off): an exact cluster whose reads are prefixes of another's, over at least L bases a mate, goes to the shortest such cluster; a tree of that relation is one cluster and its first record is written (csrc/fqd_prefix_core.hpp)
 
-    // Reads the sixteen variables.  Throws std::runtime_error on a value that is none of the above, and FastModeRefusal for
+    // Reads the seventeen variables.  Throws std::runtime_error on a value that is none of the above, and FastModeRefusal for
     // a MAXSIZE below MINSIZE, in the order KEEP, SORT, MINSIZE, MAXSIZE, MAXSIZE below MINSIZE, STRAND, UMI, UMI_MISMATCH,
-    // OPTICAL, HAMMING, UMI_HAMMING, CENTROID.
+    // OPTICAL, HAMMING, UMI_HAMMING, CENTROID, PREFIX.  (CENTROID's words for a bad value name the two values it had first.)
     static FastModes from_env();
     // What the values and the command line decide, before any GPU call; throws FastModeRefusal.  In this order: SIZEIN with
     // nothing that reads sizes, UMI_MISMATCH without UMI, HAMMING with STRAND=both, HAMMING with UMI, UMI_HAMMING without UMI,
     // UMI_HAMMING with STRAND=both, CONSENSUS with STRAND=both, CONSENSUS with SIZEIN, CENTROID=abundant with no merging switch,
-    // `--unordered`, several devices, KEEP=best with FASTA, CONSENSUS with FASTA.
+    // `--unordered`, several devices, KEEP=best with FASTA, CONSENSUS with FASTA, PREFIX with HAMMING, PREFIX with UMI (and so
+    // with the two UMI merges), PREFIX with STRAND=both, PREFIX with CONSENSUS, CENTROID=longest without PREFIX.
     void check(bool unordered, size_t n_devices, Format format) const;
 
     bool size_filter() const { return min_size > 1 || max_size != 0; }                 // a bound that can take a cluster out
     bool sized() const { return size_out || levels || sort_by_size || size_filter(); } // something reads the cluster sizes
-    bool linked() const { return keep_best || clusters || umi_mismatch || umi_hamming || optical || hamming || consensus || centroid || sized(); }   // the duplicates must be linked to their clusters
+    bool linked() const { return keep_best || clusters || umi_mismatch || umi_hamming || optical || hamming || consensus || centroid || longest || prefix || sized(); }   // the duplicates must be linked to their clusters
     bool any() const { return linked() || both_strands || umi; }                       // only the GPU-resident ordered run will do
 
     // The switches that are set, as the messages name them: "FQD_FAST_KEEP=best and FQD_FAST_UMI=colon"; "" for none.
@@ -56,7 +59,9 @@ struct FastModes {
     std::string mismatch_name() const { return umi_mismatch ? "FQD_FAST_UMI_MISMATCH=" + std::to_string(umi_mismatch) : std::string(); }
     std::string hamming_name() const { return hamming ? "FQD_FAST_HAMMING=" + std::to_string(hamming) : std::string(); }
     std::string umi_hamming_name() const { return umi_hamming ? "FQD_FAST_UMI_HAMMING=" + std::to_string(umi_hamming) : std::string(); }
-    bool merges() const { return umi_mismatch || hamming || umi_hamming; }               // a cluster may hold several exact sequences
+    std::string prefix_name() const { return prefix ? "FQD_FAST_PREFIX=" + std::to_string(prefix) : std::string(); }
+    bool merges() const { return umi_mismatch || hamming || umi_hamming || prefix; }     // a cluster may hold several exact sequences
+    bool picks_centroid() const { return centroid || longest; }                          // another sequence than the first record's may be written: the exact owners stay
     std::string optical_name() const { return optical ? "FQD_FAST_OPTICAL=" + std::to_string(optical) : std::string(); }
     // What did not fit when the GPU-resident run meets the end of HBM, for the refusal.
     std::string out_of_memory_note() const;

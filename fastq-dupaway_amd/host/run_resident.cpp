@@ -76,8 +76,9 @@ struct KeyedReads {
 struct Links { Device<uint32_t> link, owner; Device<uint32_t> umi_off, umi_link, exact; fqd_umi_info umi_info{}; };
 // The records grouped by owner: an order of the n records and a flag at the first place of every cluster; with
 // FQD_FAST_SIZEIN what every record stands for, while sizes are made.  Until the outputs are planned.
-// With FQD_FAST_CENTROID=abundant the exact owners, until the centroids are picked.
-struct Clusters { Device<uint32_t> perm; Device<uint8_t> head; Device<uint32_t> weight, exact; uint64_t count = 0; };
+// With FQD_FAST_CENTROID=abundant or =longest the exact owners, and with =longest every record's span (fqd_prefix_merge's
+// span_out), until the centroids are picked.
+struct Clusters { Device<uint32_t> perm; Device<uint8_t> head; Device<uint32_t> weight, exact, span; uint64_t count = 0; };
 // FQD_FAST_OPTICAL: where on the flow cell every record was read (fqd_read_places over file 1's ID lines), until the clusters
 // are split.
 struct Places {
@@ -97,8 +98,9 @@ struct OrderedResidentRun {
     uint64_t merged_clusters = 0;                                // FQD_FAST_UMI_MISMATCH: the clusters the merge leaves
     uint64_t near_taken = 0;                                     // FQD_FAST_HAMMING: the exact clusters that went into another
     uint64_t umi_near_taken = 0;                                 // FQD_FAST_UMI_HAMMING: the clusters in front of the stage that went into another
+    uint64_t prefix_taken = 0;                                   // FQD_FAST_PREFIX: the exact clusters that went into another
     Places places; uint64_t optical_more = 0;                    // FQD_FAST_OPTICAL: the places; the clusters the split adds
-    uint64_t centroid_moved = 0;                                 // FQD_FAST_CENTROID=abundant: the clusters written by another sequence than their first member's
+    uint64_t centroid_moved = 0;                                 // FQD_FAST_CENTROID=abundant / =longest: the clusters written by another sequence than their first member's
     uint64_t consensus_bases = 0, consensus_reads = 0;           // FQD_FAST_CONSENSUS: the bases replaced, and the records (pairs) that hold them
     std::string cluster_text[2];                                 // FQD_FAST_CLUSTERS
     Device<uint32_t> cluster_size; fqd_size_levels levels{};     // FQD_FAST_SIZEOUT / _LEVELS / _SORT / _MINSIZE / _MAXSIZE
@@ -288,14 +290,14 @@ struct OrderedResidentRun {
         else { links.owner.swap(merged_owner); keep_exact(links, merged_owner); }   // (the exact owners leave with this stage, or stay for the centroids)
     }
 
-    // FQD_FAST_CENTROID=abundant: `replaced` holds the owners a stage has just replaced.  Those of the FIRST stage that replaces any
+    // FQD_FAST_CENTROID=abundant / =longest: `replaced` holds the owners a stage has just replaced.  Those of the FIRST stage that replaces any
     // are the owners by exact key, and stay; a later stage's (the optical split behind a merge) are merged ones, and leave.
     void keep_exact(Links& links, Device<uint32_t>& replaced)
     {
-        if (fast.centroid && !links.exact.p) links.exact.swap(replaced);
+        if (fast.picks_centroid() && !links.exact.p) links.exact.swap(replaced);
     }
 
-    // The tail of merge_near, merge_near_umi and split_optical: new_owner become THE owners (the replaced ones leave with the
+    // The tail of merge_near, merge_near_umi, merge_prefixes and split_optical: new_owner become THE owners (the replaced ones leave with the
     // caller's buffer, or stay for the centroids), fqd_owners_to_keep makes the flags of them and fqd_group_owners groups the
     // records once more, into the clusters the stage counted.  what: "merge" / "split", for the message.
     void regroup_under(Links& links, Clusters& clusters, Device<uint32_t>& new_owner, uint64_t expected, const char* what)
@@ -323,9 +325,10 @@ struct OrderedResidentRun {
         }
         if (fast.hamming) { merge_near(links, clusters); dups = n - clusters.count; }
         if (fast.umi_hamming) { merge_near_umi(links, clusters); dups = n - clusters.count; }
+        if (fast.prefix) { merge_prefixes(links, clusters); dups = n - clusters.count; }
         if (fast.optical) { split_optical(links, clusters); dups = n - clusters.count; }
         if (clusters.count + dups != n) throw DeviceError("GPU engine: internal error (the clusters and the duplicates do not add up to the records)");
-        if (fast.centroid) clusters.exact.swap(links.exact);         // (check() has seen to it that a merge ran)
+        if (fast.picks_centroid()) clusters.exact.swap(links.exact); // (check() has seen to it that a merge ran)
     }
 
     // FQD_FAST_HAMMING, behind the grouping: fqd_near_merge makes of the exact clusters — the reads as they lie in the files, the
@@ -384,6 +387,35 @@ struct OrderedResidentRun {
             std::cerr << "fast: UMI substitutions <= " << fast.umi_hamming << ", " << umi_near_taken << " of " << before << " clusters merged into others, " << merged.near.pairs
                       << " pairs compared, " << merged.near.edges << " near, " << merged.links << " links, largest seed group " << merged.near.largest_group << ", "
                       << merged.near.sweeps << " sweeps\n";
+    }
+
+    // FQD_FAST_PREFIX, behind the grouping, where merge_near stands (check() sees to it that the two never run together):
+    // fqd_prefix_merge makes of the exact clusters — the reads as they lie in the files, the owners by key — the trees of the
+    // prefix relation, each owned by its first record; regroup_under makes the merged owners THE owners.  With
+    // FQD_FAST_CENTROID=longest every record's span comes back with them, for pick_centroids.
+    void merge_prefixes(Links& links, Clusters& clusters)
+    {
+        Device<uint32_t> merged_owner;
+        merged_owner.reserve(n);
+        if (fast.longest) clusters.span.reserve(n);
+        const fqd_reads reads[2] = {reads_as_they_lie(0), S == 2 ? reads_as_they_lie(1) : fqd_reads{}};
+        fqd_prefix_info merged{};
+        {
+            StageClock::Scope t("fast: prefixes, exact clusters merged on the GPU");
+            engine_ok<DeviceError>(e, fqd_prefix_merge(e, reads, links.owner.p, n, fast.prefix, 0, merged_owner.p, fast.longest ? clusters.span.p : nullptr, &merged));
+            if (merged.over_limit_first != FQD_UMI_NO_RECORD)
+                throw FastModeRefusal(fast.prefix_name() + ": " + std::to_string(merged.over_limit_nodes) + " different sequences, the one of record " +
+                                      std::to_string(merged.over_limit_first) + " (counted from 0) of " + in[0] + " the first among them, begin with the same " +
+                                      std::to_string(fast.prefix) + (S == 1 ? " bases" : " bases in each mate") + "; a group of at most " + std::to_string(merged.max_group) +
+                                      " is compared (adapter dimers, amplicons: set a larger FQD_FAST_PREFIX, or trim the reads first)");
+            if (merged.nodes != clusters.count) throw DeviceError("GPU engine: internal error (the merge and the grouping count different exact clusters)");
+            regroup_under(links, clusters, merged_owner, merged.merged, "merge");   // (the owners by key leave with this stage, or stay for the centroids)
+        }
+        prefix_taken = merged.nodes - merged.merged;
+        if (StageClock::on())
+            std::cerr << "fast: prefixes >= " << fast.prefix << ", " << prefix_taken << " of " << merged.nodes << " exact clusters merged into others, " << merged.pairs
+                      << " pairs compared, " << merged.related << " related, largest seed group " << merged.largest_group << ", deepest chain " << merged.deepest << ", "
+                      << merged.jumps << " jumps\n";
     }
 
     // FQD_FAST_OPTICAL, behind the grouping (and the merges, where they run): fqd_optical_split makes of every cluster its
@@ -450,19 +482,31 @@ struct OrderedResidentRun {
     // abundant at the head's place.  With FQD_FAST_KEEP=best the scores are then masked to that sequence's copies
     // (fqd_subcluster_scores) and picked from in place of the pick over the whole cluster.  The exact owners and the
     // abundances leave with this stage.
+    // FQD_FAST_CENTROID=longest (with FQD_FAST_PREFIX): the spans stand in the place of the abundances — a span is constant on
+    // an exact sub-cluster and a tree's largest is its root's alone, so the same pick puts the first copy of the root sequence at
+    // the head's place — and everything behind the pick is the same.
     void pick_centroids(Clusters& c)
     {
-        fqd_centroid_info found{};
-        {
-            StageClock::Scope t("fast: most abundant sequence on the GPU");
-            Device<uint32_t> abundance;
-            abundance.reserve(n);
-            engine_ok<DeviceError>(e, fqd_subcluster_sizes(e, c.perm.p, c.head.p, c.exact.p, fast.size_in ? c.weight.p : nullptr, n, abundance.p, &found));
-            engine_ok<DeviceError>(e, fqd_seq_pick_best(e, abundance.p, c.head.p, n, c.perm.p, &centroid_moved));
+        if (fast.longest) {
+            {
+                StageClock::Scope t("fast: longest sequence on the GPU");
+                engine_ok<DeviceError>(e, fqd_seq_pick_best(e, c.span.p, c.head.p, n, c.perm.p, &centroid_moved));
+            }
+            c.span.release();
+            if (StageClock::on()) std::cerr << "fast: longest sequence, " << centroid_moved << " of " << c.count << " clusters changed\n";
+        } else {
+            fqd_centroid_info found{};
+            {
+                StageClock::Scope t("fast: most abundant sequence on the GPU");
+                Device<uint32_t> abundance;
+                abundance.reserve(n);
+                engine_ok<DeviceError>(e, fqd_subcluster_sizes(e, c.perm.p, c.head.p, c.exact.p, fast.size_in ? c.weight.p : nullptr, n, abundance.p, &found));
+                engine_ok<DeviceError>(e, fqd_seq_pick_best(e, abundance.p, c.head.p, n, c.perm.p, &centroid_moved));
+            }
+            if (StageClock::on())
+                std::cerr << "fast: most abundant sequence, " << centroid_moved << " of " << c.count << " clusters changed, " << found.mixed << " mixed clusters, "
+                          << found.subclusters << " sub-clusters, largest cluster " << found.largest << "\n";
         }
-        if (StageClock::on())
-            std::cerr << "fast: most abundant sequence, " << centroid_moved << " of " << c.count << " clusters changed, " << found.mixed << " mixed clusters, " << found.subclusters
-                      << " sub-clusters, largest cluster " << found.largest << "\n";
         if (fast.keep_best) {
             StageClock::Scope t("fast: best-quality pick on the GPU");
             fqd_tags recs[2];
@@ -487,7 +531,7 @@ struct OrderedResidentRun {
     // records that stay in order of decreasing cluster size.  The sizes stay for the writer with FQD_FAST_SIZEOUT only.
     void pick_size_filter_order(Clusters& c)
     {
-        if (fast.centroid) pick_centroids(c);
+        if (fast.picks_centroid()) pick_centroids(c);
         else if (fast.keep_best) {
             const uint64_t moved = pick_best_members(e, S, files, n, c.head.p, c.perm.p, "fast: best-quality pick on the GPU");
             engine_ok<DeviceError>(e, fqd_heads_to_keep(e, c.perm.p, c.head.p, n, keep.p));
@@ -561,7 +605,7 @@ struct OrderedResidentRun {
 
 } // namespace
 
-// Everything about the sixteen switches that their values and the command line decide, before any GPU call.
+// Everything about the seventeen switches that their values and the command line decide, before any GPU call.
 void HashDupRemover::read_fast_modes(bool unordered)
 {
     fast_ = FastModes::from_env();
@@ -639,6 +683,11 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
     if (verbose_ && fast_.umi_hamming)
         std::cout << run.umi_near_taken << (S == 1 ? " distinct sequences" : " distinct sequence pairs") << " under one UMI were taken for copies of another that differs in at most "
                   << fast_.umi_hamming << (S == 1 ? " bases (" : " bases a mate (") << fast_.umi_hamming_name() << ").\n";
+    // FQD_FAST_PREFIX: what `-v` says behind its first line, which counts every record that was not written
+    if (verbose_ && fast_.prefix)
+        std::cout << run.prefix_taken << (S == 1 ? " distinct sequences" : " distinct sequence pairs") << " were taken for copies of a longer " << (S == 1 ? "sequence" : "sequence pair")
+                  << " that begins with them" << (S == 1 ? "" : ", mate by mate") << ", over at least " << fast_.prefix << (S == 1 ? " bases (" : " bases a mate (") << fast_.prefix_name()
+                  << ").\n";
     // FQD_FAST_OPTICAL: what `-v` says behind its first line, which counts the optical duplicates only
     if (verbose_ && fast_.optical)
         std::cout << run.optical_more << (S == 1 ? " reads" : " read pairs") << " that repeat an earlier sequence were written: not optical duplicates (" << fast_.optical_name() << ").\n";
@@ -651,6 +700,9 @@ bool HashDupRemover::run_ordered_resident(int S, const std::string* in, const st
         std::cout << run.centroid_moved << " clusters were written by a copy of their most abundant " << (S == 1 ? "sequence" : "sequence pair") << ", not by their first "
                   << (S == 1 ? "read" : "read pair") << " (FQD_FAST_CENTROID=abundant).\n";
     // FQD_FAST_CONSENSUS: what `-v` says behind those
+    if (verbose_ && fast_.longest)
+        std::cout << run.centroid_moved << " clusters were written by a copy of their longest " << (S == 1 ? "sequence" : "sequence pair") << ", not by their first "
+                  << (S == 1 ? "read" : "read pair") << " (FQD_FAST_CENTROID=longest).\n";
     if (verbose_ && fast_.consensus)
         std::cout << run.consensus_bases << " bases in " << run.consensus_reads << (S == 1 ? " reads" : " read pairs") << " were replaced by their cluster's consensus (FQD_FAST_CONSENSUS=1).\n";
     return true;

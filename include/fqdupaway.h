@@ -994,6 +994,51 @@ int  fqd_near_merge_umi(fqd_engine* e, const fqd_reads* reads, const uint32_t* o
                         const uint8_t* text, const uint64_t* id_start, const uint32_t* umi_off, const fqd_umi_info* info,
                         uint32_t* owner_out, fqd_near_umi_info* out);
 
+/* ---- FQD_FAST_PREFIX=L: exact clusters that are prefixes of another, over at least L bases a mate, are copies of it (added
+ * within ABI version 5: purely additive; no existing entry launches anything new).  Rule and proofs: csrc/fqd_prefix_core.hpp.
+ * A node is one exact cluster (a record with owner[i] == i); span = len1 + len2.  a is a prefix of b when len1(a) <= len1(b), the
+ * bytes of a's mate 1 are the first len1(a) bytes of b's and, for pairs, the same holds for mate 2 (same-sided: a pair with the
+ * shorter mate 1 and the longer mate 2 is not related); 'N' is a letter like any other.  A node is eligible when every mate has
+ * at least L bytes; a node that is not stays a cluster of its own.  An eligible node's parent is, among the eligible nodes it is
+ * a prefix of, the one with the least span and among those the lowest record.  A merged cluster is one tree of the parent
+ * relation, owned by its first record in input order: every member is a prefix of the tree's root, and two roots are never in
+ * one cluster (this is NOT single linkage).
+ *
+ * fqd_prefix_merge: device memory only (out: host, not NULL).  reads = the engine's segments (1 or 2), ragged or uniform, over
+ * n < 2^31 records; owner = fqd_owners' over the same records.  min_overlap = L, 1 .. 65535 (anything else: FQD_ERR_ARG); flags =
+ * 0 or FQD_PREFIX_WEAK_SEEDS.  owner_out[i] (n uint32) = the first record of record i's merged cluster; fqd_group_owners and
+ * fqd_owners_to_keep take it.  span_out[i] (n uint32, or NULL) = len1 + len2 of record i: constant on an exact cluster, and its
+ * maximum over a merged cluster is the root's alone, so fqd_seq_pick_best over it puts the first copy of the root sequence at
+ * the head's place.  Neither may overlap the other, owner, a segment's offsets or lengths, or the bases of a uniform segment
+ * (FQD_ERR_ARG).  An owner above its record, or one that is not its own owner, is FQD_ERR_ARG (counted on the device, nothing
+ * written); so is a mate of 2^31 bytes or more (a span fits 32 bits).  An eligible node's entry is (a 64-bit hash of paired?, L
+ * and the first L bytes of each mate; the node), and related nodes share a key.  The entries are sorted by key (the radix passes
+ * of the ID join); within a group of equal keys every pair of entries whose lengths allow a prefix — both mates <=, or both >=,
+ * and not one shape — is compared byte for byte over the short node's lengths, eight lanes a pair and sixteen bytes a lane, and
+ * a related pair offers (span(long) << 32 | long) to a 64-bit atomicMin at the short node: the parent.  Pointer jumping over the
+ * parents gives every node's root, an atomicMin over the nodes the first record of every tree.  *out: nodes; eligible; merged =
+ * the merged clusters (trees, and the nodes that are not eligible); groups = the seed groups; pairs = the pairs compared byte for
+ * byte; related = those found related; children = the nodes with a parent (nodes - merged); largest_group = the entries of the
+ * largest group; deepest = the longest parent chain in links, counted by a walk of every child's chain; jumps = the pointer
+ * jumps that changed something, ceil(log2(deepest)); max_group = FQD_PREFIX_MAX_GROUP.  A group of more entries than that is
+ * refused: over_limit_first = the lowest first record among the nodes of such a group (FQD_UMI_NO_RECORD: there is none),
+ * over_limit_nodes = that group's entries; the call returns FQD_OK, owner_out and span_out are unspecified, and merged, pairs,
+ * related, children, deepest and jumps are 0.  FQD_PREFIX_WEAK_SEEDS (tests) cuts every key to its low 4 bits: nodes that agree
+ * on nothing meet in one group, and the result is the same.  Scratch during the call: 24 bytes an entry for the sort, 8 bytes a
+ * record for the parents (then the trees' first records) and 4 bytes a record for the roots (owner_out holds the second array of
+ * the jumps).  Results come back after the counts, the groups, the verification and every jump; returns after the stream has
+ * drained.  stage_ms is a diagnostic (tools/prefix_probe.py): the wall time of seeds + sort + groups, of the verification and of
+ * the trees, launches and waits included. */
+#define FQD_PREFIX_MAX_GROUP 4096u
+#define FQD_PREFIX_WEAK_SEEDS 1u   /* test hook: seed keys cut to their low 4 bits */
+typedef struct fqd_prefix_info {
+    uint64_t nodes, eligible, merged, groups, pairs, related, children, largest_group, deepest, jumps, over_limit_first, over_limit_nodes;
+    uint32_t max_group, reserved;
+    float    stage_ms[3];
+} fqd_prefix_info;
+int  fqd_prefix_merge(fqd_engine* e, const fqd_reads* reads, const uint32_t* owner, uint64_t n, uint32_t min_overlap, uint32_t flags,
+                      uint32_t* owner_out, uint32_t* span_out /* may be NULL */, fqd_prefix_info* out);
+
 /* ---- FQD_FAST_CONSENSUS=1: the written member of every cluster carries the cluster's consensus (added within ABI version 5:
  * purely additive; no existing entry launches anything new).  Rule and proofs: csrc/fqd_consensus_core.hpp.  A cluster is a run
  * of (perm, head); its written member is perm[head place].  In every column p of a cluster of two or more members each member
